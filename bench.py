@@ -11,6 +11,11 @@ NUTS proposal -> re-weight -> commit, smc_sampler.py:109-140) over the resident
 particle shard.  W warm-up iterations advance the same chain untimed; then
 exactly K iterations are timed between barrier + device synchronisation on both
 sides; the maximum over ranks is taken and rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes what the last timed iteration left for the caller
+(particles and the scalar history of the timed generations, float64 .npy, at
+most 64 MB): the same arguments give the same inputs, so that two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -88,6 +93,48 @@ def cpu_baseline(x_state, model_data, seed, budget_s=6.0):
            "cpu_model": r["cpu_model"], "nproc": r["nproc"],
            "variants": {"c_all_cores": r["c_all_cores"], "python_serial_one_core": r["python_serial"]}}
     return out
+
+
+DUMP_BUDGET = 64 * 10 ** 6      # --dump-outputs: bytes of all .npy files together
+DUMP_SAMPLE_SEED = 20240607     # --dump-outputs: the particle rows kept when the population exceeds the budget
+
+
+def dump_outputs(out_dir, smc, ctx, comm, world, rank, W):
+    """--dump-outputs: what the timed path hands its caller after its last step, as float64 DIR/<name>.npy -- the particles
+    x, logw after the last timed iteration and the scalar history of the timed generations (mean_estimate,
+    variance_estimate, ess, log_likelihood, phi, acceptance_rate, resampled; leapfrogs per timed iteration).  A population
+    larger than the budget is written as a fixed, seeded sample of particle rows, the same on every run and shard
+    (particle_rows.npy: their global indices).  Every rank takes part (the shards are gathered); rank 0 writes."""
+    x, logw, _ = ctx.get_state()
+    n_local, D = x.shape
+    hist = dict(mean_estimate=smc.mean_estimate, variance_estimate=smc.variance_estimate, ess=smc.ess,
+                log_likelihood=smc.log_likelihood, phi=smc.phi, acceptance_rate=smc.acceptance_rate,
+                resampled=np.asarray(smc.resampled, dtype=np.float64))
+    row_bytes = 8 * (sum(v[0].size for v in hist.values()) + 1)          # one generation of every table (+ leapfrogs)
+    g0 = max(W, len(smc.ess) - (DUMP_BUDGET // 4) // row_bytes)           # (an enormous --steps: its last generations)
+    arrays = {k: np.asarray(v[g0:], dtype=np.float64) for k, v in hist.items()}
+    arrays["leapfrogs"] = np.asarray(smc.leapfrogs[g0:], dtype=np.float64)
+    room = DUMP_BUDGET - sum(a.nbytes for a in arrays.values()) - (1 << 20)  # (1 MiB for the .npy headers)
+    rows = None
+    if n_local * world * 8 * (D + 1) > room:
+        m = room // (8 * (D + 2)) // world
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_local, size=m, replace=False))
+        x, logw = x[rows], logw[rows]
+    if world > 1:
+        x = comm.allgather(x).reshape(-1, D)
+        logw = comm.allgather(logw).reshape(-1)
+    arrays["x"], arrays["logw"] = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(logw, dtype=np.float64)
+    if rows is not None:
+        arrays["particle_rows"] = (np.arange(world)[:, None] * n_local + rows[None, :]).reshape(-1).astype(np.float64)
+    if rank != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "generations": [int(g0), int(len(smc.ess) - 1)],
+            "particles": "all" if rows is None else f"{len(arrays['x'])} of {n_local * world} (seed {DUMP_SAMPLE_SEED})",
+            "files": {k: list(a.shape) for k, a in arrays.items()}}
 
 
 EXTRA_CONFIGS = {
@@ -252,7 +299,12 @@ def main():
     ap.add_argument("--backend", default="rccl",
                     help="shard exchange: rccl = the library's own RCCL communicator (default, no torch.distributed); "
                          "nccl = torch.distributed over RCCL; gloo = torch.distributed on the host (rehearsing ranks on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (particles and the scalar history of "
+                         "the timed generations) as float64 DIR/<name>.npy, at most 64 MB; same arguments, same inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` as the driver calls it: this process only starts the N ranks
@@ -423,6 +475,9 @@ def main():
         runs.append(dict(dt=dt, nuts_ms=float(tm[0]), launches=max(int(tm[1]), 1),
                          leaps=int(smc.leapfrogs[W:].sum())))
     assert len({r_["leaps"] for r_ in runs}) == 1, "the repeats did not do the same work"
+    dumped = None
+    if args.dump_outputs:       # the state of the last timed repeat, before anything below runs the chain again
+        dumped = dump_outputs(args.dump_outputs, smc, ctx, comm, world, rank, W)
     dt_pcie = None
     if args.history and keep_hist and world == 1:      # the same K iterations once more, x_saved / logw_saved downloaded inside the clock
         smc.restore(ck)
@@ -525,6 +580,8 @@ def main():
             "nuts_kernel_share_of_step": nuts_ms / 1e3 / dt,
             "pcie_inclusive_value": (leaps_total / dt_pcie) if dt_pcie else None,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and args.config in ("arma", "c5"):
             # second roofline entry: the resampling kernels (no generation of the timed steps resamples in steady
             # state), timed on the final weights: 28 + 8 log2(N) + 16 D algorithmic bytes per particle

@@ -17,6 +17,18 @@ def golden_dir():
     return os.path.join(ROOT, "tests", "golden")
 
 
+@pytest.fixture(scope="session")
+def gpu_present():
+    """Whether torch sees a GPU, asked in a child process.  torch carries a HIP runtime of its own; loaded after the
+    library's and initialised in this process, it takes the device, and the library's runtime finds none for the rest
+    of the session."""
+    import subprocess
+    p = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return p.stdout.strip().splitlines()[-1] == "1"
+
+
 def pytest_sessionfinish(session, exitstatus):
     """The GPU parity tests record how much of each tolerance they used (tests/_tol.py)."""
     try:

@@ -1,10 +1,11 @@
 """Generate the golden vectors under tests/golden/ by running the REAL reference.
 
-Run in the build container only (the reference does not travel):
+Run where a checkout of the reference is at hand (it is not needed anywhere else):
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+    SMCNUTS_REFERENCE=<checkout of UoL-SignalProcessingGroup/SMC-NUTS> \
+        PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 
-It imports /root/reference's `smcnuts` (SMCSampler, Samples, NUTSProposal,
+It imports the reference's `smcnuts` (SMCSampler, Samples, NUTSProposal,
 L-kernels, ESSTempering, Estimate -- all NumPy/SciPy) unchanged and drives it
 exactly as experiments/run_experiments.py:106-128 does (RandomState(10*(i+1)),
 N(0, I) sample and momentum proposals bound to the same RNG), with
@@ -26,7 +27,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+if not os.environ.get("SMCNUTS_REFERENCE"):
+    raise SystemExit("make_golden.py: set SMCNUTS_REFERENCE to a checkout of the reference (see the docstring)")
+sys.path.insert(0, os.environ["SMCNUTS_REFERENCE"])
 sys.dont_write_bytecode = True
 
 from scipy.stats import multivariate_normal  # noqa: E402

@@ -39,9 +39,8 @@ def test_product_does_not_import_oracle():
                 assert "oracle" not in src.replace("oracle.blocked_cumsum", ""), f"{f} mentions the oracle"
 
 
-def test_create_fails_loudly_without_gpu():
-    import torch
-    if torch.cuda.is_available():
+def test_create_fails_loudly_without_gpu(gpu_present):
+    if gpu_present:
         pytest.skip("GPU present")
     from smcnuts_amd import ArmaModel, SMCSampler
     from smcnuts_amd._capi import SmcnError

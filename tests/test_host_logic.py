@@ -116,12 +116,11 @@ def test_systematic_keys_properties():
             assert np.all(np.abs(np.bincount(idx, minlength=n) - n * w) < 1 + 1e-9)
 
 
-def test_host_targets_still_need_the_gpu_library():
+def test_host_targets_still_need_the_gpu_library(gpu_present):
     """A host-evaluated target only moves the DENSITY to the caller: without a GPU the
     sampler fails loudly at context creation (no CPU path); an object without the StanModel surface
     is refused up front."""
     from smcnuts_amd import SMCSampler
-    import torch
 
     class HostTarget:
         dim = 2
@@ -132,7 +131,7 @@ def test_host_targets_still_need_the_gpu_library():
 
     with pytest.raises(TypeError):
         SMCSampler(K=2, N=8, target=object(), step_size=0.1)
-    if not torch.cuda.is_available():
+    if not gpu_present:
         with pytest.raises(RuntimeError):
             SMCSampler(K=2, N=8, target=HostTarget(), step_size=0.1)
 

@@ -1,5 +1,6 @@
-import sys, time, runpy
-sys.path.insert(0, "/root/repo")
+import os, sys, time, runpy
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 from smcnuts_amd import _capi
 orig = _capi.Context.call
 T0 = time.perf_counter()
@@ -27,4 +28,4 @@ def run(self):
     print(f"[{1e3*(time.perf_counter()-T0):9.1f} ms] thread {self.name} ends after {1e3*(time.perf_counter()-t):.1f} ms", file=sys.stderr)
 threading.Thread.run = run
 sys.argv = ["bench.py"] + (sys.argv[1:] or ["--steps", "20", "--warmup", "5"]) + ["--no-cpu-baseline"]
-runpy.run_path("/root/repo/bench.py", run_name="__main__")
+runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")
