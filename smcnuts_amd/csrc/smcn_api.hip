@@ -2435,14 +2435,14 @@ static int enqueue_partials(smcn_ctx* c, const double* logw, const double* x, do
     if (ngen >= 4 && g > 64) g = 64;
     if (c->D >= 64 && g > 128) g = 128;   // wide particles: 2 block reductions per coordinate -- four particles per thread
                                           // between them (measured at D = 256, N = 131 072: 155 us against 197 at 512 blocks)
-    const int NQ = 4 + 2 * c->Dc;
-    while ((int64_t)g * NQ * ngen > (int64_t)kMaxPart * (4 * c->D * c->D + 2 * c->D + 8) && g > 1) g /= 2;
+    const int NQB = gen_block_nq(c->Dc);   // block partials: [max, cnt, s1, s2, A.., B.., reference point..]
+    while ((int64_t)g * NQB * ngen > (int64_t)kMaxPart * (4 * c->D * c->D + 2 * c->D + 8) && g > 1) g /= 2;
     const int nz = c->D >= 64 ? 8 : 1;
-    gen_partials_kernel<<<dim3(g, ngen, nz), kRedBlock, 0, c->stream>>>(logw, x, N, c->D, c->model,
-                                                                        shift ? shift : c->ss + SS_SHIFT, c->part, N,
+    gen_partials_kernel<<<dim3(g, ngen, nz), kRedBlock, 0, c->stream>>>(logw, x, N, c->D, c->model, c->part, N,
                                                                         N * c->D, (c->D > 8 && ngen == 1 && nz == 1) ? c->work : nullptr);
     const int qb = c->Dc <= 16 ? 1 : (2 * c->Dc + 7) / 8 > 64 ? 64 : (2 * c->Dc + 7) / 8;
-    gen_reduce_blocks_kernel<<<dim3(ngen, qb), kRedBlock, 0, c->stream>>>(c->part, g, c->Dc, out);
+    gen_reduce_blocks_kernel<<<dim3(ngen, qb), kRedBlock, 0, c->stream>>>(c->part, g, c->Dc,
+                                                                          shift ? shift : c->ss + SS_SHIFT, out);
     HIPC(c, hipGetLastError());
     return 0;
 }

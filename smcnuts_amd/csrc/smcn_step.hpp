@@ -66,28 +66,42 @@ __global__ void __launch_bounds__(kRedBlock) moment2_partial_kernel(const double
 
 // ---- generation statistics in two launches ------------------------------------------
 // part[gen][q][b], q = 0: block max; 1: count of elements at that max; 2: sum exp(a - max_b)
-// over the others; 3: sum exp(2(a - max_b)); 4..4+Dc: sum e c(x)_c; then sum e (c(x)_c - shift_c)^2.
-// Every block works relative to ITS OWN maximum (one pass, no grid-wide dependency); blocks
-// are then combined exactly like shards (gen_reduce_blocks_kernel, combine_ranks_kernel).
+// over the others; 3: sum exp(2(a - max_b)); 4..4+Dc: sum e (c(x)_c - ref_c); then sum e (c(x)_c - ref_c)^2;
+// then ref_c, the block's own reference point: c(x) of its first particle of largest weight.
+// Every block works relative to ITS OWN maximum and reference point (one pass, no grid-wide dependency); blocks
+// are then combined exactly like shards (gen_reduce_blocks_kernel, combine_ranks_kernel), the second moments
+// moved to the combined mean by the parallel-variance identity.  (Moment sums around a common shift far from the
+// particles -- the previous generation's mean, 0 at generation 0 -- lost eps (shift - mean)^2 / var of the variance.)
 // blockIdx.y = generation: logw + y*gsl, x + y*gsx.
+constexpr int gen_block_nq(int D) { return 4 + 3 * D; }
 __global__ void __launch_bounds__(kRedBlock) gen_partials_kernel(const double* logw0, const double* x0, int64_t N,
-                                                                 int D, int model_id, const double* shift,
-                                                                 double* part0, int64_t gsl, int64_t gsx,
+                                                                 int D, int model_id, double* part0, int64_t gsl,
+                                                                 int64_t gsx,
                                                                  double* work /* [N] or null: e_i kept for large D */) {
     __shared__ double sh[4];
     const double* logw = logw0 + (int64_t)blockIdx.y * gsl;
     const double* x = x0 + (int64_t)blockIdx.y * gsx;
-    const int nb = gridDim.x, NQ = 4 + 2 * D;
+    const int nb = gridDim.x, NQ = gen_block_nq(D);
     double* part = part0 + (int64_t)blockIdx.y * NQ * nb;
     double m = -kInf, nanflag = 0.0;
+    int64_t am = -1;                    // this thread's first index of its maximum
     for (int64_t i = (int64_t)blockIdx.x * kRedBlock + threadIdx.x; i < N; i += (int64_t)nb * kRedBlock) {
         const double v = logw[i];
         if (v != v) nanflag = 1.0;
-        m = fmax(m, v);
+        if (v > m) { m = v; am = i; }
     }
+    const double mt = m;
     m = block_max(m, sh);
     nanflag = block_max(nanflag, sh);
     const double mx = nanflag != 0.0 ? __builtin_nan("") : m;
+    // the block's first index of the maximum (indices < 2^53 are exact in a double); none when every weight is -inf
+    const double neg_first = block_max((am >= 0 && mt == m) ? -(double)am : -kInf, sh);
+    const int64_t iref = neg_first == -kInf ? -1 : (int64_t)(-neg_first);
+    auto ref_of = [&](int c) -> double {
+        if (iref < 0) return 0.0;
+        const double r = constrain_coord(model_id, c, D, x[(int64_t)c * N + iref]);
+        return finite_d(r) ? r : 0.0;
+    };
     const double sft = finite_d(mx) ? mx : 0.0;
     double cnt = 0.0, s1 = 0.0, s2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kRedBlock + threadIdx.x; i < N; i += (int64_t)nb * kRedBlock) {
@@ -130,14 +144,14 @@ __global__ void __launch_bounds__(kRedBlock) gen_partials_kernel(const double* l
         }
         for (int c = c_lo; c < c_hi; ++c) {
             double sa = 0.0, sb = 0.0;
-            const double sc = shift[c];
+            const double sc = ref_of(c);
             const double* const xc = x + (int64_t)c * N;
 #pragma unroll
             for (int k = 0; k < EK; ++k) {
                 if (on[k]) {
                     const double xv = constrain_coord(model_id, c, D, xc[first + k * stride]);
                     const double d = xv - sc;
-                    sa = fma(ev[k], xv, sa);
+                    sa = fma(ev[k], d, sa);
                     sb = fma(ev[k] * d, d, sb);
                 }
             }
@@ -146,20 +160,21 @@ __global__ void __launch_bounds__(kRedBlock) gen_partials_kernel(const double* l
             if (threadIdx.x == 0) {
                 part[(int64_t)(4 + c) * nb + blockIdx.x] = sa;
                 part[(int64_t)(4 + D + c) * nb + blockIdx.x] = sb;
+                part[(int64_t)(4 + 2 * D + c) * nb + blockIdx.x] = sc;
             }
         }
         return;
     }
     for (int c = c_lo; c < c_hi; ++c) {
         double sa = 0.0, sb = 0.0;
-        const double sc = shift[c];
+        const double sc = ref_of(c);
         for (int64_t i = (int64_t)blockIdx.x * kRedBlock + threadIdx.x; i < N; i += (int64_t)nb * kRedBlock) {
             const double v = logw[i];
             if (v == -kInf) continue;
             const double e = work ? work[i] : exp(v - sft);   // same thread wrote work[i] above
             const double xv = constrain_coord(model_id, c, D, x[(int64_t)c * N + i]);
             const double d = xv - sc;
-            sa = fma(e, xv, sa);
+            sa = fma(e, d, sa);
             sb = fma(e * d, d, sb);
         }
         sa = block_sum(sa, sh);
@@ -167,16 +182,18 @@ __global__ void __launch_bounds__(kRedBlock) gen_partials_kernel(const double* l
         if (threadIdx.x == 0) {
             part[(int64_t)(4 + c) * nb + blockIdx.x] = sa;
             part[(int64_t)(4 + D + c) * nb + blockIdx.x] = sb;
+            part[(int64_t)(4 + 2 * D + c) * nb + blockIdx.x] = sc;
         }
     }
 }
-// blocks -> this shard's partials [max, cnt, s1, s2, A.., B..] (same format as before);
-// one block per generation.
+// blocks -> this shard's partials [max, cnt, s1, s2, A.., B..]: A_c = sum e (c(x)_c - shift_c) around the shift all
+// shards share, B_c = sum e (c(x)_c - m_c)^2 around this shard's own mean m_c = shift_c + A_c / W; one block per
+// generation.  A block's sums move from its reference point r to m by  B + 2 (r - m) A_r + W_b (r - m)^2.
 __global__ void __launch_bounds__(kRedBlock) gen_reduce_blocks_kernel(const double* part0, int nb, int Dc,
-                                                                      double* out0) {
+                                                                      const double* shift, double* out0) {
     __shared__ double sh[4];
-    const int NQ = 4 + 2 * Dc;
-    const double* part = part0 + (int64_t)blockIdx.x * NQ * nb;
+    const int NQ = 4 + 2 * Dc, NQB = gen_block_nq(Dc);
+    const double* part = part0 + (int64_t)blockIdx.x * NQB * nb;
     double* out = out0 + (int64_t)blockIdx.x * NQ;
     double M = -kInf, nanflag = 0.0;
     for (int b = threadIdx.x; b < nb; b += kRedBlock) {
@@ -188,7 +205,7 @@ __global__ void __launch_bounds__(kRedBlock) gen_reduce_blocks_kernel(const doub
     nanflag = block_max(nanflag, sh);
     if (nanflag != 0.0) M = __builtin_nan("");
     const double sM = finite_d(M) ? M : 0.0;
-    double cnt = 0.0, s1 = 0.0, s2 = 0.0;
+    double cnt = 0.0, s1 = 0.0, s2 = 0.0, W = 0.0;
     for (int b = threadIdx.x; b < nb; b += kRedBlock) {
         const double mb = part[b];
         if (mb == -kInf || mb != mb) continue;
@@ -197,28 +214,44 @@ __global__ void __launch_bounds__(kRedBlock) gen_reduce_blocks_kernel(const doub
         if (mb == M) { cnt += cb; s1 += s1b * scale; }
         else s1 += (s1b + cb) * scale;
         s2 += part[3 * nb + b] * scale * scale;
+        W += (s1b + cb) * scale;
     }
     cnt = block_sum(cnt, sh);
     s1 = block_sum(s1, sh);
     s2 = block_sum(s2, sh);
+    W = block_sum(W, sh);
     if (threadIdx.x == 0 && blockIdx.y == 0) { out[0] = M; out[1] = cnt; out[2] = s1; out[3] = s2; }
-    // the moment sums are spread over blockIdx.y (each block redoes the cheap scalar part above): at D = 256 one
+    // the coordinates are spread over blockIdx.y (each block redoes the cheap scalar part above): at D = 256 one
     // block walking 516 quantities x 1024 partials took 0.55 ms
-    for (int q = 4 + blockIdx.y; q < NQ; q += gridDim.y) {
+    for (int c = blockIdx.y; c < Dc; c += gridDim.y) {
+        const double sc = shift[c];
         double a = 0.0;
         for (int b = threadIdx.x; b < nb; b += kRedBlock) {
             const double mb = part[b];
             if (mb == -kInf || mb != mb) continue;
-            a += part[(int64_t)q * nb + b] * exp((finite_d(mb) ? mb : 0.0) - sM);
+            const double Wb = part[nb + b] + part[2 * nb + b];
+            const double r = part[(int64_t)(4 + 2 * Dc + c) * nb + b];
+            a += (part[(int64_t)(4 + c) * nb + b] + (r - sc) * Wb) * exp((finite_d(mb) ? mb : 0.0) - sM);
         }
         a = block_sum(a, sh);
-        if (threadIdx.x == 0) out[q] = a;
+        const double dm = W > 0.0 ? a / W : 0.0;   // this shard's mean - shift
+        double bq = 0.0;
+        for (int b = threadIdx.x; b < nb; b += kRedBlock) {
+            const double mb = part[b];
+            if (mb == -kInf || mb != mb) continue;
+            const double Wb = part[nb + b] + part[2 * nb + b];
+            const double d = (part[(int64_t)(4 + 2 * Dc + c) * nb + b] - sc) - dm;   // reference point - shard mean
+            bq += (part[(int64_t)(4 + Dc + c) * nb + b] + d * fma(d, Wb, 2.0 * part[(int64_t)(4 + c) * nb + b])) *
+                  exp((finite_d(mb) ? mb : 0.0) - sM);
+        }
+        bq = block_sum(bq, sh);
+        if (threadIdx.x == 0) { out[4 + c] = a; out[4 + Dc + c] = bq; }
     }
 }
 
 // Combine the shard partials [max, cnt, s1, s2, A_0.., B_0..] in rank order
-// (samples.py:96-113 through scipy's logsumexp; estimate.py:79-95 with the
-// shifted one-pass variance), decide on resampling (samples.py:120), record.
+// (samples.py:96-113 through scipy's logsumexp; estimate.py:79-95: A around the shared shift, B around each shard's
+// own mean, joined by the parallel-variance identity), decide on resampling (samples.py:120), record.
 __device__ __forceinline__ void combine_ranks_body(const double* gathered, int world, int rank, int Dc,
                                                    double n_total, double log_n_local, const double* shift,
                                                    double phi, double* hist_k, double* ss, int rank_stride) {
@@ -249,18 +282,24 @@ __device__ __forceinline__ void combine_ranks_body(const double* gathered, int w
     if (nan) ll = __builtin_nan("");
     const double ess = 1.0 / (s2 * exp(2.0 * (shiftM - ll)));
     for (int c = tid; c < Dc; c += nth) {
+        const double sc = shift[c];
         double A = 0.0, B = 0.0;
         for (int g = 0; g < world; ++g) {
             const double* p = gathered + g * NQ;
             if (p[0] == -kInf) continue;
-            const double scale = exp((finite_d(p[0]) ? p[0] : 0.0) - shiftM);
-            A += p[4 + c] * scale;
-            B += p[4 + Dc + c] * scale;
+            A += p[4 + c] * exp((finite_d(p[0]) ? p[0] : 0.0) - shiftM);
         }
-        const double mean = A / W;
-        const double dm = mean - shift[c];
+        const double dm = A / W;                 // mean - shift
+        for (int g = 0; g < world; ++g) {
+            const double* p = gathered + g * NQ;
+            if (p[0] == -kInf) continue;
+            const double Wg = p[1] + p[2];
+            const double d = p[4 + c] / Wg - dm;  // shard mean - mean
+            B += fma(Wg * d, d, p[4 + Dc + c]) * exp((finite_d(p[0]) ? p[0] : 0.0) - shiftM);
+        }
+        const double mean = sc + dm;
         hist_k[H_MEAN + c] = mean;
-        hist_k[H_MEAN + Dc + c] = B / W - dm * dm;
+        hist_k[H_MEAN + Dc + c] = B / W;
         ss[SS_SHIFT + c] = mean;   // next iteration's shift
     }
     // this shard's own log-sum-exp, for local resampling: logw <- log W_shard - log N_local
