@@ -138,7 +138,7 @@ int smcn_set_lane_grid(smcn_ctx* ctx, int64_t waves);
  * only who builds them changes (bit-identical results with smcn_set_wide_eval(0)). */
 int smcn_set_lane_segments(smcn_ctx* ctx, int segments);
 
-/* Two-phase NUTS launches (group kernels whose trajectory edges live in registers: PRMwCD, Gaussians of 129..256 dimensions).
+/* Two-phase NUTS launches (the group kernel whose trajectory edges live in registers: PRMwCD).
  * A launch of the group kernels lasts as long as its longest tree; with doublings > 0 a tree that still wants a doubling
  * after that many is parked at the boundary (its state: the two edges, the selected sample, a few scalars) and finished by
  * a second launch behind the first.  widen != 0: by the wavefront-per-particle functor of the model where one exists

@@ -22,16 +22,7 @@
 #include "smcn_nuts_fin.hpp"
 #include "smcn_nuts2.hpp"
 #include "smcn_nuts3.hpp"
-#ifndef SMCN_WPE2_LC
-#define SMCN_WPE2_LC 1
-#define SMCN_WPE2_LF 0
-#endif
 #include "smcn_temper.hpp"
-#ifdef SMCN_VARIANTS
-#include "smcn_models_variants.hpp"
-#include "smcn_nuts_lane.hpp"
-#include "smcn_nuts2_kernel.hpp"
-#endif
 #include "smcn_nuts_host.hpp"
 #include "smcn_weights.hpp"
 #include "smcn_glk.hpp"
@@ -336,10 +327,7 @@ struct SetupTrace {
 // has a thread make three spare ones while it goes on, so that the next context (the cold `SMCSampler(...)` beside a
 // running one) finds them ready.
 namespace {
-#ifndef SMCN_POOL_SPARE
-#define SMCN_POOL_SPARE 3
-#endif
-constexpr int kPoolDevices = 16, kPoolSpare = SMCN_POOL_SPARE, kPoolMax = 32;
+constexpr int kPoolDevices = 16, kPoolSpare = 3, kPoolMax = 32;
 struct StreamPool {
     std::mutex mu;
     std::vector<hipStream_t> idle[kPoolDevices];
@@ -400,64 +388,23 @@ static int with_model(smcn_ctx* c, F&& f) {
         if (c->D <= 4) return f(GaussModel<4, 1>{});
         if (c->D <= 32) return f(GaussModel<32, 1>{});
         if (c->D <= 64) return f(GaussModel<64, 1>{});
-#ifdef SMCN_VARIANTS   // A/B builds: particles per wavefront x tree-stack levels in LDS at D <= 256
-        if (c->D <= 256 && getenv("SMCN_GAUSS256")) {
-            const int v = atoi(getenv("SMCN_GAUSS256"));
-            if (v == 1) return f(GaussModel<16, 16, 0>{});
-            if (v == 2) return f(GaussModel<16, 16, 1>{});
-            if (v == 3) return f(GaussModel<32, 8, 1>{});
-            if (v == 4) return f(GaussModel<32, 8, 2>{});
-            if (v == 5) return f(GaussModel<64, 4, 4, 1>{});   // one wavefront per SIMD, tree-stack levels 0-3 in LDS
-            if (v == 6) return f(GaussModel<64, 4, 3, 1>{});
-            if (v == 7) return f(GaussModel<64, 4, 1, 3>{});   // three wavefronts per SIMD (<= 168 VGPRs), one LDS level
-            if (v == 8) return f(GaussModel<64, 4, 0, 3>{});   // three wavefronts per SIMD, no LDS level
-        }
-#endif
         if (c->D <= 256) return f(GaussModel<64, 4>{});   // tree stack in HBM (BASELINE config 5)
         if (c->D <= 512) return f(GaussModel<64, 8, 2, 1>{});   // one wavefront per SIMD: 512 registers hold 8 coordinates per lane without scratch (two per SIMD spilled 620-756 B per lane)
         FAIL(c, "Gaussian target: the device functor covers D <= 512; larger targets run host-evaluated "
                 "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)");
     }
     if (c->model == SMCN_MODEL_ARMA) {
-        // the product runs arma in the lane kernels (smcn_nuts3.hpp: any series length); the group functors
-        // (8 lanes x 25 time steps, scan of the carries) remain for A/B builds
-#ifdef SMCN_VARIANTS
-        const int T = (int)c->mdata_h[0];
-        static const bool pair = !(getenv("SMCN_ARMA_PAIR") && atoi(getenv("SMCN_ARMA_PAIR")) == 0);
-        if (!pair && T == 200) return f(ArmaModel<8, 25, true>{});
-        if (!pair && T >= 1 && T < 200) return f(ArmaModel<8, 25, false>{});
-        if (T == 200) return f(ArmaModel<8, 25, true, 2>{});
-        if (T >= 1 && T < 200) return f(ArmaModel<8, 25, false, 2>{});
-#endif
+        // the product runs arma in the lane kernels (smcn_nuts3.hpp: any series length)
         FAIL(c, "arma target: this entry point has no group functor (lane kernels only)");
     }
     if (c->model == SMCN_MODEL_PRMWCD) {
         const int nobs = (int)c->mdata_h[0], M = (int)c->mdata_h[1], C = (int)c->mdata_h[2];
-#ifdef SMCN_VARIANTS   // A/B builds (the shipped shape only): 16 lanes, or the replicated-state functor (v2 kernel)
-        if (nobs == 100 && C == 11 && M == 12) {
-            static const int dist = getenv("SMCN_PRMWCD_DIST") ? atoi(getenv("SMCN_PRMWCD_DIST")) : 8;
-            if (dist == 16) return f(PrmwcdDistModel<16, 100, 11, 0, 2>{});
-            if (dist == 162) return f(PrmwcdDistModel<16, 100, 11, 2, 4>{});   // round 4: is the launch its longest tree's
-            if (dist == 322) return f(PrmwcdDistModel<32, 100, 11, 2, 4>{});   // critical path?  shorter leaves, fewer trees per wave
-            if (dist != 8) return f(PrmwcdModel<16, 100, 11>{});
-        }
-#endif
         // state distributed over 8 lanes (v1 kernel, hybrid LDS/HBM tree stack); 100 observations and 11 kernel
         // columns are the functor's capacity (the shipped data fills it), smaller data sets run in the same kernel
         if (nobs >= 1 && nobs <= 100 && C >= 1 && C <= 11 && M == C + 1) {
             if ((int64_t)c->mdata_h.size() != 4 + (int64_t)nobs * (C + 1))
                 FAIL(c, "PRMwCD target: data = [N, M, Clength, q, y_1..y_N, Xkernel (N x Clength, row-major)]");
             const bool fast_shape = nobs > 96 && C == 11 && c->mdata_h[3] == 0.5;   // what the FAST functors are unrolled for
-#ifdef SMCN_VARIANTS   // A/B builds (round 5): four lanes per particle; one lane per particle (phase 1 of a two-phase launch)
-            if (nobs == 100 && fast_shape) {
-                static const int g4 = getenv("SMCN_PRMWCD_G4") ? atoi(getenv("SMCN_PRMWCD_G4")) : 0;
-                static const int lane1 = getenv("SMCN_PRMWCD_LANE") ? atoi(getenv("SMCN_PRMWCD_LANE")) : 0;
-                if (lane1 == 1) return f(PrmwcdLaneModel<100, 11, 1>{});
-                if (lane1 == 2) return f(PrmwcdLaneModel<100, 11, 1, true>{});
-                if (g4 == 1) return f(PrmwcdDistModel<4, 100, 11, 2, 4, true, 1>{});
-                if (g4 == 2) return f(PrmwcdDistModel<4, 100, 11, 2, 1, true, 2>{});
-            }
-#endif
             if (fast_shape) return f(PrmwcdDistModel<8, 100, 11, 2, 4, true>{});   // the shipped shape: unrolled observation loop
             return f(PrmwcdDistModel<8, 100, 11, 2, 4>{});
         }
@@ -635,27 +582,14 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     int rc = 0;
     if (model_id == SMCN_MODEL_HOST) {
         if (c->D < 1 || c->D > 4096) { c->err = "host target: D out of range"; rc = -1; }
-    } else if (model_id == SMCN_MODEL_ARMA
-#ifdef SMCN_VARIANTS   // (A/B builds can route arma to the group functors, which validate their own data)
-               && getenv("SMCN_ARMA_NUTS2") == nullptr
-#endif
-    ) {
+    } else if (model_id == SMCN_MODEL_ARMA) {
         const double T = model_data[0];
         if (!(T >= 1.0) || T != (double)(int64_t)T || (int64_t)T + 1 != model_data_len) { c->err = "arma target: data = [T, y_1..y_T]"; rc = -1; }
         else c->arma_T = (int64_t)T;
     } else {
-        rc = with_model(c, [&](auto m) {
-#ifdef SMCN_VARIANTS
-            c->fused_ok = !decltype(m)::DIST && getenv("SMCN_NUTS_V1") == nullptr;
-#endif
-            return 0;
-        });
+        rc = with_model(c, [&](auto) { return 0; });
     }
-    bool lane = model_id == SMCN_MODEL_ARMA;
-#ifdef SMCN_VARIANTS
-    lane = lane && getenv("SMCN_ARMA_NUTS2") == nullptr;
-#endif
-    if (rc == 0 && lane) {
+    if (rc == 0 && model_id == SMCN_MODEL_ARMA) {
         c->lane_kernel = true;
         c->fused_ok = true;
     }
@@ -1330,38 +1264,28 @@ int smcn_bench_resample(smcn_ctx* c, int reps, int64_t iteration, double* ms_tot
 
 // ---- NUTS ---------------------------------------------------------------------------------------
 }  // extern "C"
-// the model that finishes the trees a two-phase launch parks: the same particle on more lanes where there is such a functor
+// the model that finishes the trees a two-phase launch parks: the same particle on a whole wavefront (nuts_fin_kernel)
 template <class M>
-struct resume_model { using type = M; };
+struct resume_model;
 template <int NOBS, int C_, int RED, int LEVELS, bool FAST>
 struct resume_model<PrmwcdDistModel<8, NOBS, C_, RED, LEVELS, FAST>> { using type = PrmwcdDistModel<64, NOBS, C_, 2, 5, FAST>; };
-template <int NOBS, int C_, int RED, int LEVELS, bool FAST, int WAVES>
-struct resume_model<PrmwcdDistModel<4, NOBS, C_, RED, LEVELS, FAST, WAVES>> { using type = PrmwcdDistModel<64, NOBS, C_, 2, 5, FAST>; };
-#ifdef SMCN_VARIANTS
-template <int NOBS, int C_, int LEVELS, bool LK>
-struct resume_model<PrmwcdLaneModel<NOBS, C_, LEVELS, LK>> { using type = PrmwcdDistModel<64, NOBS, C_, 2, 5, true>; };
-// one lane per particle in a kernel of its own (smcn_nuts_lane.hpp)
-template <class Model>
-static int launch_nuts_lane(smcn_ctx* c, NutsArgs a, int64_t items) {
-    const size_t lds = sizeof(double) * ((size_t)kNutsBlock * lane_lds_doubles(Model::DL) + ((Model::SHARED + 1) & ~1));
-    const void* kern = (const void*)nuts_lane_kernel<Model>;
-    HIPC(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int64_t blocks = (items + kNutsBlock - 1) / kNutsBlock;
-    if (blocks > c->num_cu) blocks = c->num_cu;
-    const int64_t need = blocks * kNutsBlock * (int64_t)lane_hbm_doubles(Model::DL);
-    if (need > c->nuts_scratch_len) {
-        HIPC(c, stream_wait(c->stream));
-        if (c->nuts_scratch) (void)cached_free(c->nuts_scratch);
-        c->nuts_scratch = nullptr;
-        HIPC(c, dalloc(&c->nuts_scratch, need));
-        c->nuts_scratch_len = need;
-    }
-    a.scratch = c->nuts_scratch;
-    c->kin_valid = false;
-    a.kin0 = nullptr; a.kin1 = nullptr; a.moved = nullptr;
+
+// Grows one of the context's scratch buffers (nuts_scratch, n2_ovf) to at least `need` doubles.
+static int grow_scratch(smcn_ctx* c, double*& buf, int64_t& len, int64_t need) {
+    if (need <= len) return 0;
+    HIPC(c, stream_wait(c->stream));     // (the old buffer may still be in use)
+    if (buf) (void)cached_free(buf);
+    buf = nullptr;
+    HIPC(c, dalloc(&buf, need));
+    len = need;
+    return 0;
+}
+// Enqueues a kernel launch between the timer events of the context's next ring slot (smcn_nuts_times).
+template <class L>
+static int timed_launch(smcn_ctx* c, L&& launch) {
     const int k = c->ev_n < kTimerRing ? c->ev_n : -1;
     if (k >= 0) HIPC(c, hipEventRecord(c->ev0[k], c->stream));
-    nuts_lane_kernel<Model><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a);
+    launch();
     HIPC(c, hipGetLastError());
     if (k >= 0) {
         HIPC(c, hipEventRecord(c->ev1[k], c->stream));
@@ -1369,29 +1293,9 @@ static int launch_nuts_lane(smcn_ctx* c, NutsArgs a, int64_t items) {
     }
     return 0;
 }
-#endif
 
 template <class Model, bool TP = false>
 static int launch_nuts_phase(smcn_ctx* c, Model, NutsArgs a, int64_t items);
-
-// A/B builds: SMCN_GAUSS_OLD_KERNEL=1 runs Gaussians of 65..512 dimensions in the generic kernel (round 4)
-static bool wave_old_kernel() {
-#ifdef SMCN_VARIANTS
-    static const bool v = getenv("SMCN_GAUSS_OLD_KERNEL") && atoi(getenv("SMCN_GAUSS_OLD_KERNEL")) != 0;
-    return v;
-#else
-    return false;
-#endif
-}
-// A/B builds: SMCN_FIN_OLD=1 finishes parked trees with the generic kernel's wave-per-particle instantiation (round 4)
-static bool fin_old_kernel() {
-#ifdef SMCN_VARIANTS
-    static const bool v = getenv("SMCN_FIN_OLD") && atoi(getenv("SMCN_FIN_OLD")) != 0;
-    return v;
-#else
-    return false;
-#endif
-}
 
 // One wavefront per PRMwCD tree (smcn_nuts_fin.hpp): the parked trees of a two-phase launch, or -- widen = 2 -- every tree.
 template <class Model>
@@ -1403,10 +1307,6 @@ static int launch_nuts_fin(smcn_ctx* c, NutsArgs a, int64_t items) {
     int per_cu = 0;
     HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nuts_fin_kernel<Model>, kNutsBlock, lds));
     if (per_cu < 1) FAIL(c, "nuts finisher kernel does not fit on a CU");
-    if (const char* e = getenv("SMCN_FIN_BLOCKS_PER_CU")) {   // tuning knob
-        const int v = atoi(e);
-        if (v >= 1 && v < per_cu) per_cu = v;
-    }
     int64_t blocks = (items + wpb - 1) / wpb;
     const int64_t cap = (int64_t)c->num_cu * per_cu;
     if (blocks > cap) blocks = cap;
@@ -1423,15 +1323,7 @@ static int launch_nuts_fin(smcn_ctx* c, NutsArgs a, int64_t items) {
         c->kin_valid = true;
     }
     HIPC(c, hipMemsetAsync(c->queue, 0, sizeof(unsigned int) * 16, c->stream));
-    const int k = c->ev_n < kTimerRing ? c->ev_n : -1;
-    if (k >= 0) HIPC(c, hipEventRecord(c->ev0[k], c->stream));
-    nuts_fin_kernel<Model><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a);
-    HIPC(c, hipGetLastError());
-    if (k >= 0) {
-        HIPC(c, hipEventRecord(c->ev1[k], c->stream));
-        c->ev_n++;
-    }
-    return 0;
+    return timed_launch(c, [&] { nuts_fin_kernel<Model><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a); });
 }
 
 // One wavefront per particle, candidates by leaf index (smcn_nuts_wave.hpp): Gaussians of 65..512 dimensions.
@@ -1444,22 +1336,12 @@ static int launch_nuts_wave_t(smcn_ctx* c, NutsArgs a) {
     int per_cu = 0;
     HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nuts_wave_kernel<Model, FULL, HAS, SLOTS, WAVES>, kNutsBlock, lds));
     if (per_cu < 1) FAIL(c, "nuts wave kernel does not fit on a CU");
-    if (const char* e = getenv("SMCN_NUTS_BLOCKS_PER_CU")) {   // tuning knob
-        const int v = atoi(e);
-        if (v >= 1 && v < per_cu) per_cu = v;
-    }
     int64_t blocks = (a.N + wpb - 1) / wpb;
     const int64_t cap = (int64_t)c->num_cu * per_cu;
     if (blocks > cap) blocks = cap;
     // first leaves of the sub-trees above the LDS slots: one area per resident wavefront
-    const int64_t need = blocks * wpb * (int64_t)kMaxLevels * wave_slot_doubles(Model::DL);
-    if (need > c->nuts_scratch_len) {
-        HIPC(c, stream_wait(c->stream));
-        if (c->nuts_scratch) (void)cached_free(c->nuts_scratch);
-        c->nuts_scratch = nullptr;
-        HIPC(c, dalloc(&c->nuts_scratch, need));
-        c->nuts_scratch_len = need;
-    }
+    if (int rc = grow_scratch(c, c->nuts_scratch, c->nuts_scratch_len, blocks * wpb * (int64_t)kMaxLevels * wave_slot_doubles(Model::DL)))
+        return rc;
     a.scratch = c->nuts_scratch;
     if (!c->kin0) {
         HIPC(c, dalloc(&c->kin0, c->N));
@@ -1469,15 +1351,7 @@ static int launch_nuts_wave_t(smcn_ctx* c, NutsArgs a) {
     a.kin0 = c->kin0; a.kin1 = c->kin1; a.moved = c->moved_i;
     c->kin_valid = true;
     HIPC(c, hipMemsetAsync(c->queue, 0, sizeof(unsigned int) * 16, c->stream));
-    const int k = c->ev_n < kTimerRing ? c->ev_n : -1;
-    if (k >= 0) HIPC(c, hipEventRecord(c->ev0[k], c->stream));
-    nuts_wave_kernel<Model, FULL, HAS, SLOTS, WAVES><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a);
-    HIPC(c, hipGetLastError());
-    if (k >= 0) {
-        HIPC(c, hipEventRecord(c->ev1[k], c->stream));
-        c->ev_n++;
-    }
-    return 0;
+    return timed_launch(c, [&] { nuts_wave_kernel<Model, FULL, HAS, SLOTS, WAVES><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a); });
 }
 template <class Model, int SLOTS, int WAVES>
 static int launch_nuts_wave_sw(smcn_ctx* c, NutsArgs a) {
@@ -1491,11 +1365,6 @@ static int launch_nuts_wave(smcn_ctx* c, NutsArgs a) {
         // three wavefronts per SIMD (<= 168 VGPRs), three LDS slots of 4 KB each per wavefront = 144 KB per CU: the third
         // wavefront hides what the round trips at a tree's two ends and the HBM stack levels cost the other two
         // (profiles/r05_c5_ab.txt: 1.74 -> 2.02 G leapfrog/s at step 0.1 against two wavefronts with four slots)
-#ifdef SMCN_VARIANTS
-        static const int cfg = getenv("SMCN_WAVE_CFG") ? atoi(getenv("SMCN_WAVE_CFG")) : 0;    // A/B: slots x wavefronts
-        if (cfg == 42) return launch_nuts_wave_sw<Model, 4, 2>(c, a);
-        if (cfg == 32) return launch_nuts_wave_sw<Model, 3, 2>(c, a);
-#endif
         // (the masked / with-likelihood instantiations need a few registers more: two wavefronts, four slots, no scratch)
         if (c->D == 64 * Model::DL && c->mdata_h[2] == 0.0) return launch_nuts_wave_t<Model, true, false, 3, 3>(c, a);
         return launch_nuts_wave_sw<Model, 4, 2>(c, a);
@@ -1506,94 +1375,72 @@ static int launch_nuts_wave(smcn_ctx* c, NutsArgs a) {
 
 template <class Model>
 static int launch_nuts(smcn_ctx* c, Model, NutsArgs a) {
-    if constexpr (model_wave_kernel<Model>::value) {
-        c->nuts_parked = 0;
-        if (!wave_old_kernel()) return launch_nuts_wave<Model>(c, a);
-    }
-    constexpr int VS0 = Model::DIST ? Model::G * Model::DL : Model::DL;
-    constexpr bool HBM0 = model_hybrid_always<Model>::value ||
-                          sizeof(double) * (size_t)(kNutsBlock / Model::G) * nuts_slot_doubles(VS0) > 150 * 1024;
-    // (nuts_kernel's REGE_K: edges in registers, park and take up; or PARK_SLOT: one lane per particle, park only)
-    constexpr bool REGE0 = HBM0 && Model::DIST && model_two_phase<Model>::value && (Model::DL <= 4 || Model::G == 1);
     c->nuts_parked = 0;
-    a.step_align = Model::G < 64 ? model_step_align<Model>::value : 1;
-    using Model2 = typename resume_model<Model>::type;
-    if constexpr (REGE0 && !std::is_same<Model2, Model>::value) {
-        // widen == 2 (tests, A/B): EVERY tree from its start in the kernel instantiation that otherwise finishes the parked
-        // ones -- the finisher's functor, its LDS and HBM stack levels -- so that the parity tests reach it on whole trees
-        if (c->nuts_wide2 == 2) {
-            a.step_align = 1;
-            if constexpr (model_fin_kernel<Model2>::value) {
-                if (!fin_old_kernel()) return launch_nuts_fin<Model2>(c, a, a.N);
+    if constexpr (model_wave_kernel<Model>::value) {
+        return launch_nuts_wave<Model>(c, a);
+    } else {
+        constexpr int VS0 = Model::DIST ? Model::G * Model::DL : Model::DL;
+        constexpr bool HBM0 = sizeof(double) * (size_t)(kNutsBlock / Model::G) * nuts_slot_doubles(VS0) > 150 * 1024;
+        // (nuts_kernel's REGE_K: edges in registers, park and take up)
+        constexpr bool REGE0 = HBM0 && Model::DIST && model_two_phase<Model>::value && Model::DL <= 4;
+        a.step_align = Model::G < 64 ? model_step_align<Model>::value : 1;
+        if constexpr (!REGE0) {
+            return launch_nuts_phase<Model, false>(c, Model{}, a, a.N);
+        } else {
+            using Model2 = typename resume_model<Model>::type;
+            // widen == 2 (tests): EVERY tree from its start in the finisher -- its functor, its LDS and HBM stack levels --
+            // so that the parity tests reach it on whole trees
+            if (c->nuts_wide2 == 2) {
+                a.step_align = 1;
+                return launch_nuts_fin<Model2>(c, a, a.N);
             }
-            return launch_nuts_phase<Model2, REGE0>(c, Model2{}, a, a.N);
-        }
-    }
-    if (!REGE0 || c->nuts_jcap <= 0 || c->nuts_jcap >= a.max_depth + 1) return launch_nuts_phase<Model, false>(c, Model{}, a, a.N);
-    // ---- two phases: trees that want more than jcap doublings are parked and finished by a second launch ----------
-    const int64_t rsz = 8 * (int64_t)c->D + 8;
-    if (!c->nuts_resume) {
-        HIPC(c, dalloc(&c->nuts_resume, c->N * rsz));
-        HIPC(c, cached_malloc((void**)&c->nuts_pend, sizeof(unsigned int) * (c->N + 1)));
-    }
-    HIPC(c, hipMemsetAsync(c->nuts_pend, 0, sizeof(unsigned int), c->stream));
-    a.jcap = c->nuts_jcap; a.resume = c->nuts_resume; a.pend = c->nuts_pend; a.resume_in = 0;
-    if constexpr (Model::G < 64) {
-        // an inner park level, taken up again by this launch's own groups (smcn_set_nuts_requeue; NutsArgs::mq)
-        static const int mq_env = getenv("SMCN_NUTS_REQUEUE") ? atoi(getenv("SMCN_NUTS_REQUEUE")) : -1;   // (A/B: overrides the setting)
-        const int mq_b = mq_env >= 0 ? mq_env : c->nuts_mq_b;
-        c->nuts_mq_used = false;
-        if (mq_b > 0 && mq_b < c->nuts_jcap && c->nuts_mq_ok) {
-            if (8 * c->D + 8 > 128) FAIL(c, "nuts: the inner park level holds records of up to 128 doubles (D <= 15)");
-            if (!c->nuts_mq) {
-                HIPC(c, cached_malloc((void**)&c->nuts_mq, sizeof(unsigned int) * (c->N + 16)));
-                HIPC(c, dalloc(&c->nuts_mq_rec, c->N * 128));
+            if (c->nuts_jcap <= 0 || c->nuts_jcap >= a.max_depth + 1) return launch_nuts_phase<Model, false>(c, Model{}, a, a.N);
+            // ---- two phases: trees that want more than jcap doublings are parked and finished by a second launch ------
+            const int64_t rsz = 8 * (int64_t)c->D + 8;
+            if (!c->nuts_resume) {
+                HIPC(c, dalloc(&c->nuts_resume, c->N * rsz));
+                HIPC(c, cached_malloc((void**)&c->nuts_pend, sizeof(unsigned int) * (c->N + 1)));
             }
-            HIPC(c, hipMemsetAsync(c->nuts_mq, 0, sizeof(unsigned int) * (c->N + 16), c->stream));
-            a.mq = c->nuts_mq; a.mq_rec = c->nuts_mq_rec; a.mq_b = mq_b;
-            c->nuts_mq_used = true;
-        }
-    }
-    int rc = launch_nuts_phase<Model, REGE0>(c, Model{}, a, a.N);
-    if (rc) return rc;
-    if (a.mq && getenv("SMCN_MQ_DEBUG")) {      // diagnostics of the inner level: allocated, taken, entries never seen, unclaimed
-        unsigned int h[8];
-        HIPC(c, hipMemcpyAsync(h, a.mq, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, stream_wait(c->stream));
-        fprintf(stderr, "[smcn] requeue level %d: parked %u taken %u lost %u unclaimed %d\n", a.mq_b, h[0], h[1], h[2], (int)h[5]);
-    }
-    if (c->nuts_wide2 && !std::is_same<Model2, Model>::value) {
-        if constexpr (model_fin_kernel<Model2>::value) {
-            if (!fin_old_kernel()) {
+            HIPC(c, hipMemsetAsync(c->nuts_pend, 0, sizeof(unsigned int), c->stream));
+            a.jcap = c->nuts_jcap; a.resume = c->nuts_resume; a.pend = c->nuts_pend; a.resume_in = 0;
+            // an inner park level, taken up again by this launch's own groups (smcn_set_nuts_requeue; NutsArgs::mq)
+            const int mq_b = c->nuts_mq_b;
+            c->nuts_mq_used = false;
+            if (mq_b > 0 && mq_b < c->nuts_jcap && c->nuts_mq_ok) {
+                if (8 * c->D + 8 > 128) FAIL(c, "nuts: the inner park level holds records of up to 128 doubles (D <= 15)");
+                if (!c->nuts_mq) {
+                    HIPC(c, cached_malloc((void**)&c->nuts_mq, sizeof(unsigned int) * (c->N + 16)));
+                    HIPC(c, dalloc(&c->nuts_mq_rec, c->N * 128));
+                }
+                HIPC(c, hipMemsetAsync(c->nuts_mq, 0, sizeof(unsigned int) * (c->N + 16), c->stream));
+                a.mq = c->nuts_mq; a.mq_rec = c->nuts_mq_rec; a.mq_b = mq_b;
+                c->nuts_mq_used = true;
+            }
+            int rc = launch_nuts_phase<Model, true>(c, Model{}, a, a.N);
+            if (rc) return rc;
+            a.jcap = 0; a.resume_in = 1; a.mq = nullptr; a.mq_b = 0;
+            if (c->nuts_wide2) {
                 // the finisher takes its trees from the device-side list (count included): nothing to wait for -- a full grid is
                 // launched and wavefronts without a ticket leave at once; smcn_nuts_parked reads the count when asked
                 c->nuts_parked = -1;
-                a.jcap = 0; a.resume_in = 1; a.mq = nullptr; a.mq_b = 0;
                 return launch_nuts_fin<Model2>(c, a, a.N);
             }
+            unsigned int parked = 0;
+            HIPC(c, hipMemcpyAsync(&parked, c->nuts_pend, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+            HIPC(c, stream_wait(c->stream));
+            c->nuts_parked = parked;
+            if (parked == 0) return 0;
+            return launch_nuts_phase<Model, true>(c, Model{}, a, (int64_t)parked);
         }
     }
-    unsigned int parked = 0;
-    HIPC(c, hipMemcpyAsync(&parked, c->nuts_pend, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    c->nuts_parked = parked;
-    if (parked == 0) return 0;
-    a.jcap = 0; a.resume_in = 1; a.mq = nullptr; a.mq_b = 0;
-    if (c->nuts_wide2 && !std::is_same<Model2, Model>::value) return launch_nuts_phase<Model2, REGE0>(c, Model2{}, a, (int64_t)parked);
-    if constexpr (Model::G == 1) FAIL(c, "two-phase launches of the one-lane-per-particle kernel need the finisher (widen != 0)");
-    return launch_nuts_phase<Model, REGE0>(c, Model{}, a, (int64_t)parked);
 }
 
 template <class Model, bool TP>
 static int launch_nuts_phase(smcn_ctx* c, Model, NutsArgs a, int64_t items) {
-#ifdef SMCN_VARIANTS
-    if constexpr (model_lane_kernel<Model>::value) return launch_nuts_lane<Model>(c, a, items);
-#endif
     constexpr int G = Model::G;
     constexpr int VS = Model::DIST ? G * Model::DL : Model::DL;
     constexpr int gpb = kNutsBlock / G;
-    constexpr bool HBM = model_hybrid_always<Model>::value ||
-                         sizeof(double) * (size_t)gpb * nuts_slot_doubles(VS) > 150 * 1024;   // does not fit LDS
+    constexpr bool HBM = sizeof(double) * (size_t)gpb * nuts_slot_doubles(VS) > 150 * 1024;   // does not fit LDS
     const size_t lds = HBM ? sizeof(double) * ((size_t)gpb * nuts_hybrid_lds_doubles(VS, Model::LDS_LEVELS) +
                                                ((Model::SHARED + 1) & ~1))
                            : sizeof(double) * ((size_t)gpb * nuts_slot_doubles(VS) + ((Model::SHARED + 1) & ~1));
@@ -1603,131 +1450,25 @@ static int launch_nuts_phase(smcn_ctx* c, Model, NutsArgs a, int64_t items) {
     int per_cu = 0;
     HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nuts_kernel<Model, HBM, TP>, kNutsBlock, lds));
     if (per_cu < 1) FAIL(c, "nuts kernel does not fit on a CU");
-    if (const char* e = getenv("SMCN_NUTS_BLOCKS_PER_CU")) {   // tuning knob
-        const int v = atoi(e);
-        if (v >= 1 && v < per_cu) per_cu = v;
-    }
     int64_t blocks = (items + gpb - 1) / gpb;
     const int64_t cap = (int64_t)c->num_cu * per_cu;
     if (blocks > cap) blocks = cap;
     if (HBM) {
-        const int64_t need = blocks * gpb * (int64_t)nuts_slot_doubles(VS);
-        if (need > c->nuts_scratch_len) {
-            HIPC(c, stream_wait(c->stream));
-            if (c->nuts_scratch) (void)cached_free(c->nuts_scratch);
-            c->nuts_scratch = nullptr;
-            HIPC(c, dalloc(&c->nuts_scratch, need));
-            c->nuts_scratch_len = need;
-        }
+        if (int rc = grow_scratch(c, c->nuts_scratch, c->nuts_scratch_len, blocks * gpb * (int64_t)nuts_slot_doubles(VS)))
+            return rc;
         a.scratch = c->nuts_scratch;
     }
     c->kin_valid = false;
     if (a.resume_in) {
         a.kin0 = nullptr; a.kin1 = nullptr; a.moved = nullptr;   // (a resumed tree's start statistics were not kept)
-    } else if constexpr (nuts_kernel_writes_stats<Model, HBM>()) {
-        if (!c->kin0) {
-            HIPC(c, dalloc(&c->kin0, c->N));
-            HIPC(c, dalloc(&c->kin1, c->N));
-            HIPC(c, cached_malloc((void**)&c->moved_i, sizeof(int32_t) * c->N));
-        }
-        a.kin0 = c->kin0; a.kin1 = c->kin1; a.moved = c->moved_i;
-        c->kin_valid = true;
     }
     HIPC(c, hipMemsetAsync(c->queue, 0, sizeof(unsigned int) * 16, c->stream));
-    const int k = c->ev_n < kTimerRing ? c->ev_n : -1;
-    if (k >= 0) HIPC(c, hipEventRecord(c->ev0[k], c->stream));
-    nuts_kernel<Model, HBM, TP><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a);
-    HIPC(c, hipGetLastError());
-    if (k >= 0) {
-        HIPC(c, hipEventRecord(c->ev1[k], c->stream));
-        c->ev_n++;
-    }
-    return 0;
+    return timed_launch(c, [&] { nuts_kernel<Model, HBM, TP><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a); });
 }
 
-#ifdef SMCN_VARIANTS
-template <class Model, bool TAPE>
-static int launch_nuts2(smcn_ctx* c, Model, Nuts2Args a, const double* tape_d, const int64_t* tape_off_d,
-                        bool fuse_reweight, int B = 1, double* gen_x = nullptr, double* gen_logw = nullptr,
-                        double* cnt = nullptr, int phase = 0 /* 0: all, 1: prep + kernel, 2: post */) {
-    constexpr int G = Model::G, DL = Model::DL, VP = n2_vp(DL);
-    constexpr int gpb = kNutsBlock / G;
-    const int64_t N = c->N;
-    if (N * (int64_t)B * n2_out_doubles(DL) * 8 >= (int64_t)1 << 32)
-        FAIL(c, "nuts2: shard too large for 32-bit record offsets (split over more shards)");
-    if (TAPE && B != 1) FAIL(c, "nuts2: recorded tapes replay one transition at a time");
-    if (phase == 2 && B > c->rec_cap) FAIL(c, "nuts2: post without a launch");
-    if (B > c->rec_cap) {   // once: sized for the longest block the caller announced (smcn_fuse_begin)
-        const int cap = (c->fuse_max > B && (int64_t)N * c->fuse_max * n2_out_doubles(DL) * 8 < ((int64_t)1 << 32))
-                            ? c->fuse_max : B;
-        HIPC(c, stream_wait(c->stream));
-        if (c->in_rec) (void)cached_free(c->in_rec);
-        if (c->out_rec) (void)cached_free(c->out_rec);
-        c->in_rec = c->out_rec = nullptr;
-        HIPC(c, dalloc(&c->in_rec, N * cap * n2_in_doubles(DL)));
-        HIPC(c, dalloc(&c->out_rec, N * cap * n2_out_doubles(DL)));
-        c->rec_cap = cap;
-    }
-    constexpr int NL = Model::N2_LDS_LEVELS;
-    const size_t lds = sizeof(double) * ((size_t)gpb * n2_slot_doubles(DL, NL) + ((Model::SHARED + 1) & ~1));
-    HIPC(c, hipFuncSetAttribute((const void*)nuts2_kernel<Model, TAPE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));   // per device: on every launch
-    int per_cu = 0;
-    HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nuts2_kernel<Model, TAPE>, kNutsBlock, lds));
-    if (per_cu < 1) FAIL(c, "nuts2 kernel does not fit on a CU");
-    if (const char* e = getenv("SMCN_NUTS_BLOCKS_PER_CU")) {   // tuning knob
-        const int v = atoi(e);
-        if (v >= 1 && v < per_cu) per_cu = v;
-    }
-    int64_t blocks = (N + gpb - 1) / gpb;
-    const int64_t cap = (int64_t)c->num_cu * per_cu;
-    if (blocks > cap) blocks = cap;
-    if (NL < 10) {   // overflow tree-stack levels, one area per resident group
-        const int64_t need = blocks * gpb * (int64_t)n2_ovf_doubles(DL, NL);
-        if (need > c->n2_ovf_len) {
-            HIPC(c, stream_wait(c->stream));
-            if (c->n2_ovf) (void)cached_free(c->n2_ovf);
-            c->n2_ovf = nullptr;
-            HIPC(c, dalloc(&c->n2_ovf, need));
-            c->n2_ovf_len = need;
-        }
-        a.ovf = c->n2_ovf;
-    }
-    if (phase != 2) {
-    // momentum draw + slice exponential + input records (samples.py:155, nuts.py:69)
-    if (c->momentum_set && B != 1) FAIL(c, "nuts2: caller-supplied momenta go with single transitions");
-    nuts2_prep_kernel<<<grid_for(N * B, 256), 256, sizeof(double) * 256 * n2_in_doubles(DL), c->stream>>>(c->x, c->momentum_set ? c->r : nullptr, c->r,
-                                                                   c->in_rec, N, c->D, VP, c->base, c->seed, a.iter,
-                                                                   B, tape_d, tape_off_d);
-    c->momentum_set = false;
-    HIPC(c, hipMemsetAsync(c->queue, 0, sizeof(unsigned int) * 4, c->stream));
-    a.in = c->in_rec;
-    a.out = c->out_rec;
-    a.B = B;
-    const int k = c->ev_n < kTimerRing ? c->ev_n : -1;
-    if (k >= 0) HIPC(c, hipEventRecord(c->ev0[k], c->stream));
-    nuts2_kernel<Model, TAPE><<<(int)blocks, kNutsBlock, lds, c->stream>>>(a);
-    HIPC(c, hipGetLastError());
-    if (k >= 0) {
-        HIPC(c, hipEventRecord(c->ev1[k], c->stream));
-        c->ev_n++;
-    }
-    }
-    if (phase == 1) return 0;
-    nuts2_post_kernel<0><<<grid_for(N, 256), 256, 0, c->stream>>>(
-        c->out_rec, c->in_rec, c->x, fuse_reweight ? c->logw : nullptr, c->x_new, c->r_new, c->lpri0, c->llik0,
-        c->lpri1, c->llik1, c->nleap, c->depth, c->ndraws, c->flags, fuse_reweight ? c->logw_new : nullptr, gen_x,
-        gen_logw, cnt, N, c->D, VP, B);
-    HIPC(c, hipGetLastError());
-    return 0;
-}
-
-#endif
-
-// One lane per particle (smcn_nuts3.hpp): one wavefront per block, no work queue; the record buffers,
-// the prep kernel (momentum draw, slice exponential) and the post kernel (unpack + forward-L re-weight)
-// are those of the v2 kernel.
-template <class Model, bool TAPE, int LC, int LF, int WPE = 1>
+// One lane per particle (smcn_nuts3.hpp): one wavefront per block, no work queue; input and output records, a prep
+// kernel (momentum draw, slice exponential) and the post kernel of smcn_nuts2.hpp (unpack + forward-L re-weight).
+template <class Model, bool TAPE, int LC, int LF>
 static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const int64_t* tape_off_d, bool fuse_reweight,
                         int B, double* gen_x, double* gen_logw, double* cnt, int phase) {
     constexpr int D = Model::D, VP = n2_vp(D);
@@ -1749,20 +1490,13 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
     // round of them would last a whole longest chain again) -- the resident lanes take the particles beyond 64 * blocks
     // from a queue as they finish their own (smcn_nuts3.hpp)
     int64_t blocks = (N + kN3Block - 1) / kN3Block;
-    const int64_t resident = (int64_t)c->num_cu * 4 * WPE;
+    const int64_t resident = (int64_t)c->num_cu * 4;
     if (c->lane_grid_cap > 0 && blocks > c->lane_grid_cap) blocks = c->lane_grid_cap;
     else if (c->lane_grid_cap == 0 && blocks > resident) blocks = resident;
     // (the ready bits of a wavefront's particles are one 64-bit word per lane: beyond 4 096 particles a wavefront the
     //  launch is the plain one -- a wavefront per 64 particles, in rounds)
     if (((N + blocks - 1) / blocks + 63) / 64 > kN3ReadyWords) blocks = (N + kN3Block - 1) / kN3Block;
-    const int64_t need = blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, LC, LF);   // doubles
-    if (need > c->n2_ovf_len) {
-        HIPC(c, stream_wait(c->stream));
-        if (c->n2_ovf) (void)cached_free(c->n2_ovf);
-        c->n2_ovf = nullptr;
-        HIPC(c, dalloc(&c->n2_ovf, need));
-        c->n2_ovf_len = need;
-    }
+    if (int rc = grow_scratch(c, c->n2_ovf, c->n2_ovf_len, blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, LC, LF))) return rc;
     a.ovf = c->n2_ovf;
     if (phase != 2) {
         if (c->momentum_set && B != 1) FAIL(c, "nuts3: caller-supplied momenta go with single transitions");
@@ -1809,19 +1543,14 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
             }
             a.handover = c->handover;
         }
-        if (WPE > 1 && !queued) FAIL(c, "nuts3: the two-wavefront instantiation is the queue kernel's");
-        const void* const kfn = (queued || WPE > 1) ? (const void*)nuts3_kernel<Model, TAPE, LC, LF, true, WPE>
-                                                    : (const void*)nuts3_kernel<Model, TAPE, LC, LF, false, 1>;
+        const void* const kfn = queued ? (const void*)nuts3_kernel<Model, TAPE, LC, LF, true, 1>
+                                       : (const void*)nuts3_kernel<Model, TAPE, LC, LF, false, 1>;
         HIPC(c, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // per device
-        const int k = c->ev_n < kTimerRing ? c->ev_n : -1;
-        if (k >= 0) HIPC(c, hipEventRecord(c->ev0[k], c->stream));
-        if (queued || WPE > 1) nuts3_kernel<Model, TAPE, LC, LF, true, WPE><<<(int)blocks, kN3Block, lds, c->stream>>>(a);
-        else nuts3_kernel<Model, TAPE, LC, LF, false, 1><<<(int)blocks, kN3Block, lds, c->stream>>>(a);
-        HIPC(c, hipGetLastError());
-        if (k >= 0) {
-            HIPC(c, hipEventRecord(c->ev1[k], c->stream));
-            c->ev_n++;
-        }
+        const int rc = timed_launch(c, [&] {
+            if (queued) nuts3_kernel<Model, TAPE, LC, LF, true, 1><<<(int)blocks, kN3Block, lds, c->stream>>>(a);
+            else nuts3_kernel<Model, TAPE, LC, LF, false, 1><<<(int)blocks, kN3Block, lds, c->stream>>>(a);
+        });
+        if (rc) return rc;
     }
     if (phase == 1) return 0;
     nuts2_post_kernel<D><<<grid_for(N, 256), 256, 0, c->stream>>>(
@@ -1920,16 +1649,7 @@ static int propose_async(smcn_ctx* c, double step_size, double phi, int max_dept
         b.queue = c->queue; b.eps = step_size; b.phi = phi; b.delta_max = delta_max; b.max_depth = max_depth;
         b.seed = c->seed; b.iter = (uint32_t)iteration; b.tape = tape_d; b.tape_off = tape_off_d;
         b.prof = c->prof; b.ovf = nullptr; b.B = B;
-        int rc3;
-#ifdef SMCN_VARIANTS
-        // A/B: two wavefronts per SIMD for populations of at least 128 particles per SIMD (SMCN_LANE_WPE=2)
-        static const int wpe = getenv("SMCN_LANE_WPE") ? atoi(getenv("SMCN_LANE_WPE")) : 1;
-        if (wpe == 2 && !tape_d && N > (int64_t)c->num_cu * 4 * 2 * kN3Block && c->lane_grid_cap == 0)
-            rc3 = launch_nuts3<ArmaLaneModel, false, SMCN_WPE2_LC, SMCN_WPE2_LF, 2>(c, b, tape_d, tape_off_d, fuse_reweight, B, gen_x,
-                                                                                   gen_logw, cnt, phase);
-        else
-#endif
-        rc3 = tape_d ? launch_nuts3<ArmaLaneModel, true, 3, 3>(c, b, tape_d, tape_off_d, fuse_reweight, B, gen_x,
+        const int rc3 = tape_d ? launch_nuts3<ArmaLaneModel, true, 3, 3>(c, b, tape_d, tape_off_d, fuse_reweight, B, gen_x,
                                                                gen_logw, cnt, phase)
                      : launch_nuts3<ArmaLaneModel, false, 3, 3>(c, b, tape_d, tape_off_d, fuse_reweight, B, gen_x,
                                                                 gen_logw, cnt, phase);
@@ -1938,56 +1658,8 @@ static int propose_async(smcn_ctx* c, double step_size, double phi, int max_dept
         c->lg_set = false;
         return 0;
     }
-#ifdef SMCN_VARIANTS
-    // A/B builds only: the second-generation kernel for replicated-state group functors (arma on 4 + 4 lanes
-    // with SMCN_ARMA_NUTS2=1, PRMwCD replicated with SMCN_PRMWCD_DIST=0); the product runs arma in nuts3_kernel
-    static const bool force_v1 = getenv("SMCN_NUTS_V1") != nullptr;
-    bool used_v2 = false;
-    int rc2 = with_model(c, [&](auto m) {
-        using M = decltype(m);
-        if constexpr (!M::DIST) {
-            if (!force_v1) {
-                Nuts2Args b;
-                b.N = N; b.particle_base = c->base; b.mdata = c->mdata; b.in = nullptr; b.out = nullptr;
-                b.queue = c->queue; b.eps = step_size; b.phi = phi; b.delta_max = delta_max; b.max_depth = max_depth;
-                b.seed = c->seed; b.iter = (uint32_t)iteration; b.tape = tape_d; b.tape_off = tape_off_d;
-                b.prof = c->prof;
-                b.ovf = nullptr;
-                used_v2 = true;
-                return tape_d ? launch_nuts2<M, true>(c, m, b, tape_d, tape_off_d, fuse_reweight, B, gen_x, gen_logw, cnt,
-                                                      phase)
-                              : launch_nuts2<M, false>(c, m, b, tape_d, tape_off_d, fuse_reweight, B, gen_x, gen_logw,
-                                                       cnt, phase);
-            }
-        }
-        return 0;
-    });
-    if (rc2) return rc2;
-    if (used_v2) {
-        if (reweighted) *reweighted = fuse_reweight;
-        c->lg_set = false;
-        return 0;
-    }
-#endif
     if (B != 1 || phase != 0) FAIL(c, "fused transitions: this model's kernel runs one transition per launch");
-    // (nuts_wave_kernel's targets take and leave the momentum one contiguous row per particle: smcn_ctx::r_pm)
-    const bool wave_target = c->model == SMCN_MODEL_GAUSS && c->D > 64 && !wave_old_kernel();
-    if (!c->momentum_set) {  // samples.py:155 with the N(0, I) momentum proposal
-        const int64_t n = N * ((c->D + 1) / 2);
-        if (wave_target)
-            normals_pm_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->r, N, c->D, c->base, c->seed, (uint32_t)iteration,
-                                                                      kStreamMomentum);
-        else
-            normals_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->r, N, c->D, c->base, c->seed, (uint32_t)iteration,
-                                                                   kStreamMomentum);
-        HIPC(c, hipGetLastError());
-        c->r_pm = wave_target;
-    }
-    c->momentum_set = false;
-    c->r_new_pm = wave_target;
     NutsArgs a;
-    a.r_pm = c->r_pm ? 1 : 0;
-    a.r_new_pm = c->r_new_pm ? 1 : 0;
     a.N = N; a.particle_base = c->base; a.mdata = c->mdata; a.x = c->x; a.r = c->r;
     a.x_new = c->x_new; a.r_new = c->r_new;
     a.lpri0 = c->lpri0; a.llik0 = c->llik0; a.lpri1 = c->lpri1; a.llik1 = c->llik1;
@@ -1998,16 +1670,35 @@ static int propose_async(smcn_ctx* c, double step_size, double phi, int max_dept
     a.scratch = nullptr;
     a.tape = tape_d;
     a.tape_off = tape_off_d;
-    int rc = with_model(c, [&](auto m) { return launch_nuts(c, m, a); });
+    int rc = with_model(c, [&](auto m) {
+        // (nuts_wave_kernel's targets take and leave the momentum one contiguous row per particle: smcn_ctx::r_pm)
+        constexpr bool wave_target = model_wave_kernel<decltype(m)>::value;
+        if (!c->momentum_set) {  // samples.py:155 with the N(0, I) momentum proposal
+            const int64_t n = N * ((c->D + 1) / 2);
+            if (wave_target)
+                normals_pm_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->r, N, c->D, c->base, c->seed,
+                                                                          (uint32_t)iteration, kStreamMomentum);
+            else
+                normals_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->r, N, c->D, c->base, c->seed,
+                                                                       (uint32_t)iteration, kStreamMomentum);
+            HIPC(c, hipGetLastError());
+            c->r_pm = wave_target;
+        }
+        c->momentum_set = false;
+        c->r_new_pm = wave_target;
+        a.r_pm = c->r_pm ? 1 : 0;
+        a.r_new_pm = c->r_new_pm ? 1 : 0;
+        return launch_nuts(c, m, a);
+    });
     if (rc) return rc;
     c->lg_set = false;
     return 0;
 }
 extern "C" {
-// Two-phase NUTS launches for the group kernels with register-resident edges (PRMwCD, Gaussians of 129..256 dimensions):
-// doublings <= 0 switches them off.  widen != 0: the parked trees are finished by the wavefront-per-particle functor of
-// the model where one exists (PRMwCD), else (and for widen == 0) by the kernel that parked them -- bit for bit the
-// one-launch result then.  widen == 2 (tests): no parking -- every tree runs from its start in the finisher's kernel.
+// Two-phase NUTS launches for the group kernel with register-resident edges (PRMwCD): doublings <= 0 switches them
+// off.  widen != 0: the parked trees are finished by the model's wavefront-per-particle functor (nuts_fin_kernel);
+// widen == 0: by the kernel that parked them -- bit for bit the one-launch result then.  widen == 2 (tests): no
+// parking -- every tree runs from its start in the finisher's kernel.
 int smcn_set_nuts_cap(smcn_ctx* c, int doublings, int widen) {
     CHECK_CTX(c);
     c->nuts_jcap = doublings > 0 ? doublings : 0;

@@ -106,14 +106,13 @@ struct GaussModel {
 // ---------------------------------------------------------------------------
 // PRMwCD with the particle state DISTRIBUTED over the group (coordinate c on lane c % G): the tree
 // state of the NUTS kernel is then DL = ceil(13 / G) doubles per vector and lane instead of 13
-// (the replicated form above needs > 256 VGPRs and spills).  One evaluation:
-//   1. every lane publishes its coordinates in the group's LDS scratch and reads all 13 back,
+// (a replicated form needed > 256 VGPRs and spilled).  One evaluation:
+//   1. every lane reads all 13 coordinates from their owners (cross-lane reads),
 //   2. lane lg accumulates the likelihood partials of observations lg, lg + G, ..,
-//   3. the 13 gradient partials per lane go through the scratch again and lane c % G sums column c
-//      (a reduce-scatter: G reads per owned coordinate instead of 13 butterflies),
+//   3. the 13 gradient partials are summed over the group and lane c % G keeps column c,
 //   4. prior terms are computed by the lane that owns the coordinate.
-// The scratch is private to a group, whose lanes sit in one wavefront: LDS operations of a wave
-// execute in order, so a wave barrier (no s_barrier) orders the exchange.
+// RED must be 2 (see the static_assert below); its default of 0 is kept only because it is part of the template's
+// parameter list, and with it of the kernels' mangled names.  Spell RED = 2 out.
 // ---------------------------------------------------------------------------
 template <int G_, int NOBS, int C_, int RED = 0, int LEVELS = 2, bool FAST = false, int WAVES = 2>
 struct PrmwcdDistModel {
@@ -127,24 +126,18 @@ struct PrmwcdDistModel {
     // the row's free slot, rows at immediate offsets from one per-lane base, exp's constants as scalar operands
     // (v_fma_f64 with an SGPR pair), and the edge cases decided ONCE behind the loop from max(mu) and
     // min(mu + [y == 0]).  Same operations in the same order for every sum: bit-identical results.
-    // RED: how the gradient partials are reduce-scattered: 0 = through G rows of LDS scratch,
-    //      1 = two DPP stages first, then 2 rows (G = 8), 2 = DPP only (no scratch at all)
+    // RED: how the gradient partials are reduce-scattered; 2 = cross-lane sums only, without LDS scratch (the one form left)
+    static_assert(RED == 2, "PrmwcdDistModel: RED = 2 is the only reduce-scatter");
     static constexpr int LDS_LEVELS = LEVELS;             // tree-stack levels kept in LDS (hybrid stack)
     static constexpr int G = G_, C = C_, M = C_ + 1, D_ = C_ + 2, DL = (C_ + 2 + G_ - 1) / G_;
     static constexpr int RS = (C_ + 1 + 1) & ~1;          // design row, padded to an even count
     static constexpr int PR = (D_ + 2) & ~1;              // partial row: 13 -> 14 doubles
-    static constexpr int SCR = RED == 0 ? G_ * PR : (RED == 1 ? (G_ / 4) * PR : 0);   // per-group exchange scratch
     static constexpr int SG = ((NOBS + G_ - 1) / G_) * G_;                   // observations padded to whole passes
     static constexpr int XROWS = FAST ? SG : NOBS;
     static constexpr int DATA = XROWS * RS + 2 * NOBS + (FAST ? 2 * SG : 0);   // design, y, lgamma(y + 1) (+ FAST: [lgamma, y == 0] pairs)
-    static constexpr int SHARED = ((DATA + 1) & ~1) + (256 / G_) * SCR, MIN_WAVES = WAVES;
+    static constexpr int SHARED = (DATA + 1) & ~1, MIN_WAVES = WAVES;
     static constexpr bool DIST = true;
-    // one wavefront per particle (the kernel that finishes parked trees: smcn_set_nuts_cap): its whole tree stack would
-    // fit LDS, but the edges are to live in registers as in the kernel that parked the tree -- the hybrid-stack form of
-    // nuts_kernel with every level in LDS (LEVELS = 10) and an HBM slot nothing ever touches
-    static constexpr bool HYBRID_ALWAYS = G_ >= 64;
     static constexpr bool TWO_PHASE = true;               // nuts_kernel: park / resume at a doubling boundary
-    static constexpr bool FIN_KERNEL = G_ >= 64;          // nuts_fin_kernel (smcn_nuts_fin.hpp) finishes / builds this functor's trees
     // nuts_kernel: its groups (8 particles a wavefront) take a new particle only every 16th loop iteration -- trees of
     // hundreds of leaves lose nothing by the wait, and the groups then do their deep merges in the same iterations
     // (config 4: 1.47 -> 1.52 G leapfrog/s; 2 / 4 / 8 / 16 / 32 / 64 within 1 % of each other)
@@ -156,7 +149,6 @@ struct PrmwcdDistModel {
     double q;
     const double* X;  // [NOBS][RS] in LDS
     const double* y;  // [NOBS]     in LDS
-    double* scr;      // [G][PR]    in LDS, this group's
 
     __device__ int dim() const { return cc + 2; }
     __device__ void init(const double* md, int lg_, double* shared) {
@@ -183,13 +175,7 @@ struct PrmwcdDistModel {
         }
         X = shared;
         y = shared + XROWS * RS;
-        scr = shared + ((DATA + 1) & ~1) + (threadIdx.x / G) * SCR;
         __syncthreads();
-    }
-    static __device__ __forceinline__ void wave_sync() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 
     // One wavefront per particle (G_ = 64, FAST; the kernel that finishes the long trees a two-phase launch parks): the
@@ -286,21 +272,8 @@ struct PrmwcdDistModel {
         }
         // ---- 1. all coordinates to every lane
         double b[PR];
-        if constexpr (RED == 2 && G_ == 4) {                      // four lanes per particle: a quad broadcast, no LDS crossbar
 #pragma unroll
-            for (int j = 0; j < PR; ++j) b[j] = (j < D_) ? quad_read(x[j / G], j % G) : 0.0;
-        } else if constexpr (RED == 2) {
-#pragma unroll
-            for (int j = 0; j < PR; ++j) b[j] = (j < D_) ? group_read<G>(x[j / G], j % G) : 0.0;
-        } else {
-#pragma unroll
-            for (int i = 0; i < DL; ++i)
-                if (lg + G * i < PR) scr[lg + G * i] = (lg + G * i < D_) ? x[i] : 0.0;
-            wave_sync();
-#pragma unroll
-            for (int j = 0; j < PR; ++j) b[j] = scr[j];
-            wave_sync();
-        }
+        for (int j = 0; j < PR; ++j) b[j] = (j < D_) ? group_read<G>(x[j / G], j % G) : 0.0;
         const int Mr = cc + 1;                             // index of g = log Gamma
         double g = 0.0;
         if (FAST && Mr == M) g = b[M];                     // (the shipped shape: no 13-way select)
@@ -386,53 +359,14 @@ struct PrmwcdDistModel {
             for (int j = 0; j < C; ++j) acc[j + 1] = fma(d, row[j], acc[j + 1]);
         }
         // ---- 3. reduce-scatter of the gradient partials: lane c % G ends with the sum of column c
-        if constexpr (RED == 0) {
 #pragma unroll
-            for (int j = 0; j < PR; ++j) scr[lg * PR + j] = acc[j];
-            wave_sync();
+        for (int j = 0; j < D_; ++j) acc[j] = group_sum<G>(acc[j]);
 #pragma unroll
-            for (int i = 0; i < DL; ++i) {
-                const int c = lg + G * i;
-                double sum = 0.0;
-                if (c < PR) {
+        for (int i = 0; i < DL; ++i) {
+            double v = 0.0;
 #pragma unroll
-                    for (int l = 0; l < G; ++l) sum += scr[l * PR + c];
-                }
-                gl[i] = (c < D_) ? sum : 0.0;
-            }
-            wave_sync();
-        } else if constexpr (RED == 1) {
-            static_assert(RED != 1 || G >= 4, "RED = 1 needs quads");
-#pragma unroll
-            for (int j = 0; j < D_; ++j) {
-                acc[j] += dpp_mov<0xB1>(acc[j]);
-                acc[j] += dpp_mov<0x4E>(acc[j]);       // every lane of a quad holds the quad's sum
-            }
-#pragma unroll
-            for (int j = 0; j < D_; ++j)
-                if ((j & 3) == (lg & 3)) scr[(lg >> 2) * PR + j] = acc[j];
-            wave_sync();
-#pragma unroll
-            for (int i = 0; i < DL; ++i) {
-                const int c = lg + G * i;
-                double sum = 0.0;
-                if (c < D_) {
-#pragma unroll
-                    for (int l = 0; l < G / 4; ++l) sum += scr[l * PR + c];
-                }
-                gl[i] = sum;
-            }
-            wave_sync();
-        } else {
-#pragma unroll
-            for (int j = 0; j < D_; ++j) acc[j] = group_sum<G>(acc[j]);
-#pragma unroll
-            for (int i = 0; i < DL; ++i) {
-                double v = 0.0;
-#pragma unroll
-                for (int j = i * G; j < (i + 1) * G && j < D_; ++j) v = (j - i * G == lg) ? acc[j] : v;
-                gl[i] = v;
-            }
+            for (int j = i * G; j < (i + 1) * G && j < D_; ++j) v = (j - i * G == lg) ? acc[j] : v;
+            gl[i] = v;
         }
         // ---- 4. priors on the owning lane: inv_gamma(Gamma | 2, 1.3) + Jacobian for g,
         //         exponential-power terms for Beta_2..Beta_M (:36-38); Beta_1 is flat

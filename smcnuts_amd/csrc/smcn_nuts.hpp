@@ -127,23 +127,12 @@ __host__ __device__ constexpr int nuts_slot_doubles(int VS) {
     return n;
 }
 
-// HBM_STACK: the per-particle tree stack (48 D + 32 doubles; 98.6 KB at D = 256) does not
-// fit in LDS; each resident group owns a slot of a global scratch buffer instead (lane-
-// contiguous vectors, so every access is a coalesced 512-byte row).
+// HBM_STACK: the tree stacks of a block's groups (nuts_slot_doubles each; 205 KB for PRMwCD's 32 groups) do not
+// fit in LDS; each resident group owns a slot of a global scratch buffer instead (lane-contiguous vectors).
 // With the stack in HBM the first Model::LDS_LEVELS levels (the ones touched every 2nd / 4th leaf) still live
 // in LDS: 1/2 + 1/4 + .. of all parks and merges never leave the CU.
 __host__ __device__ constexpr int nuts_hybrid_lds_doubles(int VS, int levels) { return levels * (2 * VS + 2 * VS + 3); }
 
-__host__ __device__ constexpr int RL_X0(bool wide, int dl) { return wide ? dl : 1; }
-// which Model / stack combinations write NutsArgs::kin0, kin1, moved
-template <class Model, bool HBM_STACK>
-constexpr bool nuts_kernel_writes_stats() { return HBM_STACK && Model::DIST && Model::DL <= 4 && Model::G == 64; }
-
-// models that ask for the hybrid (LDS levels + HBM slot) stack whatever their size
-template <class M, class = void>
-struct model_hybrid_always { static constexpr bool value = false; };
-template <class M>
-struct model_hybrid_always<M, std::enable_if_t<M::HYBRID_ALWAYS>> { static constexpr bool value = true; };
 // models whose kernels can park a tree at a doubling boundary / take a parked one up (NutsArgs::jcap, resume_in): opt-in,
 // the extra live state costs registers (the D = 256 Gaussian kernel spilled 252 bytes per lane with it)
 template <class M, class = void>
@@ -178,13 +167,8 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
     const int lane = (int)(threadIdx.x & 63u);
     const int lg = lane & (G - 1);
     constexpr int MSH = (Model::SHARED + 1) & ~1;   // block-shared model data first
-    // (G == 1, one lane per particle: the HBM slots of a block are LANE-INTERLEAVED -- element k of lane t at
-    //  [k][t] -- so that lanes at the same place of their trees touch one 512-byte row; SK = the stride between elements)
-    constexpr int SK = (HBM_STACK && G == 1) ? kNutsBlock : 1;
-    double* const slot = HBM_STACK
-        ? (G == 1 ? a.scratch + (int64_t)blockIdx.x * kNutsBlock * SLOT + threadIdx.x
-                  : a.scratch + ((int64_t)blockIdx.x * (kNutsBlock / G) + threadIdx.x / G) * SLOT)
-        : lds + MSH + (threadIdx.x / G) * SLOT;
+    double* const slot = HBM_STACK ? a.scratch + ((int64_t)blockIdx.x * (kNutsBlock / G) + threadIdx.x / G) * SLOT
+                                   : lds + MSH + (threadIdx.x / G) * SLOT;
 
     // Pointers used once per tree (inputs, outputs, statistics) are re-read from the kernel-argument segment where they
     // are needed instead of occupying ~30 scalar registers across the leaf loop (the PRMwCD kernel spilled scalars to
@@ -235,7 +219,7 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
             } else {
                 const glbp sl = (glbp)slot;
 #pragma unroll
-                for (int i = 0; i < DL; ++i) sl[(off + i * G + lg) * SK] = v[i];
+                for (int i = 0; i < DL; ++i) sl[off + i * G + lg] = v[i];
             }
         } else if constexpr (DIST) {
             if (lo >= 0) {
@@ -262,7 +246,7 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
             } else {
                 const glbp sl = (glbp)slot;
 #pragma unroll
-                for (int i = 0; i < DL; ++i) v[i] = sl[(off + i * G + lg) * SK];
+                for (int i = 0; i < DL; ++i) v[i] = sl[off + i * G + lg];
             }
         } else if (DIST && lo >= 0) {
 #pragma unroll
@@ -275,7 +259,7 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
     auto sstore = [&](int off, double v) {
         const int lo = lds_off(off);
         if constexpr (HBM_STACK) {
-            if (lg == 0) { if (lo >= 0) ((ldsp)hyb)[lo] = v; else ((glbp)slot)[off * SK] = v; }
+            if (lg == 0) { if (lo >= 0) ((ldsp)hyb)[lo] = v; else ((glbp)slot)[off] = v; }
         } else {
             if (lg == 0) { if (lo >= 0) hyb[lo] = v; else slot[off] = v; }
         }
@@ -284,7 +268,7 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
         const int lo = lds_off(off);
         if constexpr (HBM_STACK) {
             double v;
-            if (lo >= 0) v = ((ldsp)hyb)[lo]; else v = ((glbp)slot)[off * SK];
+            if (lo >= 0) v = ((ldsp)hyb)[lo]; else v = ((glbp)slot)[off];
             return v;
         } else {
             return lo >= 0 ? hyb[lo] : slot[off];
@@ -328,16 +312,11 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
     bool overflow = false;
 #pragma unroll
     for (int k = 0; k < DL; ++k) { x[k] = 0.0; r[k] = 0.0; g[k] = 0.0; }
-    // HBM-stack models (D = 256: one wavefront per particle, 4 coordinates per lane): the two edges of the
-    // trajectory and the selected sample -- touched at every doubling -- stay in REGISTERS (8 vectors = 64 VGPRs),
-    // updated by selects; only the deeper tree-stack levels travel to the HBM slot.
+    // HBM-stack models (PRMwCD: 8 lanes per particle, 2 coordinates per lane): the two edges of the trajectory and the
+    // selected sample -- touched at every doubling -- stay in REGISTERS, updated by selects; only the deeper tree-stack
+    // levels travel to the HBM slot.
     constexpr bool REGE = HBM_STACK && DIST && DL <= 4;   // (8 coordinates per lane would spill)
     constexpr bool REGE_K = REGE && TWO_PHASE && model_two_phase<Model>::value;   // NutsArgs::jcap / resume_in
-    // (edges in the slot -- one lane per particle, 13 coordinates --: such a kernel can PARK a tree for the finisher, it
-    //  never takes one up)
-    constexpr bool PARK_SLOT = !REGE && TWO_PHASE && model_two_phase<Model>::value;
-    constexpr bool WIDE = REGE && G == 64;                // the wavefront sees the whole particle: statistics in-kernel
-    double x0[RL_X0(WIDE, DL)];
     constexpr int RL = REGE ? DL : 1;
     double emx[RL], emr[RL], emg[RL], epx[RL], epr[RL], epg[RL], slx[RL], slr[RL], slp0 = 0.0, slp1 = 0.0;
 #pragma unroll
@@ -398,30 +377,11 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
                 none = t >= a.pend[0];
                 resumed = !none;
                 if (resumed) t = a.pend[1 + t];
-            } else if constexpr (HBM_STACK && DIST && G == 64) {
-                // One wavefront per particle and the [D][N] layout: a wavefront touches 8 bytes of every 64-byte line
-                // of its particle's coordinates, and the other 56 belong to the 7 neighbouring particles.  Lines
-                // (8 particles) are dealt to the XCDs -- blocks go round-robin over the XCDs, so blockIdx % 8 names the
-                // XCD, each with a queue of its own -- and consecutive grabs of an XCD take the particles of one line:
-                // its L2 then fetches / writes back every line once instead of up to 8 times.
-                const unsigned int nq = gridDim.x < 8u ? gridDim.x : 8u;
-                const unsigned int xq = blockIdx.x % nq;
-                int64_t pp = -1;
-                for (;;) {
-                    t = 0;
-                    if (lg == 0) t = atomicAdd(a.queue + 8 + xq, 1u);
-                    t = (unsigned int)__builtin_amdgcn_readfirstlane((int)t);   // (G == 64: lane 0 of the wavefront)
-                    const int64_t line = (int64_t)(t >> 3) * nq + xq;
-                    if (line * 8 >= N) break;
-                    if (line * 8 + (t & 7u) < N) { pp = line * 8 + (t & 7u); break; }
-                }
-                none = pp < 0;
-                t = none ? 0u : (unsigned int)pp;
             } else {
                 if (lg == 0) t = atomicAdd(a.queue, 1u);
                 t = (unsigned int)group_read_i<G>((int)t, 0);
                 none = (int64_t)t >= N;
-                if constexpr (REGE_K && G < 64) {
+                if constexpr (REGE_K) {
                     if (none) {
                         // no fresh particle left: a tree this launch has parked at its inner level, the oldest first.  (A
                         // group that finds none leaves: whoever parks a tree looks here right afterwards, so every entry is
@@ -488,11 +448,6 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
                     const double* const sc = rec + 8 * Dr;
                     slp0 = ld(sc); slp1 = ld(sc + 1); logu = ld(sc + 2);
                     n = (int)ld(sc + 3); j = (int)ld(sc + 4); nleap = (int)ld(sc + 5); q = (uint32_t)ld(sc + 6); overflow = ld(sc + 7) != 0.0;
-                    if constexpr (WIDE) {
-                        const double* const xin = ka->x;
-#pragma unroll
-                        for (int k = 0; k < DL; ++k) x0[k] = cv[k] ? xin[cidx[k] + p] : 0.0;
-                    }
                     qbase = q - (q % (2u * G));
                     if (taped) { const int64_t* const to = kargs()->tape_off; toff = to[p]; tlen = to[p + 1] - toff; }
                     else refill();
@@ -575,11 +530,6 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
             // nuts.py:66-87
             const double kin_start = dot(r, r);
             const double H0 = lp - 0.5 * kin_start;
-            if constexpr (WIDE) {
-#pragma unroll
-                for (int k = 0; k < DL; ++k) x0[k] = x[k];
-                if (lg == 0) { const auto kw = kargs(); if (kw->kin0) kw->kin0[p] = kin_start; }
-            }
             double ex = draw();
             if (!taped) ex = -log1p(-ex);
             logu = H0 - ex;
@@ -643,41 +593,6 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
                     sstore(crec + 2 * VS, clp); sstore(crec + 2 * VS + 1, cll); sstore(crec + 2 * VS + 2, (double)nsub);
                     break;
                 }
-                if constexpr (G == 1 && HBM_STACK) {
-                    // One lane per particle: the stack levels above the LDS one live in HBM, and nothing hides a round trip
-                    // at one wavefront per SIMD.  Everything this merge may need -- the pending candidate, its three scalars,
-                    // the sub-tree's first leaf -- is asked for at once (one trip per level instead of three dependent ones);
-                    // the candidate is loaded whether or not the draw keeps it.
-                    const int i0 = (i >> (m + 1)) << (m + 1);
-                    const int s = (i0 == 0) ? j : (__ffs(i0) - 1);
-                    double tx[DL], tr[DL], fx[DL], fr[DL];
-                    vload(CAND + m * CREC, tx);
-                    vload(CAND + m * CREC + VS, tr);
-                    vload(FIRST + (s - 1) * 2 * VS, fx);
-                    vload(FIRST + (s - 1) * 2 * VS + VS, fr);
-                    const double n1d = sload(crec + 2 * VS + 2), tlp = sload(crec + 2 * VS), tll = sload(crec + 2 * VS + 1);
-                    const double u = draw();  // nuts.py:142, always
-                    const int n1 = (int)n1d;
-                    const int den = (n1 + nsub) > 1 ? (n1 + nsub) : 1;
-                    if (!(u < (double)nsub / (double)den)) {
-#pragma unroll
-                        for (int k = 0; k < DL; ++k) { cx[k] = tx[k]; cr[k] = tr[k]; }
-                        clp = tlp; cll = tll;
-                    }
-                    nsub += n1;  // :146
-                    double sa = 0.0, sb = 0.0;  // nuts.py:152-160
-#pragma unroll
-                    for (int k = 0; k < DL; ++k) {
-                        const double dx = dir > 0 ? (x[k] - fx[k]) : (fx[k] - x[k]);
-                        const double rmn = dir > 0 ? fr[k] : r[k];
-                        const double rpl = dir > 0 ? r[k] : fr[k];
-                        sa = fma(dx, rmn, sa);
-                        sb = fma(dx, rpl, sb);
-                    }
-                    ssub = (sa < 0.0) || (sb < 0.0);  // :148
-                    ++m;
-                    continue;
-                }
                 const double u = draw();  // nuts.py:142, always
                 int n1 = (int)sload(crec + 2 * VS + 2);
                 if constexpr (G == 64) n1 = __builtin_amdgcn_readfirstlane(n1);
@@ -734,8 +649,8 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
                         sa = fma(dx, emr[k], sa);
                         sb = fma(dx, epr[k], sb);
                     }
-                    if constexpr (G == 64) wave_sum2(sa, sb, sa, sb);
-                    else { sa = group_sum<G>(sa); sb = group_sum<G>(sb); }
+                    sa = group_sum<G>(sa);
+                    sb = group_sum<G>(sb);
                     stop = ssub || (sa < 0.0) || (sb < 0.0);  // :105
                 } else {
                     vstore(eo, x); vstore(eo + VS, r); vstore(eo + 2 * VS, g);
@@ -759,16 +674,8 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
                             if (cv[k]) { xo[cidx[k] + p] = xs[k]; ro[cidx[k] + p] = rs[k]; }
                         }
                     }
-                    if constexpr (WIDE) {
-                        const double kin_end = dot(rs, rs);
-                        bool all_moved = true;
-#pragma unroll
-                        for (int k = 0; k < DL; ++k) all_moved = all_moved && (!cv[k] || xs[k] != x0[k]);
-                        const bool every = __ballot(!all_moved) == 0ull;
-                        if (lg == 0 && ka->kin1) { ka->kin1[p] = kin_end; ka->moved[p] = every ? 1 : 0; }
-                    }
                     if (lg == 0) {
-                        ka->lpri1[p] = REGE ? slp0 : slot[SELP * SK]; ka->llik1[p] = REGE ? slp1 : slot[(SELP + 1) * SK];
+                        ka->lpri1[p] = REGE ? slp0 : slot[SELP]; ka->llik1[p] = REGE ? slp1 : slot[SELP + 1];
                         ka->nleap[p] = nleap; ka->depth[p] = j; ka->ndraws[p] = (int32_t)q;
                         ka->flags[p] = overflow ? 1 : 0;
                     }
@@ -811,33 +718,6 @@ __global__ void __launch_bounds__(kNutsBlock, Model::MIN_WAVES) nuts_kernel(Nuts
                                 __hip_atomic_store(ka->mq + 16 + at, (unsigned int)p + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                 atomicAdd(reinterpret_cast<int*>(ka->mq + 5), 1);
                             }
-                        }
-                    }
-                    phase = NEED;
-                } else if (PARK_SLOT && kargs()->jcap > 0 && j == kargs()->jcap) {
-                    if constexpr (PARK_SLOT) {    // park from the slot: the same record as above
-                        const auto ka = kargs();
-                        int Dr = D;
-                        asm volatile("" : "+v"(Dr));
-                        double* const rec = ka->resume + p * (8 * (int64_t)Dr + 8);
-                        constexpr int src[8] = {EM, EM + VS, EM + 2 * VS, EP, EP + VS, EP + 2 * VS, SEL, SEL + VS};
-#pragma unroll
-                        for (int v8 = 0; v8 < 8; ++v8) {
-                            double t[DL];
-                            vload(src[v8], t);
-#pragma unroll
-                            for (int k = 0; k < DL; ++k) {
-                                const int c = lg + G * k;
-                                if (cv[k]) rec[v8 * Dr + c] = t[k];
-                            }
-                        }
-                        const double s0 = sload(SELP), s1 = sload(SELP + 1);
-                        if (lg == 0) {
-                            double* const sc = rec + 8 * Dr;
-                            sc[0] = s0; sc[1] = s1; sc[2] = logu;
-                            sc[3] = (double)n; sc[4] = (double)j; sc[5] = (double)nleap; sc[6] = (double)q; sc[7] = overflow ? 1.0 : 0.0;
-                            const unsigned int at = atomicAdd(ka->pend, 1u);
-                            ka->pend[1 + at] = (unsigned int)p;
                         }
                     }
                     phase = NEED;

@@ -1,21 +1,7 @@
-// NUTS proposal, second generation of the kernel for models whose state is
-// replicated on the G lanes of a group (arma, PRMwCD): same algorithm and same
-// results as nuts_kernel (smcn_nuts.hpp; reference smcnuts/proposal/nuts.py:34-175),
-// restructured around what the in-kernel profile showed -- two thirds of the
-// cycles went into the divergent tree bookkeeping, not into the gradient:
-//
-//  * per-particle INPUT and OUTPUT records (16-byte chunks, one per lane) instead
-//    of strided [D][N] accesses; the next particle's record is prefetched while the
-//    current tree is built, so the queue never exposes HBM latency;
-//  * the slice variable's Exp(1) is drawn by the prep kernel (no log1p here);
-//  * uniforms come from a 32-entry LDS ring refilled 16 at a time by ONE Philox
-//    call per lane at a convergent point (a draw is one broadcast ds_read_b64);
-//  * the top-level accept / U-turn of a doubling is one more level of the same
-//    merge loop; merge probabilities are compared through the sign of one FMA
-//    (u*den - n'' < 0) instead of a division;
-//  * U-turn dot products are computed once and sign-flipped by direction;
-//  * LDS vectors are moved as 16-byte accesses; the start of a tree and the start
-//    of a doubling share one code path.
+// Records of the lane NUTS kernel (smcn_nuts3.hpp) and the kernels around it: the prep kernel that packs each
+// particle's start point, momentum and slice exponential, and the post kernel that unpacks the results and
+// re-weights with the forward L-kernel.  (The layouts were first built for a second-generation group kernel, since retired
+// with the other A/B variants.)
 #pragma once
 #include "smcn_nuts.hpp"
 
@@ -28,21 +14,6 @@ namespace smcn {
 __host__ __device__ constexpr int n2_vp(int DL) { return (DL + 1) & ~1; }
 __host__ __device__ constexpr int n2_in_doubles(int DL) { return 2 * n2_vp(DL) + 2; }
 __host__ __device__ constexpr int n2_out_doubles(int DL) { return 2 * n2_vp(DL) + 6; }
-// L = tree-stack levels kept in LDS (Model::N2_LDS_LEVELS); deeper levels live in a global
-// overflow area of n2_ovf_doubles per resident group.
-__host__ __device__ constexpr int n2_slot_doubles(int DL, int L = 10) {
-    const int VP = n2_vp(DL);
-    int n = n2_out_doubles(DL) + 6 * VP + L * 2 * VP + L * (2 * VP + 4) + 32;
-    n = (n + 1) & ~1;
-    // slot stride = an odd multiple of 4 banks: the (up to 16) groups of a wave land on disjoint
-    // 4-bank sets.  (L = 10, DL = 4 keeps the 274 the kernel was tuned with.)
-    if (L == 10) { while ((2 * n) % 64 != 36) n += 2; }
-    else { while (n % 4 != 2) n += 2; }
-    return n;
-}
-__host__ __device__ constexpr int n2_ovf_doubles(int DL, int L) {
-    return (10 - L) * (2 * n2_vp(DL) + 2 * n2_vp(DL) + 4);
-}
 
 struct Nuts2Args {
     int64_t N;
@@ -59,7 +30,7 @@ struct Nuts2Args {
     const double* tape;
     const int64_t* tape_off;
     unsigned long long* prof;
-    double* ovf;        // overflow tree-stack levels, one area per resident group (models with N2_LDS_LEVELS < 10)
+    double* ovf;        // overflow tree-stack levels, one area per resident wavefront (smcn_nuts3.hpp)
     const double* logw0 = nullptr;   // nuts3 with B > 1 and the forward L-kernel: the log-weights before the block;
                                      // transitions b < B-1 then leave COMPACT records [x'(VP), logw_b, stats0]
     // nuts3 with fewer lanes than particles (smcn_nuts3.hpp, QUEUE): a particle's block of B transitions is handed on in SEGMENTS of seg_len
@@ -73,68 +44,10 @@ struct Nuts2Args {
                                      // re-associated sums); bit 1 = idle lanes draw the stragglers' uniforms (always on: same bits)
 };
 
-// prep: momentum draw (samples.py:155) + slice exponential (nuts.py:69) + packing
-// of the input records.  r_in != null: momenta supplied by the caller.
-__global__ void __launch_bounds__(256) nuts2_prep_kernel(const double* x, const double* r_in, double* r_out, double* in,
-                                                         int64_t N, int D, int VP, int64_t particle_base, uint64_t seed,
-                                                         uint32_t iter, int B, const double* tape,
-                                                         const int64_t* tape_off) {
-    // One thread builds one record (2 VP + 2 doubles: stride 80 B at D = 4); the block's 256 records
-    // are contiguous in memory, so they are staged in LDS and leave as coalesced 16-byte chunks.
-    extern __shared__ double prep_stage[];
-    using d2 = double __attribute__((ext_vector_type(2)));
-    const int RS = 2 * VP + 2;
-    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x, t = t0 + threadIdx.x;
-    const bool live = t < N * B;
-    if (live) {
-        const int b = (int)(t / N);
-        const int64_t p = t - (int64_t)b * N;
-        double* rec = prep_stage + (int64_t)threadIdx.x * RS;
-        for (int c = 0; c < VP; ++c) rec[c] = (c < D && b == 0) ? x[(int64_t)c * N + p] : 0.0;
-        if (r_in) {   // caller-supplied momenta (single transition only)
-            for (int c = 0; c < VP; ++c) rec[VP + c] = (c < D) ? r_in[(int64_t)c * N + p] : 0.0;
-        } else {
-            for (int m = 0; 2 * m < VP; ++m) {
-                double z0 = 0.0, z1 = 0.0;
-                if (2 * m < D) {
-                    const u32x4 o = philox4x32_10({(uint32_t)m, (uint32_t)(particle_base + p), iter + (uint32_t)b,
-                                                   kStreamMomentum}, (uint32_t)seed, (uint32_t)(seed >> 32));
-                    const double u1 = u53(o.a, o.b), u2 = u53(o.c, o.d);
-                    const double rad = sqrt(-2.0 * log1p(-u1));
-                    double sn, cs;
-                    sincospi(2.0 * u2, &sn, &cs);        // exact argument; cheaper than sincos(2 pi u2)
-                    z0 = rad * cs;
-                    z1 = (2 * m + 1 < D) ? rad * sn : 0.0;
-                    if (b == B - 1) {   // the resident r is the last transition's momentum
-                        r_out[(int64_t)(2 * m) * N + p] = z0;
-                        if (2 * m + 1 < D) r_out[(int64_t)(2 * m + 1) * N + p] = z1;
-                    }
-                }
-                rec[VP + 2 * m] = z0;
-                rec[VP + 2 * m + 1] = z1;
-            }
-        }
-        double e0;
-        if (tape) {
-            const int64_t o = tape_off[p];
-            e0 = (tape_off[p + 1] > o) ? tape[o] : 0.5;
-        } else {
-            e0 = -log1p(-philox_uniform(seed, iter + (uint32_t)b, (uint32_t)(particle_base + p), kStreamNuts, 0u));
-        }
-        rec[2 * VP] = e0;
-        rec[2 * VP + 1] = 0.0;
-    }
-    __syncthreads();
-    const int64_t nrec = (N * B - t0) < (int64_t)blockDim.x ? (N * B - t0) : (int64_t)blockDim.x;   // records of this block
-    const int64_t nch = nrec * (RS / 2);
-    d2* dst = reinterpret_cast<d2*>(in + t0 * RS);
-    const d2* src = reinterpret_cast<const d2*>(prep_stage);
-    for (int64_t c = threadIdx.x; c < nch; c += blockDim.x) dst[c] = src[c];
-}
-
-// The same for the lane kernel (smcn_nuts3.hpp), whose records are PAIR-MAJOR ([transition][16-byte pair][N]: consecutive
-// threads write consecutive pairs, no staging): the start point only for the block's first transition (the kernel
-// continues from its own samples), momentum and slice exponential for every transition.
+// prep: momentum draw (samples.py:155) + slice exponential (nuts.py:69) + packing of the input records, which are
+// PAIR-MAJOR ([transition][16-byte pair][N]: consecutive threads write consecutive pairs, no staging): the start point only
+// for the block's first transition (the kernel continues from its own samples), momentum and slice exponential for every
+// transition.  r_in != null: momenta supplied by the caller.
 template <int D>
 __global__ void __launch_bounds__(256) nuts3_prep_kernel(const double* x, const double* r_in, double* r_out, double* in,
                                                          int64_t N, int64_t particle_base, uint64_t seed, uint32_t iter,
@@ -161,7 +74,7 @@ __global__ void __launch_bounds__(256) nuts3_prep_kernel(const double* x, const 
         if (r_in) {   // caller-supplied momenta (single transition only)
             z.x = r_in[(int64_t)(2 * m) * N + p];
             z.y = (2 * m + 1 < D) ? r_in[(int64_t)(2 * m + 1 < D ? 2 * m + 1 : 0) * N + p] : 0.0;
-        } else {      // the draws of nuts2_prep_kernel: same keys, same arithmetic
+        } else {      // Box-Muller on one Philox draw per coordinate pair
             const u32x4 o = philox4x32_10({(uint32_t)m, (uint32_t)(particle_base + p), iter + (uint32_t)b, kStreamMomentum},
                                           (uint32_t)seed, (uint32_t)(seed >> 32));
             const double u1 = u53(o.a, o.b), u2 = u53(o.c, o.d);

@@ -1,6 +1,6 @@
 // NUTS proposal, third generation: ONE LANE OWNS ONE PARTICLE.
 //
-// Same algorithm, same draws and same results as nuts_kernel / nuts2_kernel (reference
+// Same algorithm, same draws and same results as nuts_kernel (reference
 // smcnuts/proposal/nuts.py:34-175: rvs, generate_nuts_samples, build_tree, NUTSLeapfrog,
 // stop_criterion), for models whose value + gradient a single lane can evaluate without
 // cross-lane traffic (LaneModel concept below: arma by forward sensitivities).
@@ -715,13 +715,8 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
     auto take_record = [&](bool c) __attribute__((always_inline)) {   // r, e0 of the transition about to start, from the prefetched record
         __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the record's LDS-DMA (a tree old) has landed
         d2 pr[VH + 1];
-#ifdef SMCN_ABL_NOTAKE
-#pragma unroll
-        for (int k = 0; k <= VH; ++k) { pr[k].x = 0.3 + 0.1 * k; pr[k].y = -0.2; }
-#else
 #pragma unroll
         for (int k = 0; k <= VH; ++k) pr[k] = L[(PREF + k) * 64];
-#endif
         if (c) {
 #pragma unroll
             for (int k = 0; k < VH; ++k) {
@@ -740,9 +735,6 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
         d2 t;
         t.x = u53(o.a, o.b);
         t.y = u53(o.c, o.d);
-#ifdef SMCN_ABL_NOPHILOX
-        t.x = 0.37 + 1e-3 * (qfill & 255u); t.y = 0.61;
-#endif
         L[(RING + ((qfill >> 1) & 3u)) * 64] = t;
         qfill += 2u;
     };
@@ -805,7 +797,6 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
         out_cur += out_stride;
         d2 t;
         const unsigned long long s0 = (unsigned long long)(unsigned)nldone | ((unsigned long long)(unsigned)j << 32);
-#ifndef SMCN_ABL_NOSTORE   // (ablation build: prices the record stores)
 #pragma unroll
         for (int k = 0; k < VH; ++k) {   // (the record is contiguous, unlike the lane-private layouts)
             t.x = rx[2 * k];
@@ -843,7 +834,6 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
             t.y = __longlong_as_double((long long)s1);
             orec[(2 * VH + 2) * N] = t;
         }
-#endif
     };
     unsigned int it = 0u;            // (QUEUE: the iteration's number)
     for (;; ++it) {
@@ -870,11 +860,7 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
             need = need > 7 ? 7 : need;
             const unsigned long long am0 = __ballot(act);
             const int na0 = __popcll(am0);
-#ifdef SMCN_ABL_NOTAILHELP   // (A/B build: every lane draws for itself at every population)
-            if (false) {
-#else
             if (Model::HAS_WIDE && (a.wide & 2) != 0 && na0 <= 16) {   // (the draws are the same bits whoever computes them)
-#endif
                 // Few trees left: a Philox round costs the wavefront the same for four lanes as for 64, so when a lane runs
                 // low FOUR lanes draw for each tree -- lanes 4g .. 4g+3 the next four blocks of the g-th active lane's
                 // stream, straight into its ring, as far as they fit -- and the next round is ~5 iterations away, not 1.
@@ -1005,14 +991,12 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
                 if (need && csrc >= 0) {
                     if (csrc == 0) { movv(cx, c0x); movv(cr, c0r); movd2(cl, c0l); }
                     else if (csrc == 1) { movv(cx, c1x); movv(cr, c1r); movd2(cl, c1l); }
-#ifndef SMCN_ABL_NOCANDLDS
                     else with_cand(csrc, [&](auto cp) __attribute__((always_inline)) {
                         double tx[D], tr[D];
                         ld_vec(cp, tx); ld_vec(cp + VH * 64, tr);
                         const d2 tl = cp[2 * VH * 64];
                         movv(cx, tx); movv(cr, tr); movd2(cl, tl);
                     });
-#endif
                 }
             };
             // one merge (nuts.py:136-148) of the parked first half (count nfirst) whose sub-tree began at
@@ -1057,16 +1041,9 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
             }
             while (how == 0) {       // levels >= 2 (LDS, then the overflow area)
                 double fx[D], fr[D];
-#ifdef SMCN_ABL_NOMERGELDS   // (ablation builds price one piece of the bookkeeping each: wrong trees, per-iteration cycles only)
-                const int nfirst = 1;
-#pragma unroll
-                for (int k = 0; k < D; ++k) { fx[k] = ex[k]; fr[k] = er[k]; }
-                const double u = 0.5; ++q;
-#else
                 const int nfirst = (int)*nst_ptr(m);
                 with_first(m + 1, [&](auto fp) __attribute__((always_inline)) { ld_vec(fp, fx); ld_vec(fp + VH * 64, fr); });
                 const double u = ring_draw();     // :142, always
-#endif
                 merge(m, u, nfirst, fx, fr);
                 ++m;
                 how = ends();
@@ -1134,9 +1111,7 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
                         PROF(10);
                         emit_record(!more, qdone, ovdone, nldone);
                         PROF(13);
-#ifndef SMCN_ABL_NOLOAD
                         if (more && bdone + 2 < a.B) request();
-#endif
                     }
                 } else {
                     start_doubling = true;
@@ -1257,10 +1232,8 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
                         have_next = true;
                     }
                 }
-#ifndef SMCN_ABL_NOLOAD
                 // the prefetch slots get the first record of the job just taken, or the lane's own next record
                 if (got || (runs && b + 1 < a.B)) request();
-#endif
             }
         }
         PROF(11);
@@ -1269,12 +1242,6 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
             double kin = 0.0;
 #pragma unroll
             for (int k = 0; k < D; ++k) kin = fma(r[k], r[k], kin);
-#ifdef SMCN_ABL_INITMOVS   // (ablation: what do moves under a FEW-lane exec mask cost?  the init block's moves repeated)
-            if (init) {
-#pragma unroll
-                for (int rep = 0; rep < SMCN_ABL_INITMOVS; ++rep) { movv(rx, x); movv(rr, r); mov64(k0, kin); mov64(lpri0, lpri); }
-            }
-#endif
             if (init) {
                 mov64(logu, (lp - 0.5 * kin) - logu);          // H0 - Exp(1)
                 mov64(k0, kin);                                // |r0|^2: q = N(r0; 0, I) of the weight update

@@ -28,10 +28,7 @@
 
 namespace smcn {
 
-#ifndef SMCN_WAVE_R0
-#define SMCN_WAVE_R0 2        // A/B: the start momentum comes back from global memory (0), from an LDS slot (1), from registers (2)
-#endif
-constexpr int kWaveLdsSlots = 4;   // LDS slots of a wavefront (4 KB each at 4 coordinates per lane): the start momentum + first leaves 1..3
+constexpr int kWaveLdsSlots = 4;   // LDS slots of a wavefront (4 KB each at 4 coordinates per lane): first leaves 1..4
 
 template <class M, class = void>
 struct model_wave_kernel { static constexpr bool value = false; };
@@ -51,13 +48,13 @@ __device__ __forceinline__ double wfirst(double v) {
 
 // FULL: every lane's DL coordinates are real (D = 64 DL: no masking anywhere); HAS: the target has a likelihood factor
 // (both are facts of the model data the launcher knows: compile-time here, so that neither costs a select per coordinate)
-// SLOTS: LDS slots per wavefront (slot 0: the start momentum r0, which the replay needs again; slots 1..: first leaves);
+// SLOTS: LDS slots per wavefront, the first leaves of the lowest levels (the start momentum r0, which the replay needs
+// again, stays in registers);
 // WAVES: wavefronts per SIMD the kernel is compiled for.
 template <class Model, bool FULL, bool HAS, int SLOTS = kWaveLdsSlots, int WAVES = Model::MIN_WAVES>
 __global__ void __launch_bounds__(kNutsBlock, WAVES) nuts_wave_kernel(NutsArgs a) {
     static_assert(Model::G == 64 && Model::DIST && (Model::DL % 2) == 0, "one wavefront per particle, pairs of coordinates");
-    constexpr int R0S = SMCN_WAVE_R0 == 1 ? 1 : 0;
-    constexpr int DL = Model::DL, LF = SLOTS - R0S, SLOTD = wave_slot_doubles(DL);
+    constexpr int DL = Model::DL, LF = SLOTS, SLOTD = wave_slot_doubles(DL);
     using d2 = double __attribute__((ext_vector_type(2)));
     using lds2 = __attribute__((address_space(3))) d2*;
     using glb2 = __attribute__((address_space(1))) d2*;
@@ -66,8 +63,7 @@ __global__ void __launch_bounds__(kNutsBlock, WAVES) nuts_wave_kernel(NutsArgs a
     const int lane = (int)(threadIdx.x & 63u);
     const int wave = (int)(threadIdx.x >> 6);
     // first leaves: [slot][pair][lane] pairs of doubles -- x pairs first, then r pairs; every access a conflict-free b128
-    const lds2 r0s = (lds2)(lds + wave * SLOTS * SLOTD) + lane;            // slot 0: r0 in its first DL / 2 pairs
-    const lds2 fl = r0s + R0S * (SLOTD / 2);
+    const lds2 fl = (lds2)(lds + wave * SLOTS * SLOTD) + lane;
     const glb2 fg = (glb2)(a.scratch + ((int64_t)blockIdx.x * (kNutsBlock / 64) + wave) * (int64_t)(kMaxLevels * SLOTD)) + lane;
 
     auto kargs = [&]() __attribute__((always_inline)) {     // per-tree pointers: re-read where used (smcn_nuts.hpp)
@@ -254,14 +250,9 @@ __global__ void __launch_bounds__(kNutsBlock, WAVES) nuts_wave_kernel(NutsArgs a
                 x0[k] = x[k];
             }
         }
-        [[maybe_unused]] double r0[DL];
-        if constexpr (SMCN_WAVE_R0 == 1) {
+        double r0[DL];
 #pragma unroll
-            for (int t = 0; t < DL / 2; ++t) r0s[t * 64] = d2{r[2 * t], r[2 * t + 1]};
-        } else if constexpr (SMCN_WAVE_R0 == 2) {
-#pragma unroll
-            for (int k = 0; k < DL; ++k) r0[k] = r[k];
-        }
+        for (int k = 0; k < DL; ++k) r0[k] = r[k];
         q = 0; qbase = 0; overflow = false;
         if (taped) { toff = a.tape_off[p]; tlen = a.tape_off[p + 1] - toff; }
         else refill();
@@ -369,22 +360,8 @@ __global__ void __launch_bounds__(kNutsBlock, WAVES) nuts_wave_kernel(NutsArgs a
         double lpri1 = lpri0, llik1 = llik0, kin1 = kin_start;
         bool moved = false;
         // this tree's start comes back
-        if constexpr (SMCN_WAVE_R0 == 1) {
 #pragma unroll
-            for (int t = 0; t < DL / 2; ++t) {
-                const d2 v = r0s[t * 64];
-                r[2 * t] = v.x; r[2 * t + 1] = v.y;
-            }
-        } else if constexpr (SMCN_WAVE_R0 == 2) {
-#pragma unroll
-            for (int k = 0; k < DL; ++k) r[k] = r0[k];
-        } else {
-            const auto ka = kargs();
-            const double* const rin = ka->r;
-            const bool rpm = ka->r_pm != 0;
-#pragma unroll
-            for (int k = 0; k < DL; ++k) r[k] = (FULL || cv[k]) ? (rpm ? rin[p * D + lane + 64 * k] : rin[cidx[k] + p]) : 0.0;
-        }
+        for (int k = 0; k < DL; ++k) r[k] = r0[k];
 #pragma unroll
         for (int k = 0; k < DL; ++k) x[k] = x0[k];
         if (sel != 0) {

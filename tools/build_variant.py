@@ -1,5 +1,7 @@
-"""Diagnostic / A-B builds of the library (same ABI), kept out of the product .so:
+"""Diagnostic builds of the library (same ABI), kept out of the product .so:
     python tools/build_variant.py <tag> [-DNAME ...]   ->  smcnuts_amd/variants/libsmcnuts_<tag>.so
+The defines are the diagnostic switches of the sources: -DSMCN_PROFILE (and -DSMCN_PROFILE_TAIL=n), the in-kernel
+section profile tools/prof_sections*.py read; -DSMCN_TRACE_SETUP, where a context's set-up time goes.
 Load one with SMCN_LIB=<path>."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -7,11 +7,13 @@ rocprofv3 --kernel-trace --pmc SQ_LEVEL_WAVES SQ_CYCLES SQ_BUSY_CYCLES SQ_WAVES 
 python3 - <<'PY'
 import csv, collections
 rows=list(csv.DictReader(open('gpurun_out/pmc_occ/occ_counter_collection.csv')))
-acc=collections.defaultdict(list)
+acc=collections.defaultdict(lambda: collections.defaultdict(list))
+res={}
 for r in rows:
-    if 'nuts2_kernel' in r['Kernel_Name']:
-        acc[r['Counter_Name']].append(float(r['Counter_Value']))
-        lds=r.get('LDS_Block_Size'); vg=r.get('VGPR_Count'); ag=r.get('Accum_VGPR_Count'); sg=r.get('SGPR_Count'); grid=r.get('Grid_Size'); wg=r.get('Workgroup_Size')
-for k,v in acc.items(): print(k, sum(v[-4:])/4)
-print('LDS',lds,'VGPR',vg,'AGPR',ag,'SGPR',sg,'grid',grid,'wg',wg)
+    k=r['Kernel_Name'].split('(')[0][-70:]
+    acc[k][r['Counter_Name']].append(float(r['Counter_Value']))
+    res[k]=(r.get('LDS_Block_Size'), r.get('VGPR_Count'), r.get('Accum_VGPR_Count'), r.get('SGPR_Count'), r.get('Grid_Size'), r.get('Workgroup_Size'))
+for k,d in acc.items():
+    for cn,v in d.items(): print(f"{k:42s} {cn:16s}", sum(v[-4:])/len(v[-4:]))
+    print(k, 'LDS %s VGPR %s AGPR %s SGPR %s grid %s wg %s' % res[k])
 PY

@@ -17,6 +17,6 @@ for f in sorted(glob.glob('gpurun_out/pmc_traffic/*_counter_collection.csv')):
         k=r['Kernel_Name'].split('(')[0][-70:]
         acc[k][r['Counter_Name']].append(float(r['Counter_Value']))
     for k,d in acc.items():
-        if 'nuts2_kernel' in k or 'prep' in k or 'post' in k:
+        if 'prep' in k or 'post' in k:
             for cn,v in d.items(): print(f"{k:42s} {cn:20s} mean_last4={sum(v[-4:])/4:.4e}")
 PY

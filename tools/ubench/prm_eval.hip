@@ -76,7 +76,6 @@ int main(int argc, char** argv) {
     };
     all(PrmwcdDistModel<8, 100, 11, 2, 4>{}, "product <8,100,11,RED=2>");
     all(PrmwcdDistModel<8, 100, 11, 2, 4, true>{}, "RED=2, FAST observation loop");
-    all(PrmwcdDistModel<8, 100, 11, 0, 4>{}, "RED=0 (LDS scratch)");
 #ifdef PRM_EVAL_VARIANTS
     PRM_EVAL_VARIANTS
 #endif
