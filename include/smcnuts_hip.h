@@ -34,6 +34,7 @@ typedef struct smcn_ctx smcn_ctx;
 #define SMCN_MODEL_ARMA 1   /* data = [T, y_1..y_T]                 stan_models/arma/arma.stan   */
 #define SMCN_MODEL_PRMWCD 2 /* data = [N, M, Clength, q, y.., Xkernel..]  stan_models/PRMwCD/PRMwCD.stan */
 #define SMCN_MODEL_HOST 3   /* data = [D]: the density is the caller's (smcn_set_host_target)              */
+#define SMCN_MODEL_GLM 4    /* data = [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], D = p + intercept <= 64 */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

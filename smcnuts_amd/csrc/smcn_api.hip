@@ -411,8 +411,41 @@ static int with_model(smcn_ctx* c, F&& f) {
         FAIL(c, "PRMwCD target: the device functor holds up to N=100 observations and Clength=11 columns (M = Clength + 1); "
                 "larger data: pass the model object as a host-evaluated target");
     }
+    if (c->model == SMCN_MODEL_GLM) {
+        // (smcn_ctx_create has checked the data and refused D > 64)
+        if (c->D <= 16) return f(GlmModel<8, 2>{});
+        return f(GlmModel<64, 1>{});
+    }
     if (c->model == SMCN_MODEL_HOST) FAIL(c, "host target: this entry point needs a device-native model");
     FAIL(c, "model not available in this build");
+}
+
+// SMCN_MODEL_GLM: checks the caller's data block; "" and D, or what is wrong with it
+static std::string glm_check(const double* md, int64_t len, int* D_out) {
+    const char* layout = "GLM target: data = [family, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)]";
+    if (len < 4) return layout;
+    const double fam = md[0], nd = md[1], pd = md[2], icd = md[3];
+    if (!(fam == 0.0 || fam == 1.0)) return "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log)";
+    if (!(icd == 0.0 || icd == 1.0)) return "GLM target: intercept must be 0 or 1";
+    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd)) return "GLM target: n must be an integer >= 1";
+    if (!(pd >= 0.0 && pd <= 1048576.0 && pd == (double)(int64_t)pd)) return "GLM target: p must be an integer >= 0";
+    const int64_t n = (int64_t)nd, p = (int64_t)pd, D = p + (int64_t)icd;
+    if (D < 1) return "GLM target: no coefficients (p = 0 without an intercept)";
+    if (D > 64)
+        return "GLM target: the device functor covers D <= 64 coefficients; larger models run host-evaluated "
+               "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)";
+    if (len != 4 + D + n + n * p) return layout;
+    for (int64_t c = 0; c < D; ++c)
+        if (!(md[4 + c] > 0.0 && std::isfinite(md[4 + c]))) return "GLM target: prior sds must be finite and > 0";
+    for (int64_t i = 0; i < n; ++i) {
+        const double y = md[4 + D + i];
+        const bool ok = fam == 0.0 ? (y == 0.0 || y == 1.0) : (y >= 0.0 && y <= 9007199254740992.0 && y == std::floor(y));
+        if (!ok) return fam == 0.0 ? "GLM target: bernoulli_logit needs y in {0, 1}" : "GLM target: poisson_log needs y in {0, 1, 2, ..}";
+    }
+    for (int64_t t = 0; t < n * p; ++t)
+        if (!std::isfinite(md[4 + D + n + t])) return "GLM target: X must be finite";
+    *D_out = (int)D;
+    return "";
 }
 
 extern "C" {
@@ -507,6 +540,15 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
         case SMCN_MODEL_ARMA: c->D = 4; break;
         case SMCN_MODEL_PRMWCD: c->D = (int)model_data[1] + 1; break;
         case SMCN_MODEL_HOST: c->D = (int)model_data[0]; break;
+        case SMCN_MODEL_GLM: {
+            const std::string why = glm_check(model_data, model_data_len, &c->D);
+            if (!why.empty()) {
+                g_create_error = "smcn_ctx_create: " + why;
+                delete c;
+                return -1;
+            }
+            break;
+        }
         default:
             g_create_error = "smcn_ctx_create: unknown model id";
             delete c;
@@ -544,6 +586,24 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             for (int i = 0; i < nobs + 2; ++i)
                 for (int j = 0; j < RS; ++j)
                     mup.push_back(i < nobs ? (j < C ? model_data[4 + nobs + (size_t)i * C + j] : (j == RS - 1 ? model_data[4 + i] : 0.0)) : 0.0);
+        }
+    }
+    // GLM: behind the caller's data the table GlmModel reads (smcn_models.hpp) -- a row per observation,
+    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1)], at a 128-byte boundary, zero rows up to a
+    // multiple of 64 observations
+    if (model_id == SMCN_MODEL_GLM) {
+        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3], D = c->D;
+        const int RS = glm_row_doubles((int)D);
+        const int64_t t0 = glm_table_offset(D, n, p), rows = glm_table_rows(n);
+        mup.assign(t0 + rows * RS, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            if (ic) row[0] = 1.0;
+            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + D + n + i * p + j];
+            const double y = model_data[4 + D + i];
+            row[RS - 2] = y;
+            row[RS - 1] = std::lgamma(y + 1.0);
         }
     }
     const int64_t mlen = (int64_t)mup.size();

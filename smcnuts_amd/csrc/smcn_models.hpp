@@ -399,5 +399,166 @@ struct PrmwcdDistModel {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Canonical-link GLM (SMCN_MODEL_GLM): Bernoulli-logit or Poisson-log likelihood of a linear predictor
+// eta = X beta (+ intercept), independent Gaussian priors N(0, s_c^2) on the D <= 64 coefficients.
+// The density works on the table smcn_ctx_create repacks behind the caller's data (glm_table_offset): a row per
+// observation, [1 (intercept only), X_i1 .. X_ip, 0 (to an even column count DP), y_i, lgamma(y_i + 1)], RS = DP + 2
+// doubles, at a 128-byte boundary, zero rows up to a multiple of 64 -- every lane reads whole rows, unmasked, with
+// 16-byte loads.  The design stays in global memory (L2 / Infinity Cache): the G lanes of every particle group of a
+// wavefront read the same rows in the same instructions (nuts_kernel's lock step), so a row is fetched once per
+// wavefront.  The family is a wave-uniform runtime branch.
+//   G = 8 (D <= 16): coordinate c on lane c % 8; every lane gathers the D coefficients, lane lg evaluates observations
+//                    lg, lg + 8, .. and the D gradient partials are reduce-scattered over the group.
+//   G = 64 (D <= 64): one particle per wavefront, coordinate c on lane c.  Observations go in chunks of 64, one per lane:
+//                    eta with the coefficients read out as scalars (v_readlane), then the chunk's 64 residuals read out
+//                    the same way and lane c accumulates column c of the chunk's rows -- the column sums come out on the
+//                    lane that owns the coordinate, with no butterfly at all.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline int64_t glm_table_offset(int64_t D, int64_t n, int64_t p) {
+    return (4 + D + n + n * p + 15) / 16 * 16;
+}
+__host__ __device__ inline int glm_row_doubles(int D) { return ((D + 1) & ~1) + 2; }
+__host__ __device__ inline int64_t glm_table_rows(int64_t n) { return (n + 63) / 64 * 64; }
+
+template <int G_, int DL_>
+struct GlmModel {
+    static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
+    static constexpr bool DIST = true;
+    static constexpr int DMAX = G_ * DL_;
+    static_assert(G_ == 64 ? DL_ == 1 : (DMAX % 2) == 0, "GlmModel: 64 lanes with one coordinate each, or an even capacity");
+    using d2 = double __attribute__((ext_vector_type(2)));
+    int lg, D, DP, RS, n;
+    bool poisson;
+    const double* T;      // the repacked table
+    double inv_s2[DL], lc[DL];   // 1 / s_c^2 and -log s_c - log(2 pi) / 2 of the lane's coordinates (0 beyond D)
+
+    __device__ int dim() const { return D; }
+    __device__ void init(const double* md, int lg_, double*) {
+        lg = lg_;
+        poisson = md[0] != 0.0;
+        n = (int)md[1];
+        const int p = (int)md[2];
+        D = p + (int)md[3];
+        DP = (D + 1) & ~1;
+        RS = glm_row_doubles(D);
+        T = md + glm_table_offset(D, n, p);
+#pragma unroll
+        for (int i = 0; i < DL; ++i) {
+            const int c = lg + G * i;
+            const double s = c < D ? md[4 + c] : 1.0;
+            inv_s2[i] = c < D ? 1.0 / (s * s) : 0.0;
+            lc[i] = c < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
+        }
+    }
+    // one observation: log-likelihood term and residual y - E[y | eta]
+    __device__ __forceinline__ void obs(double eta, double y, double lgy, double& term, double& d) const {
+        if (poisson) {
+            const double mu = exp_fast(eta);
+            term = ((y == 0.0 ? 0.0 : y * eta) - mu) - lgy;
+            term = mu < kInf ? term : -kInf;             // poisson_log_lpmf: exp(eta) overflows
+            d = y - mu;
+        } else {
+            // y eta - softplus(eta), softplus(eta) = max(eta, 0) + log1p(e^-|eta|); y eta - max(eta, 0) is min(eta, 0) for
+            // y = 1 and -max(eta, 0) for y = 0, without the cancellation
+            const double t = exp_fast(-fabs(eta));
+            double inv;
+            const double l1 = log1p_pos(t, inv);          // inv = 1 / (1 + e^-|eta|) = sigmoid(|eta|)
+            term = (y != 0.0 ? fmin(eta, 0.0) : -fmax(eta, 0.0)) - l1;
+            d = y - (eta >= 0.0 ? inv : t * inv);
+        }
+    }
+    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
+        double ll = 0.0, lp = 0.0;
+#pragma unroll
+        for (int i = 0; i < DL; ++i) {
+            gp[i] = -x[i] * inv_s2[i];
+            lp += fma(-0.5 * x[i], x[i] * inv_s2[i], lc[i]);
+        }
+        if constexpr (G_ == 64) {
+            // (four accumulators for the column sums and two for eta: one wavefront per SIMD is all the tree stack in LDS
+            //  leaves room for, so dependent FMA chains are not hidden behind other wavefronts)
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            const int col = lg < DP ? lg : 0;
+            for (int k0 = 0; k0 < n; k0 += 64) {
+                const double* const rowp = T + (int64_t)(k0 + lg) * RS;
+                const d2* const row = (const d2*)rowp;
+                double e0 = 0.0, e1 = 0.0;
+                for (int j = 0; j < DP; j += 2) {          // (j wave-uniform: the coefficients are scalar operands)
+                    const d2 v = row[j >> 1];
+                    e0 = fma(group_read<64>(x[0], j), v.x, e0);
+                    e1 = fma(group_read<64>(x[0], j + 1), v.y, e1);
+                }
+                const double e = e0 + e1;
+                const d2 yl = row[DP >> 1];
+                double term, d;
+                obs(e, yl.x, yl.y, term, d);
+                const bool live = k0 + lg < n;
+                ll += live ? term : 0.0;
+                d = live ? d : 0.0;
+                // column `lg` of the chunk's 64 rows, weighted by their residuals (read out as scalars)
+                const double* const colp = T + (int64_t)k0 * RS + col;
+#pragma unroll 16
+                for (int i = 0; i < 64; ++i) acc[i & 3] = fma(lane_value(d, i), colp[(int64_t)i * RS], acc[i & 3]);
+            }
+            gl[0] = lg < D ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.0;
+            double L, P, u0, u1;
+            wave_sum4(ll, lp, 0.0, 0.0, L, P, u0, u1);
+            llik = L;
+            lpri = P;
+        } else {
+            // ---- 1. the D coefficients to every lane of the group
+            double b[DMAX];
+#pragma unroll
+            for (int j = 0; j < DMAX; ++j) b[j] = group_read<G>(x[j / G], j % G);
+            // ---- 2. this lane's observations lg, lg + G, ..
+            double acc[DMAX];
+#pragma unroll
+            for (int j = 0; j < DMAX; ++j) acc[j] = 0.0;
+            const int S = (n + G - 1) / G;
+#pragma unroll 1
+            for (int k = 0; k < S; ++k) {
+                const int i = lg + G * k;
+                const d2* const row = (const d2*)(T + (int64_t)i * RS);
+                double e = 0.0;
+#pragma unroll
+                for (int j2 = 0; j2 < DMAX / 2; ++j2) {
+                    if (2 * j2 < DP) {                    // (DP wave-uniform)
+                        const d2 v = row[j2];
+                        e = fma(b[2 * j2], v.x, e);
+                        e = fma(b[2 * j2 + 1], v.y, e);
+                    }
+                }
+                const d2 yl = row[DP >> 1];
+                double term, d;
+                obs(e, yl.x, yl.y, term, d);
+                const bool live = i < n;
+                ll += live ? term : 0.0;
+                d = live ? d : 0.0;
+                // (the row again, from the cache: holding it across the residual costs 2 DMAX registers)
+#pragma unroll
+                for (int j2 = 0; j2 < DMAX / 2; ++j2) {
+                    if (2 * j2 < DP) {
+                        const d2 v = row[j2];
+                        acc[2 * j2] = fma(d, v.x, acc[2 * j2]);
+                        acc[2 * j2 + 1] = fma(d, v.y, acc[2 * j2 + 1]);
+                    }
+                }
+            }
+            // ---- 3. reduce-scatter of the gradient partials: lane c % G ends with the sum of column c
+#pragma unroll
+            for (int j = 0; j < DMAX; ++j) acc[j] = j < DP ? group_sum<G>(acc[j]) : 0.0;
+#pragma unroll
+            for (int i = 0; i < DL; ++i) {
+                double v = 0.0;
+#pragma unroll
+                for (int j = i * G; j < (i + 1) * G; ++j) v = (j - i * G == lg) ? acc[j] : v;
+                gl[i] = (lg + G * i) < D ? v : 0.0;
+            }
+            llik = group_sum<G>(ll);
+            lpri = group_sum<G>(lp);
+        }
+    }
+};
 
 }  // namespace smcn

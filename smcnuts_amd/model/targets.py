@@ -204,6 +204,71 @@ class PRMwCDModel(DeviceTarget):
         self.two_phase_default = (9, True, 8) if (96 < int(d["N"]) <= 100 and int(d["Clength"]) == 11 and float(d["q"]) == 0.5) else None
 
 
+GLM_FAMILIES = ("bernoulli_logit", "poisson_log")
+GLM_MAX_DIM = 64
+
+
+class GLMTarget(DeviceTarget):
+    """Canonical-link GLM on the device: y_i ~ bernoulli_logit(eta_i) or poisson_log(eta_i), eta = [b_0 +] X b,
+    independent N(0, prior_sd_c^2) priors on the D = p + intercept coefficients (the intercept is coordinate 0).
+    Coordinates are unconstrained; log pi_phi = lpri + phi * llik.  D <= 64 (larger models: HostTarget).
+
+    Data block (include/smcnuts_hip.h, SMCN_MODEL_GLM):
+    [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)]."""
+    model_id = _capi.MODEL_GLM
+
+    def __init__(self, X, y, family="bernoulli_logit", prior_sd=2.5, intercept=True):
+        if family not in GLM_FAMILIES:
+            raise ValueError(f"GLMTarget: family must be one of {GLM_FAMILIES}, not {family!r}")
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2:
+            raise ValueError("GLMTarget: X must be an (n, p) matrix")
+        n, p = X.shape
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim != 1 or y.shape[0] != n:
+            raise ValueError(f"GLMTarget: y must be a vector of the n = {n} observations X has rows for")
+        if n < 1:
+            raise ValueError("GLMTarget: at least one observation")
+        ic = 1 if intercept else 0
+        D = p + ic
+        if D < 1:
+            raise ValueError("GLMTarget: no coefficients (p = 0 without an intercept)")
+        if D > GLM_MAX_DIM:
+            raise ValueError(f"GLMTarget: D = {D} coefficients; the device functor covers D <= {GLM_MAX_DIM}. "
+                             "Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
+        if not np.all(np.isfinite(X)):
+            raise ValueError("GLMTarget: X must be finite")
+        if family == "bernoulli_logit":
+            if not np.all((y == 0.0) | (y == 1.0)):
+                raise ValueError("GLMTarget: bernoulli_logit needs y in {0, 1}")
+        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
+            raise ValueError("GLMTarget: poisson_log needs y in {0, 1, 2, ...}")
+        s = np.asarray(prior_sd, dtype=np.float64)
+        if s.ndim == 0:
+            s = np.full(D, float(s))
+        if s.shape != (D,):
+            raise ValueError(f"GLMTarget: prior_sd must be a scalar or one value per coefficient (D = {D})")
+        if not np.all(np.isfinite(s) & (s > 0.0)):
+            raise ValueError("GLMTarget: prior_sd must be finite and > 0")
+        self.family, self.intercept = family, bool(intercept)
+        self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
+        data = np.concatenate([[float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic)], s, y, X.reshape(-1)])
+        names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)]
+        super().__init__(data, D, names)
+
+
+def LogisticRegression(X, y, prior_sd=2.5, intercept=True):
+    """Bayesian logistic regression: GLMTarget(X, y, family="bernoulli_logit", ...)."""
+    return GLMTarget(X, y, family="bernoulli_logit", prior_sd=prior_sd, intercept=intercept)
+
+
+def PoissonRegression(X, y, prior_sd=2.5, intercept=True):
+    """Bayesian Poisson regression with a log link: GLMTarget(X, y, family="poisson_log", ...)."""
+    return GLMTarget(X, y, family="poisson_log", prior_sd=prior_sd, intercept=intercept)
+
+
 def StanModel(model_name, model_path=None, data_path=None):
     """Same call shape as the reference's StanModel(model_name, model_path,
     data_path) (bridgestan.py:13); resolves the model NAME to its device

@@ -1,0 +1,91 @@
+"""GLM target (GLMTarget, SMCN_MODEL_GLM) throughput on one MI355X: one JSON line per case.
+
+    python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096]
+
+GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
+(1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)} and poisson_log at (1 000, 25); synthetic data from fixed seeds.  The step size of each case
+is the largest of a halving ladder whose pilot NUTS launch averages >= 8 leapfrogs per tree (trees of 2^3-2^4).
+Per case: leapfrog/s and mean leapfrogs per tree of a K-generation SMCSampler run (forward L-kernel, device-resident
+loop), milliseconds per NUTS launch (smcn_timers), and the fp64 rate counted as 4 n D flop per leapfrog (eta and the
+gradient: two multiply-adds per design entry) against the 78.6 TF peak bench.py uses.  The (1 000, 25) logistic case is
+also run at --host-N particles both device-native and through HostTarget with the numpy density of tests/_glm.py.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+PEAK_FP64 = 78.6e12
+
+# (the two D = 16 / 17 cases sit on either side of the boundary between the functor's two shapes)
+CASES = [("bernoulli_logit", 100, 8), ("bernoulli_logit", 1000, 25), ("bernoulli_logit", 10000, 64),
+         ("poisson_log", 1000, 25), ("bernoulli_logit", 1000, 16), ("bernoulli_logit", 1000, 17)]
+
+
+def pick_step(target, N, seed):
+    from smcnuts_amd import _capi
+    ctx = _capi.Context(N, target.model_id, target.model_data)
+    ctx.set_seed(seed)
+    ctx.call("smcn_init_particles_std_normal", 1.0)
+    x0, _, _ = ctx.get_state()
+    eps = 0.4
+    for _ in range(10):
+        ctx.set_state(x=x0)                                   # generation 0's particles
+        ctx.propose_nuts(eps, 1.0, 0)
+        m = float(ctx.tree_stats()["nleap"].mean())
+        if m >= 8.0:
+            break
+        eps *= 0.5
+    ctx.close()
+    return eps, m
+
+
+def run(target, N, K, eps, seed):
+    from smcnuts_amd import SMCSampler
+    smc = SMCSampler(K=K, N=N, target=target, step_size=eps, seed=seed)
+    ctx = smc.samples.ctx
+    ctx.timers(reset=True)
+    smc.sample(show_progress=False)
+    ms, launches = ctx.timers()[:2]
+    leaps = int(smc.leapfrogs.sum())
+    return dict(run_s=smc.run_time, leapfrogs=leaps, leapfrog_per_s=leaps / smc.run_time,
+                nleap_mean=leaps / (N * K), nuts_ms_per_launch=(ms / launches) if launches else None,
+                launches=int(launches), device_resident=bool(smc.device_resident))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--K", type=int, default=10)
+    ap.add_argument("--N", type=int, default=65536)
+    ap.add_argument("--host-N", type=int, default=4096)
+    ap.add_argument("--host-K", type=int, default=3)
+    a = ap.parse_args()
+    import _glm
+    from smcnuts_amd import GLMTarget
+    for family, n, D in CASES:
+        X, y = _glm.synthetic(family, n, D - 1, 1000 + D, scale=0.5)
+        t = GLMTarget(X, y, family=family, prior_sd=2.0)
+        eps, pilot = pick_step(t, a.N, 5)
+        run(t, a.N, 2, eps, 6)                                   # warm-up: code objects, allocations
+        r = run(t, a.N, a.K, eps, 7)
+        r.update(case=f"{family}_n{n}_D{D}", family=family, n=n, D=D, N=a.N, K=a.K, step_size=eps, pilot_nleap=pilot,
+                 fp64_tflops=4.0 * n * D * r["leapfrog_per_s"] / 1e12)
+        r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
+        print(json.dumps(r), flush=True)
+        if (family, n, D) == ("bernoulli_logit", 1000, 25):
+            dev = run(t, a.host_N, a.host_K, eps, 8)
+            host = run(_glm.GLMNumpy(X, y, family, 2.0), a.host_N, a.host_K, eps, 8)
+            print(json.dumps(dict(case=f"{family}_n{n}_D{D}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
+                                  device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
+                                  speedup=host["run_s"] / dev["run_s"])), flush=True)
+
+
+if __name__ == "__main__":
+    main()
