@@ -34,7 +34,10 @@ typedef struct smcn_ctx smcn_ctx;
 #define SMCN_MODEL_ARMA 1   /* data = [T, y_1..y_T]                 stan_models/arma/arma.stan   */
 #define SMCN_MODEL_PRMWCD 2 /* data = [N, M, Clength, q, y.., Xkernel..]  stan_models/PRMwCD/PRMwCD.stan */
 #define SMCN_MODEL_HOST 3   /* data = [D]: the density is the caller's (smcn_set_host_target)              */
-#define SMCN_MODEL_GLM 4    /* data = [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], D = p + intercept <= 64 */
+#define SMCN_MODEL_GLM 4    /* data = [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], D = p + intercept <= 64;
+                              family 2 (normal, sigma = e^tau) or 3 (neg_binomial_2_log, phi = e^tau): [family, n, p, intercept,
+                              s_1..s_Dc, m_tau, s_tau, y_1..y_n, X], Dc = p + intercept, x = (b_1..b_Dc, tau), D = Dc + 1 <= 64,
+                              tau ~ N(m_tau, s_tau^2); constrain reports e^tau */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

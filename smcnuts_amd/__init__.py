@@ -9,4 +9,5 @@ on this path and no CPU fallback.
 """
 from .smc_sampler import SMCSampler  # noqa: F401
 from .model.targets import (ArmaModel, GaussianTarget, GLMTarget, HostTarget, IsoGaussian,  # noqa: F401
-                            LogisticRegression, PoissonRegression, PRMwCDModel, StanModel)
+                            LinearRegression, LogisticRegression, NegativeBinomialRegression, PoissonRegression,
+                            PRMwCDModel, StanModel)

@@ -62,6 +62,7 @@ struct smcn_ctx {
     int device = 0;
     int64_t N = 0, base = 0;
     int model = 0, D = 0, Dc = 0;
+    int cmodel = 0;   // the model id the constrained-space kernels get (constrain_coord: ids 1 and 2 exp the last coordinate)
     int num_cu = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -413,6 +414,11 @@ static int with_model(smcn_ctx* c, F&& f) {
     }
     if (c->model == SMCN_MODEL_GLM) {
         // (smcn_ctx_create has checked the data and refused D > 64)
+        if (c->mdata_h[0] >= 2.0) {                       // normal / neg_binomial_2_log: D counts tau
+            // (G = 8 up to D = 8 only: GlmDispModel<8, 2>'s NUTS kernel needs 256 VGPRs + 152 B of scratch)
+            if (c->D <= 8) return f(GlmDispModel<8, 1>{});
+            return f(GlmDispModel<64, 1>{});
+        }
         if (c->D <= 16) return f(GlmModel<8, 2>{});
         return f(GlmModel<64, 1>{});
     }
@@ -420,30 +426,53 @@ static int with_model(smcn_ctx* c, F&& f) {
     FAIL(c, "model not available in this build");
 }
 
-// SMCN_MODEL_GLM: checks the caller's data block; "" and D, or what is wrong with it
+// SMCN_MODEL_GLM: checks the caller's data block; "" and D (tau included), or what is wrong with it
 static std::string glm_check(const double* md, int64_t len, int* D_out) {
     const char* layout = "GLM target: data = [family, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)]";
+    const char* layout_disp = "GLM target: data = [family, n, p, intercept, s_1..s_Dc, m_tau, s_tau, y_1..y_n, "
+                              "X (n x p, row-major)] for families 2 (normal) and 3 (neg_binomial_2_log)";
     if (len < 4) return layout;
     const double fam = md[0], nd = md[1], pd = md[2], icd = md[3];
-    if (!(fam == 0.0 || fam == 1.0)) return "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log)";
+    if (!(fam == 0.0 || fam == 1.0 || fam == 2.0 || fam == 3.0))
+        return "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log), or 2 (normal) or 3 (neg_binomial_2_log) "
+               "with a dispersion prior";
+    const bool disp = fam >= 2.0;
     if (!(icd == 0.0 || icd == 1.0)) return "GLM target: intercept must be 0 or 1";
     if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd)) return "GLM target: n must be an integer >= 1";
     if (!(pd >= 0.0 && pd <= 1048576.0 && pd == (double)(int64_t)pd)) return "GLM target: p must be an integer >= 0";
-    const int64_t n = (int64_t)nd, p = (int64_t)pd, D = p + (int64_t)icd;
-    if (D < 1) return "GLM target: no coefficients (p = 0 without an intercept)";
+    const int64_t n = (int64_t)nd, p = (int64_t)pd, Dc = p + (int64_t)icd, D = Dc + (disp ? 1 : 0);
+    if (Dc < 1) return "GLM target: no coefficients (p = 0 without an intercept)";
     if (D > 64)
         return "GLM target: the device functor covers D <= 64 coefficients; larger models run host-evaluated "
                "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)";
-    if (len != 4 + D + n + n * p) return layout;
-    for (int64_t c = 0; c < D; ++c)
+    const int64_t y0 = 4 + Dc + (disp ? 2 : 0);        // where y starts
+    if (len != y0 + n + n * p) {
+        // a block laid out for families 0 / 1 but naming a dispersion family
+        if (disp && len == 4 + Dc + n + n * p)
+            return "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log) for a block without m_tau, s_tau; "
+                   "families 2 (normal) and 3 (neg_binomial_2_log) take data = [family, n, p, intercept, s_1..s_Dc, "
+                   "m_tau, s_tau, y_1..y_n, X]";
+        return disp ? layout_disp : layout;
+    }
+    for (int64_t c = 0; c < Dc; ++c)
         if (!(md[4 + c] > 0.0 && std::isfinite(md[4 + c]))) return "GLM target: prior sds must be finite and > 0";
+    if (disp) {
+        if (!std::isfinite(md[4 + Dc])) return "GLM target: m_tau must be finite";
+        if (!(md[5 + Dc] > 0.0 && std::isfinite(md[5 + Dc]))) return "GLM target: s_tau must be finite and > 0";
+    }
     for (int64_t i = 0; i < n; ++i) {
-        const double y = md[4 + D + i];
-        const bool ok = fam == 0.0 ? (y == 0.0 || y == 1.0) : (y >= 0.0 && y <= 9007199254740992.0 && y == std::floor(y));
-        if (!ok) return fam == 0.0 ? "GLM target: bernoulli_logit needs y in {0, 1}" : "GLM target: poisson_log needs y in {0, 1, 2, ..}";
+        const double y = md[y0 + i];
+        if (fam == 0.0) {
+            if (!(y == 0.0 || y == 1.0)) return "GLM target: bernoulli_logit needs y in {0, 1}";
+        } else if (fam == 2.0) {
+            if (!std::isfinite(y)) return "GLM target: normal needs finite y";
+        } else if (!(y >= 0.0 && y <= 9007199254740992.0 && y == std::floor(y))) {
+            return fam == 1.0 ? "GLM target: poisson_log needs y in {0, 1, 2, ..}"
+                              : "GLM target: neg_binomial_2_log needs y in {0, 1, 2, .., 2^53}";
+        }
     }
     for (int64_t t = 0; t < n * p; ++t)
-        if (!std::isfinite(md[4 + D + n + t])) return "GLM target: X must be finite";
+        if (!std::isfinite(md[y0 + n + t])) return "GLM target: X must be finite";
     *D_out = (int)D;
     return "";
 }
@@ -555,6 +584,9 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             return -1;
     }
     c->Dc = c->D;
+    // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
+    // constrain_coord applies to arma's log sigma (the other models keep their own id)
+    c->cmodel = (model_id == SMCN_MODEL_GLM && model_data[0] >= 2.0) ? SMCN_MODEL_ARMA : model_id;
     auto fail = [&](const char* what, hipError_t er) {
         g_create_error = std::string("smcn_ctx_create: ") + what + ": " + hipGetErrorString(er);
         free_all(c);
@@ -588,22 +620,24 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
                     mup.push_back(i < nobs ? (j < C ? model_data[4 + nobs + (size_t)i * C + j] : (j == RS - 1 ? model_data[4 + i] : 0.0)) : 0.0);
         }
     }
-    // GLM: behind the caller's data the table GlmModel reads (smcn_models.hpp) -- a row per observation,
+    // GLM: behind the caller's data the table GlmModel / GlmDispModel read (smcn_models.hpp) -- a row per observation,
     // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1)], at a 128-byte boundary, zero rows up to a
-    // multiple of 64 observations
+    // multiple of 64 observations.  The row width follows the Dc coefficients; the dispersion families' block has m_tau
+    // and s_tau between the prior sds and y (HD: the doubles before y).
     if (model_id == SMCN_MODEL_GLM) {
-        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3], D = c->D;
-        const int RS = glm_row_doubles((int)D);
-        const int64_t t0 = glm_table_offset(D, n, p), rows = glm_table_rows(n);
+        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
+        const int64_t Dc = p + ic, HD = model_data[0] >= 2.0 ? Dc + 2 : Dc;
+        const int RS = glm_row_doubles((int)Dc);
+        const int64_t t0 = glm_table_offset(HD, n, p), rows = glm_table_rows(n);
         mup.assign(t0 + rows * RS, 0.0);
         std::copy(model_data, model_data + model_data_len, mup.begin());
         for (int64_t i = 0; i < n; ++i) {
             double* row = mup.data() + t0 + i * RS;
             if (ic) row[0] = 1.0;
-            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + D + n + i * p + j];
-            const double y = model_data[4 + D + i];
+            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + HD + n + i * p + j];
+            const double y = model_data[4 + HD + i];
             row[RS - 2] = y;
-            row[RS - 1] = std::lgamma(y + 1.0);
+            row[RS - 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
         }
     }
     const int64_t mlen = (int64_t)mup.size();
@@ -938,7 +972,7 @@ int smcn_target_constrain(smcn_ctx* c, const double* x, int64_t M, double* out) 
     if (rc) return rc;
     if ((rc = ensure_stage2(c, n))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->model);
+    constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->cmodel);
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(out, c->stage2, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
@@ -1176,7 +1210,7 @@ int smcn_moment_sums(smcn_ctx* c, const double* mean, double* sums) {
         dmean = c->scal + 16;
         HIPC(c, hipMemcpyAsync(dmean, mean, sizeof(double) * c->Dc, hipMemcpyHostToDevice, c->stream));
     }
-    moment_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(c->x, c->wn, c->N, c->D, c->model, dmean, c->part);
+    moment_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(c->x, c->wn, c->N, c->D, c->cmodel, dmean, c->part);
     sum_final_kernel<<<final_grid(c->D), kRedBlock, 0, c->stream>>>(c->part, g, c->D, c->scal + 16 + c->D);
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(sums, c->scal + 16 + c->D, sizeof(double) * c->Dc, hipMemcpyDeviceToHost, c->stream));
@@ -2189,7 +2223,7 @@ static int enqueue_partials(smcn_ctx* c, const double* logw, const double* x, do
     const int NQB = gen_block_nq(c->Dc);   // block partials: [max, cnt, s1, s2, A.., B.., reference point..]
     while ((int64_t)g * NQB * ngen > (int64_t)kMaxPart * (4 * c->D * c->D + 2 * c->D + 8) && g > 1) g /= 2;
     const int nz = c->D >= 64 ? 8 : 1;
-    gen_partials_kernel<<<dim3(g, ngen, nz), kRedBlock, 0, c->stream>>>(logw, x, N, c->D, c->model, c->part, N,
+    gen_partials_kernel<<<dim3(g, ngen, nz), kRedBlock, 0, c->stream>>>(logw, x, N, c->D, c->cmodel, c->part, N,
                                                                         N * c->D, (c->D > 8 && ngen == 1 && nz == 1) ? c->work : nullptr);
     const int qb = c->Dc <= 16 ? 1 : (2 * c->Dc + 7) / 8 > 64 ? 64 : (2 * c->Dc + 7) / 8;
     gen_reduce_blocks_kernel<<<dim3(ngen, qb), kRedBlock, 0, c->stream>>>(c->part, g, c->Dc,

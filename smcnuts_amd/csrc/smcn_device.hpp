@@ -382,6 +382,65 @@ __device__ __forceinline__ void box_muller_lean(double u1, double u2, double& z0
     z1 = rad * sn;
 }
 
+// ---- log-gamma and digamma tails for arguments x >= kGammaAsym ------------------------------------------------
+// lgamma(x) = (x - 1/2) log x - x + log(2 pi) / 2 + stirling_tail(x),   psi(x) = log x - 1 / (2x) - digamma_tail(x);
+// eight terms of each asymptotic series in 1 / x^2 (the first omitted term is below 2e-18 of the result's scale at
+// x = 10).  `ix` = 1 / x.  ROCm has no device digamma: digamma_pos shifts its argument up to >= 10 with
+// psi(x) = psi(x + 1) - 1 / x and then takes the series.
+constexpr double kGammaAsym = 10.0;
+__device__ __forceinline__ double stirling_tail(double ix) {   // sum B_2k / (2k (2k - 1) x^(2k - 1)), k = 1..8
+    const double t = ix * ix;
+    double p = -3617.0 / 122400.0;
+    p = fma(p, t, 1.0 / 156.0);
+    p = fma(p, t, -691.0 / 360360.0);
+    p = fma(p, t, 1.0 / 1188.0);
+    p = fma(p, t, -1.0 / 1680.0);
+    p = fma(p, t, 1.0 / 1260.0);
+    p = fma(p, t, -1.0 / 360.0);
+    p = fma(p, t, 1.0 / 12.0);
+    return p * ix;
+}
+__device__ __forceinline__ double digamma_tail(double ix) {    // sum B_2k / (2k x^2k), k = 1..8
+    const double t = ix * ix;
+    double p = -3617.0 / 8160.0;
+    p = fma(p, t, 1.0 / 12.0);
+    p = fma(p, t, -691.0 / 32760.0);
+    p = fma(p, t, 1.0 / 132.0);
+    p = fma(p, t, -1.0 / 240.0);
+    p = fma(p, t, 1.0 / 252.0);
+    p = fma(p, t, -1.0 / 120.0);
+    p = fma(p, t, 1.0 / 12.0);
+    return p * t;
+}
+// x shifted up to >= kGammaAsym (x > 0 finite, normal: at most 10 steps), with P = x (x + 1) .. and S = 1 / x + 1 / (x + 1) + ..
+// over the steps taken (P = 1, S = 0 for none)
+__device__ __forceinline__ double gamma_shift(double x, double& P, double& S) {
+    P = 1.0;
+    S = 0.0;
+#pragma unroll 1
+    while (x < kGammaAsym) {
+        P *= x;
+        S += 1.0 / x;
+        x += 1.0;
+    }
+    return x;
+}
+// psi(x) for x > 0 (finite, normal)
+__device__ __forceinline__ double digamma_pos(double x) {
+    double P, S;
+    x = gamma_shift(x, P, S);
+    const double ix = 1.0 / x;
+    return ((log(x) - 0.5 * ix) - digamma_tail(ix)) - S;
+}
+// lgamma(x) and psi(x) for x > 0 (finite, normal), from one shift: lgamma(x) = lgamma(x + m) - log P
+__device__ __forceinline__ void lgamma_digamma_pos(double x, double& lg, double& psi) {
+    double P, S;
+    x = gamma_shift(x, P, S);
+    const double ix = 1.0 / x, lx = log(x);
+    lg = (fma(x - 0.5, lx, -x) + (0.5 * kLog2Pi + stirling_tail(ix))) - log(P);
+    psi = ((lx - 0.5 * ix) - digamma_tail(ix)) - S;
+}
+
 // log pi_phi with the target adapter's failure convention (bridgestan.py:45-49)
 __device__ __forceinline__ double combine_lp(double lpri, double llik, double phi) {
     const double lp = lpri + phi * llik;

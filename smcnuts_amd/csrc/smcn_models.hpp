@@ -561,4 +561,237 @@ struct GlmModel {
     }
 };
 
+
+// ---------------------------------------------------------------------------
+// GLM with a dispersion coordinate (SMCN_MODEL_GLM families 2 and 3): x = (b_1..b_Dc, tau), D = Dc + 1, tau last and
+// unconstrained, prior N(m_tau, s_tau^2) on tau (= a lognormal prior on sigma / phi = e^tau with its Jacobian).
+//   2 normal:             y ~ N(eta, sigma^2), sigma = e^tau
+//   3 neg_binomial_2_log: y ~ NB2(mu = e^eta, phi = e^tau) (Stan's parameterisation)
+// The table and both shapes are GlmModel's (row width from Dc; column `aux` = lgamma(y + 1), unused by `normal`); tau
+// is read like any coordinate and its gradient is one more sum over the observations, which lands on the lane that owns
+// coordinate Dc.  A sibling of GlmModel rather than a template switch on it, so that GlmModel's instruction streams and
+// register allocation stay as they are (its G = 8 NUTS kernel is at 246 VGPRs).  Shapes: G = 8 with one coordinate per
+// lane for D <= 8 (the two-coordinate form spills), G = 64 for 9 <= D <= 64.
+// NB accuracy where phi >> y + mu: for phi >= kGammaAsym, lgamma(y + phi) - lgamma(phi) - y tau and psi(y + phi) - psi(phi)
+// are formed from Stirling's series with log1p(y / phi) -- no lgamma(phi)-sized or phi tau-sized intermediate; below,
+// as differences of lgamma / psi, each from a shift up to >= kGammaAsym and the same series (lgamma(phi) and psi(phi)
+// are O(1 + |tau|) there; the device library's lgamma inlined into the observation loop made the kernels spill).
+// Everything that depends on tau alone is
+// formed once per evaluation.  Non-finite: -inf when e^-2tau (normal), e^eta or e^tau (NB) overflows, or e^tau
+// leaves the normal range (NB, tau < -708.39).
+// ---------------------------------------------------------------------------
+constexpr double kLogDblMax = 709.782712893384;        // log(DBL_MAX), rounded down: exp(v) is finite for v <= this
+constexpr double kLogDblMinNormal = -708.3964185322641;   // log(DBL_MIN), rounded up
+
+template <int G_, int DL_>
+struct GlmDispModel {
+    static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
+    static constexpr bool DIST = true;
+    static constexpr int DMAX = G_ * DL_;
+    static_assert(G_ == 64 ? DL_ == 1 : (DMAX % 2) == 0, "GlmDispModel: 64 lanes with one coordinate each, or an even capacity");
+    using d2 = double __attribute__((ext_vector_type(2)));
+    int lg, D, Dc, DP, RS, n;
+    bool nb;
+    const double* T;      // the repacked table
+    double mc[DL], inv_s2[DL], lc[DL];   // prior mean, 1 / s^2 and -log s - log(2 pi) / 2 of the lane's coordinates
+
+    // what one evaluation derives from tau alone (the two families share the registers)
+    struct TauConst {
+        double tau;
+        double phi, iphi;             // normal: e^-2tau, -tau - log(2 pi) / 2;  NB: e^tau, 1 / phi
+        double c1, c2;                // NB: Stirling and digamma tails of phi (big), or lgamma(phi) and psi(phi)
+        bool big, bad;
+    };
+
+    __device__ int dim() const { return D; }
+    __device__ void init(const double* md, int lg_, double*) {
+        lg = lg_;
+        nb = md[0] == 3.0;
+        n = (int)md[1];
+        const int p = (int)md[2];
+        Dc = p + (int)md[3];
+        D = Dc + 1;
+        DP = (Dc + 1) & ~1;
+        RS = glm_row_doubles(Dc);
+        T = md + glm_table_offset(Dc + 2, n, p);
+#pragma unroll
+        for (int i = 0; i < DL; ++i) {
+            const int c = lg + G * i;
+            const double s = c < Dc ? md[4 + c] : (c == Dc ? md[5 + Dc] : 1.0);
+            mc[i] = c == Dc ? md[4 + Dc] : 0.0;
+            inv_s2[i] = c < D ? 1.0 / (s * s) : 0.0;
+            lc[i] = c < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
+        }
+    }
+    __device__ __forceinline__ TauConst tau_const(double tau) const {
+        TauConst k;
+        k.tau = tau;
+        if (!nb) {
+            k.bad = -2.0 * tau > kLogDblMax;
+            k.phi = exp_fast(-2.0 * tau);
+            k.iphi = -tau - 0.5 * kLog2Pi;
+            k.c1 = k.c2 = 0.0;
+            k.big = false;
+        } else {
+            k.bad = !(tau <= kLogDblMax && tau >= kLogDblMinNormal);
+            k.phi = k.bad ? 1.0 : exp_fast(tau);
+            k.iphi = 1.0 / k.phi;
+            k.big = k.phi >= kGammaAsym;
+            if (k.big) {
+                k.c1 = stirling_tail(k.iphi);
+                k.c2 = digamma_tail(k.iphi);
+            } else {
+                lgamma_digamma_pos(k.phi, k.c1, k.c2);
+            }
+        }
+        return k;
+    }
+    // one observation: log-likelihood term, d term / d eta and d term / d tau
+    __device__ __forceinline__ void obs(const TauConst& k, double eta, double y, double lgy, double& term, double& d,
+                                        double& gt) const {
+        if (!nb) {
+            const double r = y - eta;
+            const double rw = r * k.phi;                 // (phi: e^-2tau, iphi: -tau - log(2 pi) / 2)
+            const double q = r * rw;
+            term = fma(-0.5, q, k.iphi);
+            d = rw;
+            gt = q - 1.0;
+        } else {
+            const double x = y + k.phi;
+            // A = lgamma(y + phi) - lgamma(phi) [- y tau when big], B = psi(y + phi) - psi(phi); both 0 at y = 0.  One
+            // pair of asymptotic tails either way: at y + phi (big), or at y + phi shifted up to >= kGammaAsym
+            double P, S;
+            const double xs = k.big ? x : gamma_shift(y == 0.0 ? kGammaAsym : x, P, S);
+            const double ix = 1.0 / xs;
+            const double st = stirling_tail(ix), dt = digamma_tail(ix);
+            double A, B, ts;
+            if (k.big) {
+                double ir;                                   // 1 / (1 + y / phi) = phi / x
+                const double l1 = log1p_pos(y * k.iphi, ir);   // log(x / phi)
+                A = fma(x - 0.5, l1, -y) + (st - k.c1);
+                B = fma(0.5 * y, ix * k.iphi, l1) - (dt - k.c2);
+                ts = 0.0;
+            } else {                                         // (xs >= 10 and P >= 1: log_ge1)
+                const double lx = log_ge1(xs);
+                A = ((fma(xs - 0.5, lx, -xs) + (0.5 * kLog2Pi + st)) - log_ge1(P)) - k.c1;
+                B = (((lx - 0.5 * ix) - dt) - S) - k.c2;
+                ts = k.tau;
+            }
+            A = y == 0.0 ? 0.0 : A;
+            B = y == 0.0 ? 0.0 : B;
+            // softplus(eta - tau) = log(mu + phi) - tau, sigmoid(eta - tau) = mu / (mu + phi) and its complement
+            const double z = eta - k.tau;
+            const double t = exp_fast(-fabs(z));
+            double inv;
+            const double sp = fmax(z, 0.0) + log1p_pos(t, inv);
+            const double ti = t * inv;
+            const double sg = z >= 0.0 ? inv : ti, sc = z >= 0.0 ? ti : inv;
+            term = ((A - lgy) - x * sp) + y * (eta - ts);
+            term = eta <= kLogDblMax ? term : -kInf;           // e^eta overflows
+            d = fma(-x, sg, y);
+            gt = fma(k.phi, (B - sp) + sg, -y * sc);
+        }
+    }
+    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
+        double ll = 0.0, lp = 0.0, gt = 0.0;
+#pragma unroll
+        for (int i = 0; i < DL; ++i) {
+            const double v = x[i] - mc[i];
+            gp[i] = -v * inv_s2[i];
+            lp += fma(-0.5 * v, v * inv_s2[i], lc[i]);
+        }
+        double xt = x[0];
+#pragma unroll
+        for (int i = 1; i < DL; ++i) xt = Dc / G == i ? x[i] : xt;
+        const TauConst k = tau_const(group_read<G>(xt, Dc % G));
+        if constexpr (G_ == 64) {
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            const int col = lg < DP ? lg : 0;
+            const double xb = lg < Dc ? x[0] : 0.0;           // (tau is not a coefficient: 0 on the pad column)
+            for (int k0 = 0; k0 < n; k0 += 64) {
+                const double* const rowp = T + (int64_t)(k0 + lg) * RS;
+                const d2* const row = (const d2*)rowp;
+                double e0 = 0.0, e1 = 0.0;
+                for (int j = 0; j < DP; j += 2) {
+                    const d2 v = row[j >> 1];
+                    e0 = fma(group_read<64>(xb, j), v.x, e0);
+                    e1 = fma(group_read<64>(xb, j + 1), v.y, e1);
+                }
+                const double e = e0 + e1;
+                const d2 yl = row[DP >> 1];
+                double term, d, g;
+                obs(k, e, yl.x, yl.y, term, d, g);
+                const bool live = k0 + lg < n;
+                ll += live ? term : 0.0;
+                gt += live ? g : 0.0;
+                d = live ? d : 0.0;
+                const double* const colp = T + (int64_t)k0 * RS + col;
+#pragma unroll 16
+                for (int i = 0; i < 64; ++i) acc[i & 3] = fma(lane_value(d, i), colp[(int64_t)i * RS], acc[i & 3]);
+            }
+            double L, P, GT, u1;
+            wave_sum4(ll, lp, gt, 0.0, L, P, GT, u1);
+            gl[0] = lg < Dc ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : (lg == Dc ? GT : 0.0);
+            llik = k.bad ? -kInf : L;
+            lpri = P;
+        } else {
+            // ---- 1. the Dc coefficients to every lane of the group (0 in tau's slot and beyond)
+            double b[DMAX];
+#pragma unroll
+            for (int j = 0; j < DMAX; ++j) {
+                const double v = group_read<G>(x[j / G], j % G);
+                b[j] = j < Dc ? v : 0.0;
+            }
+            // ---- 2. this lane's observations lg, lg + G, ..
+            double acc[DMAX];
+#pragma unroll
+            for (int j = 0; j < DMAX; ++j) acc[j] = 0.0;
+            const int S = (n + G - 1) / G;
+#pragma unroll 1
+            for (int kk = 0; kk < S; ++kk) {
+                const int i = lg + G * kk;
+                const d2* const row = (const d2*)(T + (int64_t)i * RS);
+                double e = 0.0;
+#pragma unroll
+                for (int j2 = 0; j2 < DMAX / 2; ++j2) {
+                    if (2 * j2 < DP) {
+                        const d2 v = row[j2];
+                        e = fma(b[2 * j2], v.x, e);
+                        e = fma(b[2 * j2 + 1], v.y, e);
+                    }
+                }
+                const d2 yl = row[DP >> 1];
+                double term, d, g;
+                obs(k, e, yl.x, yl.y, term, d, g);
+                const bool live = i < n;
+                ll += live ? term : 0.0;
+                gt += live ? g : 0.0;
+                d = live ? d : 0.0;
+#pragma unroll
+                for (int j2 = 0; j2 < DMAX / 2; ++j2) {
+                    if (2 * j2 < DP) {
+                        const d2 v = row[j2];
+                        acc[2 * j2] = fma(d, v.x, acc[2 * j2]);
+                        acc[2 * j2 + 1] = fma(d, v.y, acc[2 * j2 + 1]);
+                    }
+                }
+            }
+            // ---- 3. reduce-scatter of the gradient partials; tau's sum to the lane that owns coordinate Dc
+#pragma unroll
+            for (int j = 0; j < DMAX; ++j) acc[j] = j < Dc ? group_sum<G>(acc[j]) : 0.0;
+            const double GT = group_sum<G>(gt);
+#pragma unroll
+            for (int i = 0; i < DL; ++i) {
+                double v = 0.0;
+#pragma unroll
+                for (int j = i * G; j < (i + 1) * G; ++j) v = (j - i * G == lg) ? acc[j] : v;
+                const int c = lg + G * i;
+                gl[i] = c < Dc ? v : (c == Dc ? GT : 0.0);
+            }
+            llik = k.bad ? -kInf : group_sum<G>(ll);
+            lpri = group_sum<G>(lp);
+        }
+    }
+};
+
 }  // namespace smcn

@@ -9,6 +9,7 @@ and the temperature phi is a kernel argument (the reference rewrites the JSON
 data file and reloads the model on every change, bridgestan.py:122-146).
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -204,22 +205,45 @@ class PRMwCDModel(DeviceTarget):
         self.two_phase_default = (9, True, 8) if (96 < int(d["N"]) <= 100 and int(d["Clength"]) == 11 and float(d["q"]) == 0.5) else None
 
 
-GLM_FAMILIES = ("bernoulli_logit", "poisson_log")
+GLM_FAMILIES = ("bernoulli_logit", "poisson_log", "normal", "neg_binomial_2_log")
+GLM_DISPERSION = {"normal": "sigma", "neg_binomial_2_log": "phi"}    # the families with a sampled scale, and its name
 GLM_MAX_DIM = 64
+_NO_PRIOR = object()
 
 
 class GLMTarget(DeviceTarget):
-    """Canonical-link GLM on the device: y_i ~ bernoulli_logit(eta_i) or poisson_log(eta_i), eta = [b_0 +] X b,
-    independent N(0, prior_sd_c^2) priors on the D = p + intercept coefficients (the intercept is coordinate 0).
+    """GLM on the device, eta = [b_0 +] X b, independent N(0, prior_sd_c^2) priors on the Dc = p + intercept
+    coefficients (the intercept is coordinate 0):
+      bernoulli_logit:    y_i ~ bernoulli_logit(eta_i)
+      poisson_log:        y_i ~ poisson_log(eta_i)
+      normal:             y_i ~ normal(eta_i, sigma)
+      neg_binomial_2_log: y_i ~ neg_binomial_2_log(eta_i, phi)   (Stan's parameterisation: mean e^eta, var mu + mu^2 / phi)
+    The two last families sample tau = log sigma / log phi as the last coordinate (D = Dc + 1), with the prior
+    tau ~ N(m, s^2) for dispersion_prior = (m, s) -- sigma / phi ~ lognormal(m, s); `constrain` reports sigma / phi.
     Coordinates are unconstrained; log pi_phi = lpri + phi * llik.  D <= 64 (larger models: HostTarget).
 
     Data block (include/smcnuts_hip.h, SMCN_MODEL_GLM):
-    [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)]."""
+    [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], or
+    [family (2 normal, 3 neg_binomial_2_log), n, p, intercept, s_1..s_Dc, m, s, y_1..y_n, X]."""
     model_id = _capi.MODEL_GLM
 
-    def __init__(self, X, y, family="bernoulli_logit", prior_sd=2.5, intercept=True):
+    def __init__(self, X, y, family="bernoulli_logit", prior_sd=2.5, intercept=True, dispersion_prior=_NO_PRIOR):
         if family not in GLM_FAMILIES:
             raise ValueError(f"GLMTarget: family must be one of {GLM_FAMILIES}, not {family!r}")
+        disp = family in GLM_DISPERSION
+        if not disp and dispersion_prior is not _NO_PRIOR:
+            raise ValueError(f"GLMTarget: {family} has no dispersion parameter; dispersion_prior is for "
+                             f"{tuple(GLM_DISPERSION)}")
+        if disp:
+            m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
+            try:
+                m_tau, s_tau = (float(v) for v in m_s)
+            except (TypeError, ValueError):
+                raise ValueError("GLMTarget: dispersion_prior must be a pair (m, s)") from None
+            if not math.isfinite(m_tau):
+                raise ValueError("GLMTarget: dispersion_prior's m must be finite")
+            if not (math.isfinite(s_tau) and s_tau > 0.0):
+                raise ValueError("GLMTarget: dispersion_prior's s must be finite and > 0")
         X = np.asarray(X, dtype=np.float64)
         if X.ndim == 1:
             X = X.reshape(-1, 1)
@@ -232,30 +256,43 @@ class GLMTarget(DeviceTarget):
         if n < 1:
             raise ValueError("GLMTarget: at least one observation")
         ic = 1 if intercept else 0
-        D = p + ic
-        if D < 1:
+        Dc = p + ic
+        D = Dc + (1 if disp else 0)
+        if Dc < 1:
             raise ValueError("GLMTarget: no coefficients (p = 0 without an intercept)")
         if D > GLM_MAX_DIM:
-            raise ValueError(f"GLMTarget: D = {D} coefficients; the device functor covers D <= {GLM_MAX_DIM}. "
+            what = f"D = {D} coefficients" if not disp else f"D = {D} coordinates ({Dc} coefficients and tau)"
+            raise ValueError(f"GLMTarget: {what}; the device functor covers D <= {GLM_MAX_DIM}. "
                              "Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
         if not np.all(np.isfinite(X)):
             raise ValueError("GLMTarget: X must be finite")
         if family == "bernoulli_logit":
             if not np.all((y == 0.0) | (y == 1.0)):
                 raise ValueError("GLMTarget: bernoulli_logit needs y in {0, 1}")
-        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
-            raise ValueError("GLMTarget: poisson_log needs y in {0, 1, 2, ...}")
+        elif family == "poisson_log":
+            if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
+                raise ValueError("GLMTarget: poisson_log needs y in {0, 1, 2, ...}")
+        elif family == "normal":
+            if not np.all(np.isfinite(y)):
+                raise ValueError("GLMTarget: normal needs finite y")
+        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
+            raise ValueError("GLMTarget: neg_binomial_2_log needs y in {0, 1, 2, ..., 2^53}")
         s = np.asarray(prior_sd, dtype=np.float64)
         if s.ndim == 0:
-            s = np.full(D, float(s))
-        if s.shape != (D,):
-            raise ValueError(f"GLMTarget: prior_sd must be a scalar or one value per coefficient (D = {D})")
+            s = np.full(Dc, float(s))
+        if s.shape != (Dc,):
+            raise ValueError(f"GLMTarget: prior_sd must be a scalar or one value per coefficient ({Dc})"
+                             if disp else f"GLMTarget: prior_sd must be a scalar or one value per coefficient (D = {D})")
         if not np.all(np.isfinite(s) & (s > 0.0)):
             raise ValueError("GLMTarget: prior_sd must be finite and > 0")
         self.family, self.intercept = family, bool(intercept)
         self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
-        data = np.concatenate([[float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic)], s, y, X.reshape(-1)])
+        self.dispersion_prior = (m_tau, s_tau) if disp else None
+        head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic)]
+        data = np.concatenate([head, s, [m_tau, s_tau] if disp else [], y, X.reshape(-1)])
         names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)]
+        if disp:
+            names.append(GLM_DISPERSION[family])
         super().__init__(data, D, names)
 
 
@@ -267,6 +304,20 @@ def LogisticRegression(X, y, prior_sd=2.5, intercept=True):
 def PoissonRegression(X, y, prior_sd=2.5, intercept=True):
     """Bayesian Poisson regression with a log link: GLMTarget(X, y, family="poisson_log", ...)."""
     return GLMTarget(X, y, family="poisson_log", prior_sd=prior_sd, intercept=intercept)
+
+
+def LinearRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True):
+    """Bayesian linear regression, y ~ normal(eta, sigma) with log sigma ~ N(m, s^2):
+    GLMTarget(X, y, family="normal", ...).  The last coordinate is log sigma; constrain() reports sigma."""
+    return GLMTarget(X, y, family="normal", prior_sd=prior_sd, intercept=intercept, dispersion_prior=dispersion_prior)
+
+
+def NegativeBinomialRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True):
+    """Bayesian negative-binomial (NB2) regression with a log link, y ~ neg_binomial_2_log(eta, phi) with
+    log phi ~ N(m, s^2): GLMTarget(X, y, family="neg_binomial_2_log", ...).  The last coordinate is log phi;
+    constrain() reports phi."""
+    return GLMTarget(X, y, family="neg_binomial_2_log", prior_sd=prior_sd, intercept=intercept,
+                     dispersion_prior=dispersion_prior)
 
 
 def StanModel(model_name, model_path=None, data_path=None):

@@ -1,14 +1,16 @@
 """GLM target (GLMTarget, SMCN_MODEL_GLM) throughput on one MI355X: one JSON line per case.
 
-    python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096]
+    python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096] [--families normal,neg_binomial_2_log]
 
 GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
-(1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)} and poisson_log at (1 000, 25); synthetic data from fixed seeds.  The step size of each case
+(1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)}, poisson_log at (1 000, 25), and normal and neg_binomial_2_log
+(D counts tau) at (100, 8), (1 000, 16), (1 000, 25); synthetic data from fixed seeds (--families: a subset).  The step size of each case
 is the largest of a halving ladder whose pilot NUTS launch averages >= 8 leapfrogs per tree (trees of 2^3-2^4).
 Per case: leapfrog/s and mean leapfrogs per tree of a K-generation SMCSampler run (forward L-kernel, device-resident
 loop), milliseconds per NUTS launch (smcn_timers), and the fp64 rate counted as 4 n D flop per leapfrog (eta and the
-gradient: two multiply-adds per design entry) against the 78.6 TF peak bench.py uses.  The (1 000, 25) logistic case is
-also run at --host-N particles both device-native and through HostTarget with the numpy density of tests/_glm.py.
+gradient: two multiply-adds per design entry) against the 78.6 TF peak bench.py uses.  The (1 000, 25) cases of
+logistic, normal and NB are also run at --host-N particles both device-native and through HostTarget with the numpy
+density of tests/_glm.py / tests/_glm_disp.py.
 """
 import argparse
 import json
@@ -26,7 +28,10 @@ PEAK_FP64 = 78.6e12
 
 # (the two D = 16 / 17 cases sit on either side of the boundary between the functor's two shapes)
 CASES = [("bernoulli_logit", 100, 8), ("bernoulli_logit", 1000, 25), ("bernoulli_logit", 10000, 64),
-         ("poisson_log", 1000, 25), ("bernoulli_logit", 1000, 16), ("bernoulli_logit", 1000, 17)]
+         ("poisson_log", 1000, 25), ("bernoulli_logit", 1000, 16), ("bernoulli_logit", 1000, 17),
+         ("normal", 100, 8), ("normal", 1000, 16), ("normal", 1000, 25),
+         ("neg_binomial_2_log", 100, 8), ("neg_binomial_2_log", 1000, 16), ("neg_binomial_2_log", 1000, 25)]
+HOST_CASES = (("bernoulli_logit", 1000, 25), ("normal", 1000, 25), ("neg_binomial_2_log", 1000, 25))
 
 
 def pick_step(target, N, seed):
@@ -66,12 +71,24 @@ def main():
     ap.add_argument("--N", type=int, default=65536)
     ap.add_argument("--host-N", type=int, default=4096)
     ap.add_argument("--host-K", type=int, default=3)
+    ap.add_argument("--families", default=None, help="comma-separated subset of the families (default: all)")
     a = ap.parse_args()
     import _glm
+    import _glm_disp
     from smcnuts_amd import GLMTarget
+    fams = None if a.families is None else set(a.families.split(","))
     for family, n, D in CASES:
-        X, y = _glm.synthetic(family, n, D - 1, 1000 + D, scale=0.5)
-        t = GLMTarget(X, y, family=family, prior_sd=2.0)
+        if fams is not None and family not in fams:
+            continue
+        disp = family in _glm_disp.DISP_FAMILIES
+        if disp:
+            X, y = _glm_disp.synthetic(family, n, D - 2, 1000 + D, scale=0.5)
+            t = GLMTarget(X, y, family=family, prior_sd=2.0, dispersion_prior=(0.0, 2.5))
+            host_model = lambda: _glm_disp.GLMDispNumpy(X, y, family, 2.0, (0.0, 2.5))
+        else:
+            X, y = _glm.synthetic(family, n, D - 1, 1000 + D, scale=0.5)
+            t = GLMTarget(X, y, family=family, prior_sd=2.0)
+            host_model = lambda: _glm.GLMNumpy(X, y, family, 2.0)
         eps, pilot = pick_step(t, a.N, 5)
         run(t, a.N, 2, eps, 6)                                   # warm-up: code objects, allocations
         r = run(t, a.N, a.K, eps, 7)
@@ -79,9 +96,9 @@ def main():
                  fp64_tflops=4.0 * n * D * r["leapfrog_per_s"] / 1e12)
         r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
         print(json.dumps(r), flush=True)
-        if (family, n, D) == ("bernoulli_logit", 1000, 25):
+        if (family, n, D) in HOST_CASES:
             dev = run(t, a.host_N, a.host_K, eps, 8)
-            host = run(_glm.GLMNumpy(X, y, family, 2.0), a.host_N, a.host_K, eps, 8)
+            host = run(host_model(), a.host_N, a.host_K, eps, 8)
             print(json.dumps(dict(case=f"{family}_n{n}_D{D}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
                                   device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
                                   speedup=host["run_s"] / dev["run_s"])), flush=True)
