@@ -38,6 +38,12 @@ typedef struct smcn_ctx smcn_ctx;
                               family 2 (normal, sigma = e^tau) or 3 (neg_binomial_2_log, phi = e^tau): [family, n, p, intercept,
                               s_1..s_Dc, m_tau, s_tau, y_1..y_n, X], Dc = p + intercept, x = (b_1..b_Dc, tau), D = Dc + 1 <= 64,
                               tau ~ N(m_tau, s_tau^2); constrain reports e^tau */
+#define SMCN_MODEL_HGLM 5   /* varying-intercept GLM, non-centred: data = [family (0..3 as SMCN_MODEL_GLM), n, p, intercept, J,
+                              s_1..s_Dc, s_tau, (m_d, s_d: families 2, 3), y_1..y_n, g_1..g_n (in 0..J-1), X (n x p, row-major)],
+                              Dc = p + intercept >= 0, J >= 1 groups; eta_i = [b_0 +] X_i b + e^lt z_{g_i}, b_c ~ N(0, s_c^2),
+                              z_j ~ N(0, 1), e^lt ~ half-normal(s_tau), ld ~ N(m_d, s_d^2) (dispersion e^ld);
+                              x = (b_1..b_Dc, z_1..z_J, lt [, ld]), D = Dc + J + 1 (+ 1) <= 64;
+                              constrain reports (b, e^lt z_1..e^lt z_J, e^lt [, e^ld]) */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

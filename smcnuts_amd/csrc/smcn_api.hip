@@ -92,6 +92,8 @@ struct smcn_ctx {
     int64_t stage_len = 0;
     double* stage2 = nullptr;
     int64_t stage2_len = 0;
+    double* cstage = nullptr;   // SMCN_MODEL_HGLM: the constrained population the moment kernels read ([ngen][D][N])
+    int64_t cstage_len = 0;
     int32_t *nleap = nullptr, *depth = nullptr, *ndraws = nullptr, *flags = nullptr;
     int64_t* idx = nullptr;
     unsigned int* queue = nullptr;
@@ -422,6 +424,8 @@ static int with_model(smcn_ctx* c, F&& f) {
         if (c->D <= 16) return f(GlmModel<8, 2>{});
         return f(GlmModel<64, 1>{});
     }
+    // (smcn_ctx_create has checked the data and refused D > 64)
+    if (c->model == SMCN_MODEL_HGLM) return f(GlmHierModel<64, 1>{});
     if (c->model == SMCN_MODEL_HOST) FAIL(c, "host target: this entry point needs a device-native model");
     FAIL(c, "model not available in this build");
 }
@@ -477,6 +481,60 @@ static std::string glm_check(const double* md, int64_t len, int* D_out) {
     return "";
 }
 
+// SMCN_MODEL_HGLM: checks the caller's data block; "" and D, or what is wrong with it
+static std::string hglm_check(const double* md, int64_t len, int* D_out) {
+    const char* layout = "hierarchical GLM target: data = [family, n, p, intercept, J, s_1..s_Dc, s_tau, (m_d, s_d: families "
+                         "2, 3), y_1..y_n, g_1..g_n, X (n x p, row-major)]";
+    if (len < 5) return layout;
+    const double fam = md[0], nd = md[1], pd = md[2], icd = md[3], Jd = md[4];
+    if (!(fam == 0.0 || fam == 1.0 || fam == 2.0 || fam == 3.0))
+        return "hierarchical GLM target: family must be 0 (bernoulli_logit), 1 (poisson_log), 2 (normal) or 3 "
+               "(neg_binomial_2_log)";
+    const bool disp = fam >= 2.0;
+    if (!(icd == 0.0 || icd == 1.0)) return "hierarchical GLM target: intercept must be 0 or 1";
+    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd))
+        return "hierarchical GLM target: n must be an integer >= 1";
+    if (!(pd >= 0.0 && pd <= 1048576.0 && pd == (double)(int64_t)pd))
+        return "hierarchical GLM target: p must be an integer >= 0";
+    if (!(Jd >= 1.0 && Jd <= 1048576.0 && Jd == (double)(int64_t)Jd))
+        return "hierarchical GLM target: J must be an integer >= 1 (the number of groups)";
+    const int64_t n = (int64_t)nd, p = (int64_t)pd, Dc = p + (int64_t)icd, J = (int64_t)Jd;
+    const int64_t D = Dc + J + 1 + (disp ? 1 : 0);
+    if (D > 64)
+        return "hierarchical GLM target: the device functor covers D = Dc + J + 1 (+ 1) <= 64 coordinates; larger models "
+               "run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
+               "HostTarget)";
+    const int64_t head = hglm_head(Dc, disp);
+    if (len != head + 2 * n + n * p) return layout;
+    for (int64_t c = 0; c < Dc; ++c)
+        if (!(md[5 + c] > 0.0 && std::isfinite(md[5 + c]))) return "hierarchical GLM target: prior sds must be finite and > 0";
+    if (!(md[5 + Dc] > 0.0 && std::isfinite(md[5 + Dc]))) return "hierarchical GLM target: s_tau must be finite and > 0";
+    if (disp) {
+        if (!std::isfinite(md[6 + Dc])) return "hierarchical GLM target: m_d must be finite";
+        if (!(md[7 + Dc] > 0.0 && std::isfinite(md[7 + Dc]))) return "hierarchical GLM target: s_d must be finite and > 0";
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const double y = md[head + i];
+        if (fam == 0.0) {
+            if (!(y == 0.0 || y == 1.0)) return "hierarchical GLM target: bernoulli_logit needs y in {0, 1}";
+        } else if (fam == 2.0) {
+            if (!std::isfinite(y)) return "hierarchical GLM target: normal needs finite y";
+        } else if (!(y >= 0.0 && y <= 9007199254740992.0 && y == std::floor(y))) {
+            return fam == 1.0 ? "hierarchical GLM target: poisson_log needs y in {0, 1, 2, ..}"
+                              : "hierarchical GLM target: neg_binomial_2_log needs y in {0, 1, 2, .., 2^53}";
+        }
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const double g = md[head + n + i];
+        if (!(g >= 0.0 && g < Jd && g == std::floor(g)))
+            return "hierarchical GLM target: every group index g must be an integer in [0, J)";
+    }
+    for (int64_t t = 0; t < n * p; ++t)
+        if (!std::isfinite(md[head + 2 * n + t])) return "hierarchical GLM target: X must be finite";
+    *D_out = (int)D;
+    return "";
+}
+
 extern "C" {
 
 int smcn_version(void) { return 1; }
@@ -514,7 +572,7 @@ static void free_all(smcn_ctx* c) {
                     c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
                     c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
                     c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover};
+                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage};
     if (c->rows_h) (void)hipHostFree(c->rows_h);
     if (c->hist_h) (void)hipHostFree(c->hist_h);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
@@ -578,6 +636,15 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             }
             break;
         }
+        case SMCN_MODEL_HGLM: {
+            const std::string why = hglm_check(model_data, model_data_len, &c->D);
+            if (!why.empty()) {
+                g_create_error = "smcn_ctx_create: " + why;
+                delete c;
+                return -1;
+            }
+            break;
+        }
         default:
             g_create_error = "smcn_ctx_create: unknown model id";
             delete c;
@@ -587,6 +654,9 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
     // constrain_coord applies to arma's log sigma (the other models keep their own id)
     c->cmodel = (model_id == SMCN_MODEL_GLM && model_data[0] >= 2.0) ? SMCN_MODEL_ARMA : model_id;
+    // hierarchical GLM: its constrained space is not coordinate-wise; the moment kernels read a constrained copy of the
+    // population (hglm_constrained) with the identity
+    if (model_id == SMCN_MODEL_HGLM) c->cmodel = SMCN_MODEL_HOST;
     auto fail = [&](const char* what, hipError_t er) {
         g_create_error = std::string("smcn_ctx_create: ") + what + ": " + hipGetErrorString(er);
         free_all(c);
@@ -638,6 +708,26 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             const double y = model_data[4 + HD + i];
             row[RS - 2] = y;
             row[RS - 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
+        }
+    }
+    // hierarchical GLM: the table GlmHierModel reads -- GlmModel's row with the group index behind y and lgamma(y + 1),
+    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1), g_i, 0], at a 128-byte boundary, zero
+    // rows up to a multiple of 64 observations
+    if (model_id == SMCN_MODEL_HGLM) {
+        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
+        const int64_t Dc = p + ic, head = hglm_head(Dc, model_data[0] >= 2.0);
+        const int RS = hglm_row_doubles((int)Dc), DP = RS - 4;
+        const int64_t t0 = hglm_table_offset(head, n, p), rows = glm_table_rows(n);
+        mup.assign(t0 + rows * RS, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            if (ic) row[0] = 1.0;
+            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[head + 2 * n + i * p + j];
+            const double y = model_data[head + i];
+            row[DP] = y;
+            row[DP + 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
+            row[DP + 2] = model_data[head + n + i];
         }
     }
     const int64_t mlen = (int64_t)mup.size();
@@ -787,6 +877,22 @@ static int ensure_stage2(smcn_ctx* c, int64_t n) {
     c->stage2 = nullptr;
     HIPC(c, dalloc(&c->stage2, n));
     c->stage2_len = n;
+    return 0;
+}
+// SMCN_MODEL_HGLM: the constrained population of ngen consecutive generations ([ngen][D][N] from x) into c->cstage, on
+// the context's stream; *out is what the moment kernels then read with the identity (c->cmodel)
+static int hglm_constrained(smcn_ctx* c, const double* x, int ngen, const double** out) {
+    const int64_t M = (int64_t)ngen * c->N, n = M * c->D;
+    if (n > c->cstage_len) {
+        if (c->cstage) (void)cached_free(c->cstage);
+        c->cstage = nullptr;
+        HIPC(c, dalloc(&c->cstage, n));
+        c->cstage_len = n;
+    }
+    const int Dc = (int)c->mdata_h[2] + (int)c->mdata_h[3], J = (int)c->mdata_h[4];
+    hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, c->cstage, M, c->N, c->D, Dc, J, 1, c->N);
+    HIPC(c, hipGetLastError());
+    *out = c->cstage;
     return 0;
 }
 // host [N][D] -> device [D][N]
@@ -972,7 +1078,12 @@ int smcn_target_constrain(smcn_ctx* c, const double* x, int64_t M, double* out) 
     if (rc) return rc;
     if ((rc = ensure_stage2(c, n))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->cmodel);
+    if (c->model == SMCN_MODEL_HGLM)
+        hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, M, c->D,
+                                                                       (int)c->mdata_h[2] + (int)c->mdata_h[3],
+                                                                       (int)c->mdata_h[4], c->D, 1);
+    else
+        constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->cmodel);
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(out, c->stage2, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
@@ -1210,7 +1321,12 @@ int smcn_moment_sums(smcn_ctx* c, const double* mean, double* sums) {
         dmean = c->scal + 16;
         HIPC(c, hipMemcpyAsync(dmean, mean, sizeof(double) * c->Dc, hipMemcpyHostToDevice, c->stream));
     }
-    moment_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(c->x, c->wn, c->N, c->D, c->cmodel, dmean, c->part);
+    const double* xs = c->x;
+    if (c->model == SMCN_MODEL_HGLM) {
+        const int rc = hglm_constrained(c, c->x, 1, &xs);
+        if (rc) return rc;
+    }
+    moment_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(xs, c->wn, c->N, c->D, c->cmodel, dmean, c->part);
     sum_final_kernel<<<final_grid(c->D), kRedBlock, 0, c->stream>>>(c->part, g, c->D, c->scal + 16 + c->D);
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(sums, c->scal + 16 + c->D, sizeof(double) * c->Dc, hipMemcpyDeviceToHost, c->stream));
@@ -2223,6 +2339,10 @@ static int enqueue_partials(smcn_ctx* c, const double* logw, const double* x, do
     const int NQB = gen_block_nq(c->Dc);   // block partials: [max, cnt, s1, s2, A.., B.., reference point..]
     while ((int64_t)g * NQB * ngen > (int64_t)kMaxPart * (4 * c->D * c->D + 2 * c->D + 8) && g > 1) g /= 2;
     const int nz = c->D >= 64 ? 8 : 1;
+    if (c->model == SMCN_MODEL_HGLM) {
+        const int rc = hglm_constrained(c, x, ngen, &x);
+        if (rc) return rc;
+    }
     gen_partials_kernel<<<dim3(g, ngen, nz), kRedBlock, 0, c->stream>>>(logw, x, N, c->D, c->cmodel, c->part, N,
                                                                         N * c->D, (c->D > 8 && ngen == 1 && nz == 1) ? c->work : nullptr);
     const int qb = c->Dc <= 16 ? 1 : (2 * c->Dc + 7) / 8 > 64 ? 64 : (2 * c->Dc + 7) / 8;

@@ -794,4 +794,126 @@ struct GlmDispModel {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Varying-intercept (hierarchical) GLM, non-centred (SMCN_MODEL_HGLM): Dc = p + intercept fixed coefficients b, J groups,
+// group index g_i of observation i,
+//   eta_i = [b_0 +] X_i b + e^lt z_{g_i},   y_i ~ family(eta_i [, e^ld])   (the four SMCN_MODEL_GLM families, same terms)
+//   b_c ~ N(0, s_c^2), z_j ~ N(0, 1), tau = e^lt ~ half-normal(s_tau) with its Jacobian, ld ~ N(m_d, s_d^2) (families 2, 3).
+// x = (b_1..b_Dc, z_1..z_J, lt [, ld]), D = Dc + J + 1 (+ 1) <= 64; one wavefront per particle, coordinate c on lane c.
+// The table smcn_ctx_create repacks behind the caller's block: a row per observation, [1 (intercept), X_i1 .. X_ip,
+// 0 (to an even count DP), y_i, lgamma(y_i + 1), g_i, 0], RS = DP + 4 doubles, at a 128-byte boundary, zero rows up to a
+// multiple of 64.  Lane l takes row k0 + l of each 64-row chunk, as GlmModel<64, 1>:
+//   eta: the fixed part with the coefficients read out as scalars, the group part with ONE cross-lane read (ds_bpermute)
+//        of z from lane Dc + g_i;
+//   the 64-step read-out of the chunk's residuals: lane c < Dc accumulates d_i X_ic, lane Dc + j accumulates d_i [g_i == j]
+//        (the broadcast group index compared with its own j; no column load), multiplied by e^lt once at the end;
+//   d / d lt = sum_i d_i alpha_{g_i} (a per-lane term) and the dispersion sum go through wave_sum4 with llik and lpri.
+// The per-observation terms are GlmModel's / GlmDispModel's own obs() (and tau_const()), called on members of which only
+// the family flag is set.  Non-finite: the GLM rules, and -inf (lpri and llik) when e^(2 lt) overflows.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline int64_t hglm_head(int64_t Dc, bool disp) { return 5 + Dc + 1 + (disp ? 2 : 0); }
+__host__ __device__ inline int64_t hglm_table_offset(int64_t head, int64_t n, int64_t p) {
+    return (head + 2 * n + n * p + 15) / 16 * 16;
+}
+__host__ __device__ inline int hglm_row_doubles(int Dc) { return ((Dc + 1) & ~1) + 4; }
+
+template <int G_, int DL_>
+struct GlmHierModel {
+    static_assert(G_ == 64 && DL_ == 1, "GlmHierModel: one wavefront per particle, one coordinate per lane");
+    static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
+    static constexpr bool DIST = true;
+    using d2 = double __attribute__((ext_vector_type(2)));
+    GlmModel<64, 1> glm;          // families 0 / 1: obs() (only `poisson` is set)
+    GlmDispModel<64, 1> disp;     // families 2 / 3: tau_const() and obs() (only `nb` is set)
+    int lg, D, Dc, J, DP, RS, n;
+    int role;                     // this lane's coordinate: 0 coefficient, 1 group z_j, 2 lt, 3 ld, 4 none
+    bool hasd;
+    const double* T;              // the repacked table
+    double mc, inv_s2, lc;        // prior of the lane's coordinate: mean, 1 / s^2, constant
+
+    __device__ int dim() const { return D; }
+    __device__ void init(const double* md, int lg_, double*) {
+        lg = lg_;
+        const double fam = md[0];
+        hasd = fam >= 2.0;
+        glm.poisson = fam == 1.0;
+        disp.nb = fam == 3.0;
+        n = (int)md[1];
+        const int p = (int)md[2];
+        Dc = p + (int)md[3];
+        J = (int)md[4];
+        D = Dc + J + 1 + (hasd ? 1 : 0);
+        DP = (Dc + 1) & ~1;
+        RS = hglm_row_doubles(Dc);
+        T = md + hglm_table_offset(hglm_head(Dc, hasd), n, p);
+        role = lg < Dc ? 0 : (lg < Dc + J ? 1 : (lg == Dc + J ? 2 : (lg < D ? 3 : 4)));
+        double s = 1.0;
+        mc = 0.0;
+        if (role == 0) s = md[5 + lg];
+        else if (role == 2) s = md[5 + Dc];
+        else if (role == 3) { mc = md[6 + Dc]; s = md[7 + Dc]; }
+        inv_s2 = role < 4 ? 1.0 / (s * s) : 0.0;
+        // half-normal on tau with the Jacobian of lt = log tau: log 2 - log s_tau - log(2 pi) / 2 (+ lt - e^2lt / 2 s_tau^2)
+        lc = role == 2 ? (0.69314718055994530942 - log(s)) - 0.5 * kLog2Pi : (role < 4 ? -log(s) - 0.5 * kLog2Pi : 0.0);
+    }
+    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
+        // ---- everything that depends on lt or ld alone, once
+        const double lt = group_read<64>(x[0], Dc + J);
+        const double tau = exp_fast(lt), e2 = tau * tau;
+        const bool bad = !(e2 < kInf);                     // e^(2 lt) overflows
+        const auto k = disp.tau_const(hasd ? group_read<64>(x[0], Dc + J + 1) : 0.0);
+        // ---- prior of the lane's coordinate
+        double lp, g0;
+        if (role == 2) {
+            lp = (lc + lt) - 0.5 * e2 * inv_s2;
+            g0 = fma(-e2, inv_s2, 1.0);
+        } else {
+            const double v = x[0] - mc;
+            g0 = -v * inv_s2;
+            lp = fma(-0.5 * v, v * inv_s2, lc);
+        }
+        // ---- observations, 64 a chunk
+        double acc[4] = {0.0, 0.0, 0.0, 0.0}, ll = 0.0, gt = 0.0, ga = 0.0;
+        const int col = lg < DP ? lg : 0;
+        const bool grp = role == 1;
+        const int jl = lg - Dc;                            // (group lanes) this lane's j
+        const double xb = lg < Dc ? x[0] : 0.0;            // (0 on the pad column)
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const d2* const row = (const d2*)(T + (int64_t)(k0 + lg) * RS);
+            double e0 = 0.0, e1 = 0.0;
+            for (int j = 0; j < DP; j += 2) {              // (j wave-uniform: the coefficients are scalar operands)
+                const d2 v = row[j >> 1];
+                e0 = fma(group_read<64>(xb, j), v.x, e0);
+                e1 = fma(group_read<64>(xb, j + 1), v.y, e1);
+            }
+            const d2 yl = row[DP >> 1];
+            const int gi = (int)row[(DP >> 1) + 1].x;
+            const double a = tau * __shfl(x[0], Dc + gi, 64);   // alpha_{g_i}
+            const double e = (e0 + e1) + a;
+            double term, d, g = 0.0;
+            if (hasd) disp.obs(k, e, yl.x, yl.y, term, d, g);
+            else glm.obs(e, yl.x, yl.y, term, d);
+            const bool live = k0 + lg < n;
+            ll += live ? term : 0.0;
+            gt += live ? g : 0.0;
+            d = live ? d : 0.0;
+            ga = fma(d, a, ga);
+            // the chunk's 64 residuals read out as scalars: column `lg` of their rows, or their group indicator
+            const double* const colp = T + (int64_t)k0 * RS + col;
+#pragma unroll 16
+            for (int i = 0; i < 64; ++i) {
+                const double w = grp ? (__builtin_amdgcn_readlane(gi, i) == jl ? 1.0 : 0.0) : colp[(int64_t)i * RS];
+                acc[i & 3] = fma(lane_value(d, i), w, acc[i & 3]);
+            }
+        }
+        double L, P, GT, GA;
+        wave_sum4(ll, lp, gt, ga, L, P, GT, GA);
+        const double cs = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        gl[0] = role == 0 ? cs : (role == 1 ? tau * cs : (role == 2 ? GA : (role == 3 ? GT : 0.0)));
+        gp[0] = g0;
+        llik = (bad || k.bad) ? -kInf : L;
+        lpri = bad ? -kInf : P;
+    }
+};
+
 }  // namespace smcn

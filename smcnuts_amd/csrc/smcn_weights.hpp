@@ -112,6 +112,22 @@ __global__ void constrain_kernel(const double* x, double* out, int64_t M, int D,
     const int c = (int)(t % D);
     out[t] = constrain_coord(model_id, c, D, x[t]);
 }
+// constrain() of the hierarchical GLM (SMCN_MODEL_HGLM): (b, z, lt [, ld]) -> (b, e^lt z, e^lt [, e^ld]).  Not
+// coordinate-wise (alpha_j = tau z_j), so a pass of its own that writes the constrained population out; the moment
+// kernels then run on that with the identity (model id 3).  One thread per particle; particle t of M has coordinate c
+// at x[(t / Np) * Np * D + (t % Np) * si + c * sc] (host [M][D]: Np = M, si = D, sc = 1; device [ngen][D][N]: Np = N,
+// si = 1, sc = N).
+__global__ void hglm_constrain_kernel(const double* x, double* out, int64_t M, int64_t Np, int D, int Dc, int J,
+                                      int64_t si, int64_t sc) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    const int64_t base = (t / Np) * Np * D + (t % Np) * si;
+    const double tau = exp(x[base + (int64_t)(Dc + J) * sc]);
+    for (int c = 0; c < D; ++c) {
+        const double v = x[base + (int64_t)c * sc];
+        out[base + (int64_t)c * sc] = c < Dc ? v : (c < Dc + J ? tau * v : exp(v));
+    }
+}
 
 // ---- transposes between host [N][D] and device [D][N] ------------------------
 __global__ void transpose_kernel(const double* in, double* out, int64_t rows, int64_t cols) {

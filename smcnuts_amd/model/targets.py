@@ -296,6 +296,112 @@ class GLMTarget(DeviceTarget):
         super().__init__(data, D, names)
 
 
+class HierarchicalGLM(DeviceTarget):
+    """Varying-intercept GLM on the device, non-centred: observations fall into J groups, group j has the intercept
+    alpha_j = tau z_j,
+      eta_i = [b_0 +] X_i b + tau z_{g_i},   y_i ~ family(eta_i [, e^ld])   (GLMTarget's four families, same terms)
+      b_c ~ N(0, prior_sd_c^2),  z_j ~ N(0, 1),  tau ~ half-normal(group_sd_prior) (sampled as lt = log tau, with its
+      Jacobian),  e^ld ~ lognormal(m, s) for dispersion_prior = (m, s) (families normal / neg_binomial_2_log).
+    x = (b_1..b_Dc, z_1..z_J, lt [, ld]), D = Dc + J + 1 (+ 1) <= 64 (larger models: HostTarget); Dc = p + intercept may
+    be 0.  `groups` holds each observation's group in 0..J-1, J = max + 1 unless n_groups is given (groups without
+    observations keep their prior).  `constrain` reports (b, alpha_1..alpha_J, tau [, sigma | phi]).
+
+    Data block (include/smcnuts_hip.h, SMCN_MODEL_HGLM):
+    [family, n, p, intercept, J, s_1..s_Dc, s_tau, (m, s: families 2, 3), y_1..y_n, g_1..g_n, X (n x p, row-major)]."""
+    model_id = _capi.MODEL_HGLM
+
+    def __init__(self, X, y, groups, family="bernoulli_logit", prior_sd=2.5, group_sd_prior=1.0, intercept=True,
+                 dispersion_prior=_NO_PRIOR, n_groups=None):
+        if family not in GLM_FAMILIES:
+            raise ValueError(f"HierarchicalGLM: family must be one of {GLM_FAMILIES}, not {family!r}")
+        disp = family in GLM_DISPERSION
+        if not disp and dispersion_prior is not _NO_PRIOR:
+            raise ValueError(f"HierarchicalGLM: {family} has no dispersion parameter; dispersion_prior is for "
+                             f"{tuple(GLM_DISPERSION)}")
+        if disp:
+            m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
+            try:
+                m_d, s_d = (float(v) for v in m_s)
+            except (TypeError, ValueError):
+                raise ValueError("HierarchicalGLM: dispersion_prior must be a pair (m, s)") from None
+            if not math.isfinite(m_d):
+                raise ValueError("HierarchicalGLM: dispersion_prior's m must be finite")
+            if not (math.isfinite(s_d) and s_d > 0.0):
+                raise ValueError("HierarchicalGLM: dispersion_prior's s must be finite and > 0")
+        try:
+            s_tau = float(group_sd_prior)
+        except (TypeError, ValueError):
+            raise ValueError("HierarchicalGLM: group_sd_prior must be a number") from None
+        if not (math.isfinite(s_tau) and s_tau > 0.0):
+            raise ValueError("HierarchicalGLM: group_sd_prior must be finite and > 0")
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2:
+            raise ValueError("HierarchicalGLM: X must be an (n, p) matrix")
+        n, p = X.shape
+        if n < 1:
+            raise ValueError("HierarchicalGLM: at least one observation")
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim != 1 or y.shape[0] != n:
+            raise ValueError(f"HierarchicalGLM: y must be a vector of the n = {n} observations X has rows for")
+        g = np.asarray(groups)
+        if g.ndim != 1 or g.shape[0] != n:
+            raise ValueError(f"HierarchicalGLM: groups must be a vector of the n = {n} observations X has rows for")
+        if g.dtype == bool or not (np.issubdtype(g.dtype, np.integer) or np.issubdtype(g.dtype, np.floating)):
+            raise ValueError("HierarchicalGLM: groups must be integers")
+        gf = g.astype(np.float64)
+        if not np.all(np.isfinite(gf) & (gf == np.floor(gf))):
+            raise ValueError("HierarchicalGLM: groups must be integers")
+        if np.any(gf < 0):
+            raise ValueError("HierarchicalGLM: groups must be >= 0")
+        J = int(gf.max()) + 1 if n_groups is None else n_groups
+        if isinstance(J, bool) or not isinstance(J, (int, np.integer)) or J < 1:
+            raise ValueError("HierarchicalGLM: n_groups must be an integer >= 1")
+        J = int(J)
+        if gf.max() >= J:
+            raise ValueError(f"HierarchicalGLM: groups must be in 0..n_groups - 1 = {J - 1}")
+        ic = 1 if intercept else 0
+        Dc = p + ic
+        D = Dc + J + 1 + (1 if disp else 0)
+        if D > GLM_MAX_DIM:
+            raise ValueError(f"HierarchicalGLM: D = {D} coordinates ({Dc} coefficients, {J} groups, tau"
+                             f"{', ' + GLM_DISPERSION[family] if disp else ''}); the device functor covers "
+                             f"D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget "
+                             "instead.")
+        if not np.all(np.isfinite(X)):
+            raise ValueError("HierarchicalGLM: X must be finite")
+        if family == "bernoulli_logit":
+            if not np.all((y == 0.0) | (y == 1.0)):
+                raise ValueError("HierarchicalGLM: bernoulli_logit needs y in {0, 1}")
+        elif family == "poisson_log":
+            if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
+                raise ValueError("HierarchicalGLM: poisson_log needs y in {0, 1, 2, ...}")
+        elif family == "normal":
+            if not np.all(np.isfinite(y)):
+                raise ValueError("HierarchicalGLM: normal needs finite y")
+        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
+            raise ValueError("HierarchicalGLM: neg_binomial_2_log needs y in {0, 1, 2, ..., 2^53}")
+        s = np.asarray(prior_sd, dtype=np.float64)
+        if s.ndim == 0:
+            s = np.full(Dc, float(s))
+        if s.shape != (Dc,):
+            raise ValueError(f"HierarchicalGLM: prior_sd must be a scalar or one value per coefficient ({Dc})")
+        if not np.all(np.isfinite(s) & (s > 0.0)):
+            raise ValueError("HierarchicalGLM: prior_sd must be finite and > 0")
+        self.family, self.intercept, self.n_groups = family, bool(intercept), J
+        self.X, self.y, self.groups, self.prior_sd = X.copy(), y.copy(), gf.astype(np.int64), s.copy()
+        self.group_sd_prior = s_tau
+        self.dispersion_prior = (m_d, s_d) if disp else None
+        head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic), float(J)]
+        data = np.concatenate([head, s, [s_tau], [m_d, s_d] if disp else [], y, gf, X.reshape(-1)])
+        names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)] \
+            + [f"alpha.{j + 1}" for j in range(J)] + ["tau"]
+        if disp:
+            names.append(GLM_DISPERSION[family])
+        super().__init__(data, D, names)
+
+
 def LogisticRegression(X, y, prior_sd=2.5, intercept=True):
     """Bayesian logistic regression: GLMTarget(X, y, family="bernoulli_logit", ...)."""
     return GLMTarget(X, y, family="bernoulli_logit", prior_sd=prior_sd, intercept=intercept)

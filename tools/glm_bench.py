@@ -1,6 +1,8 @@
-"""GLM target (GLMTarget, SMCN_MODEL_GLM) throughput on one MI355X: one JSON line per case.
+"""GLM targets (GLMTarget, SMCN_MODEL_GLM; HierarchicalGLM, SMCN_MODEL_HGLM) throughput on one MI355X: one JSON line
+per case.
 
     python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096] [--families normal,neg_binomial_2_log]
+                              [--models glm,hier]
 
 GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
 (1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)}, poisson_log at (1 000, 25), and normal and neg_binomial_2_log
@@ -11,6 +13,9 @@ loop), milliseconds per NUTS launch (smcn_timers), and the fp64 rate counted as 
 gradient: two multiply-adds per design entry) against the 78.6 TF peak bench.py uses.  The (1 000, 25) cases of
 logistic, normal and NB are also run at --host-N particles both device-native and through HostTarget with the numpy
 density of tests/_glm.py / tests/_glm_disp.py.
+Hierarchical cases (varying intercepts, D = Dc + J + 1 (+ 1)): bernoulli_logit with n = 1 000, Dc = 5, J = 20 and
+normal with n = 1 000, Dc = 3, J = 50, the same way; the logistic one also against HostTarget with tests/_hglm.py's
+numpy density.  Their flop count is 4 n (Dc + 1) per leapfrog (eta's fixed part and its gradient, plus the group term).
 """
 import argparse
 import json
@@ -32,6 +37,9 @@ CASES = [("bernoulli_logit", 100, 8), ("bernoulli_logit", 1000, 25), ("bernoulli
          ("normal", 100, 8), ("normal", 1000, 16), ("normal", 1000, 25),
          ("neg_binomial_2_log", 100, 8), ("neg_binomial_2_log", 1000, 16), ("neg_binomial_2_log", 1000, 25)]
 HOST_CASES = (("bernoulli_logit", 1000, 25), ("normal", 1000, 25), ("neg_binomial_2_log", 1000, 25))
+# hierarchical: (family, n, Dc, J)
+HIER_CASES = [("bernoulli_logit", 1000, 5, 20), ("normal", 1000, 3, 50)]
+HIER_HOST_CASES = (("bernoulli_logit", 1000, 5, 20),)
 
 
 def pick_step(target, N, seed):
@@ -72,12 +80,14 @@ def main():
     ap.add_argument("--host-N", type=int, default=4096)
     ap.add_argument("--host-K", type=int, default=3)
     ap.add_argument("--families", default=None, help="comma-separated subset of the families (default: all)")
+    ap.add_argument("--models", default="glm,hier", help="glm (GLMTarget cases), hier (HierarchicalGLM cases), or both")
     a = ap.parse_args()
+    models = set(a.models.split(","))
     import _glm
     import _glm_disp
     from smcnuts_amd import GLMTarget
     fams = None if a.families is None else set(a.families.split(","))
-    for family, n, D in CASES:
+    for family, n, D in (CASES if "glm" in models else []):
         if fams is not None and family not in fams:
             continue
         disp = family in _glm_disp.DISP_FAMILIES
@@ -100,6 +110,35 @@ def main():
             dev = run(t, a.host_N, a.host_K, eps, 8)
             host = run(host_model(), a.host_N, a.host_K, eps, 8)
             print(json.dumps(dict(case=f"{family}_n{n}_D{D}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
+                                  device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
+                                  speedup=host["run_s"] / dev["run_s"])), flush=True)
+    if "hier" in models:
+        hier(a, fams)
+
+
+def hier(a, fams):
+    import _hglm
+    from smcnuts_amd import HierarchicalGLM
+    for family, n, Dc, J in HIER_CASES:
+        if fams is not None and family not in fams:
+            continue
+        disp = family in _hglm.gd.DISP_FAMILIES
+        D = Dc + J + 1 + (1 if disp else 0)
+        X, y, g = _hglm.synthetic(family, n, Dc - 1, J, 2000 + D)
+        kw = dict(dispersion_prior=(0.0, 2.5)) if disp else {}
+        t = HierarchicalGLM(X, y, g, family=family, prior_sd=2.0, group_sd_prior=1.0, n_groups=J, **kw)
+        host_model = lambda: _hglm.HGLMNumpy(X, y, g, family, 2.0, 1.0, (0.0, 2.5), n_groups=J)
+        eps, pilot = pick_step(t, a.N, 5)
+        run(t, a.N, 2, eps, 6)
+        r = run(t, a.N, a.K, eps, 7)
+        r.update(case=f"hier_{family}_n{n}_Dc{Dc}_J{J}", family=family, n=n, Dc=Dc, J=J, D=D, N=a.N, K=a.K,
+                 step_size=eps, pilot_nleap=pilot, fp64_tflops=4.0 * n * (Dc + 1) * r["leapfrog_per_s"] / 1e12)
+        r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
+        print(json.dumps(r), flush=True)
+        if (family, n, Dc, J) in HIER_HOST_CASES:
+            dev = run(t, a.host_N, a.host_K, eps, 8)
+            host = run(host_model(), a.host_N, a.host_K, eps, 8)
+            print(json.dumps(dict(case=f"hier_{family}_n{n}_Dc{Dc}_J{J}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
                                   device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
                                   speedup=host["run_s"] / dev["run_s"])), flush=True)
 
