@@ -44,6 +44,12 @@ typedef struct smcn_ctx smcn_ctx;
                               z_j ~ N(0, 1), e^lt ~ half-normal(s_tau), ld ~ N(m_d, s_d^2) (dispersion e^ld);
                               x = (b_1..b_Dc, z_1..z_J, lt [, ld]), D = Dc + J + 1 (+ 1) <= 64;
                               constrain reports (b, e^lt z_1..e^lt z_J, e^lt [, e^ld]) */
+#define SMCN_MODEL_CATEGORICAL 6   /* categorical (multinomial logistic) regression, class 0 the reference: data = [K, n, p,
+                              intercept, s_1..s_D, y_1..y_n (labels in 0..K-1), X (n x p, row-major)], 2 <= K <= 16,
+                              Dc = p + intercept >= 1; eta_i0 = 0, eta_ik = [b_k0 +] X_i b_k (k = 1..K-1),
+                              log p(y_i) = eta_{i,y_i} - logsumexp_k eta_ik, b_c ~ N(0, s_c^2);
+                              x = (b_1,1..b_1,Dc, .., b_K-1,1..b_K-1,Dc) class-major, D = (K - 1) Dc <= 64;
+                              constrain is the identity */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

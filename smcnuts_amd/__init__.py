@@ -8,6 +8,6 @@ include/smcnuts_hip.h (libsmcnuts_hip.so), reached through ctypes.  No PyTorch
 on this path and no CPU fallback.
 """
 from .smc_sampler import SMCSampler  # noqa: F401
-from .model.targets import (ArmaModel, GaussianTarget, GLMTarget, HierarchicalGLM, HostTarget, IsoGaussian,  # noqa: F401
-                            LinearRegression, LogisticRegression, NegativeBinomialRegression, PoissonRegression,
-                            PRMwCDModel, StanModel)
+from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GLMTarget, HierarchicalGLM,  # noqa: F401
+                            HostTarget, IsoGaussian, LinearRegression, LogisticRegression, NegativeBinomialRegression,
+                            PoissonRegression, PRMwCDModel, StanModel)

@@ -426,6 +426,11 @@ static int with_model(smcn_ctx* c, F&& f) {
     }
     // (smcn_ctx_create has checked the data and refused D > 64)
     if (c->model == SMCN_MODEL_HGLM) return f(GlmHierModel<64, 1>{});
+    if (c->model == SMCN_MODEL_CATEGORICAL) {
+        // (checked at creation: 2 <= K <= 16, D = (K - 1) Dc <= 64)
+        if (c->D <= 8) return f(GlmCatModel<8, 1>{});
+        return f(GlmCatModel<64, 1>{});
+    }
     if (c->model == SMCN_MODEL_HOST) FAIL(c, "host target: this entry point needs a device-native model");
     FAIL(c, "model not available in this build");
 }
@@ -531,6 +536,38 @@ static std::string hglm_check(const double* md, int64_t len, int* D_out) {
     }
     for (int64_t t = 0; t < n * p; ++t)
         if (!std::isfinite(md[head + 2 * n + t])) return "hierarchical GLM target: X must be finite";
+    *D_out = (int)D;
+    return "";
+}
+
+// SMCN_MODEL_CATEGORICAL: checks the caller's data block; "" and D, or what is wrong with it
+static std::string cat_check(const double* md, int64_t len, int* D_out) {
+    const char* layout = "categorical target: data = [K, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], "
+                         "D = (K - 1) (p + intercept)";
+    if (len < 4) return layout;
+    const double Kd = md[0], nd = md[1], pd = md[2], icd = md[3];
+    if (!(Kd >= 2.0 && Kd <= (double)kCatMaxClasses && Kd == std::floor(Kd)))
+        return "categorical target: K must be an integer in [2, 16] (the device functor holds up to 16 classes; more "
+               "run host-evaluated: SMCN_MODEL_HOST + smcn_set_host_target, any object with logpdf / logpdfgrad "
+               "through HostTarget)";
+    if (!(icd == 0.0 || icd == 1.0)) return "categorical target: intercept must be 0 or 1";
+    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd)) return "categorical target: n must be an integer >= 1";
+    if (!(pd >= 0.0 && pd <= 1048576.0 && pd == (double)(int64_t)pd)) return "categorical target: p must be an integer >= 0";
+    const int64_t n = (int64_t)nd, p = (int64_t)pd, Dc = p + (int64_t)icd, D = ((int64_t)Kd - 1) * Dc;
+    if (Dc < 1) return "categorical target: no coefficients (p = 0 without an intercept)";
+    if (D > 64)
+        return "categorical target: the device functor covers D = (K - 1) (p + intercept) <= 64 coefficients; larger "
+               "models run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad "
+               "through HostTarget)";
+    if (len != 4 + D + n + n * p) return layout;
+    for (int64_t c = 0; c < D; ++c)
+        if (!(md[4 + c] > 0.0 && std::isfinite(md[4 + c]))) return "categorical target: prior sds must be finite and > 0";
+    for (int64_t i = 0; i < n; ++i) {
+        const double y = md[4 + D + i];
+        if (!(y >= 0.0 && y < Kd && y == std::floor(y))) return "categorical target: every label y must be an integer in [0, K)";
+    }
+    for (int64_t t = 0; t < n * p; ++t)
+        if (!std::isfinite(md[4 + D + n + t])) return "categorical target: X must be finite";
     *D_out = (int)D;
     return "";
 }
@@ -645,6 +682,15 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             }
             break;
         }
+        case SMCN_MODEL_CATEGORICAL: {
+            const std::string why = cat_check(model_data, model_data_len, &c->D);
+            if (!why.empty()) {
+                g_create_error = "smcn_ctx_create: " + why;
+                delete c;
+                return -1;
+            }
+            break;
+        }
         default:
             g_create_error = "smcn_ctx_create: unknown model id";
             delete c;
@@ -728,6 +774,22 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             row[DP] = y;
             row[DP + 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
             row[DP + 2] = model_data[head + n + i];
+        }
+    }
+    // categorical: GlmModel's table with the row width from the Dc columns and the label in the y slot, [1 (intercept),
+    // X_i1 .. X_ip, 0 .. (to an even count), y_i, 0] (GlmCatModel)
+    if (model_id == SMCN_MODEL_CATEGORICAL) {
+        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
+        const int64_t D = c->D;
+        const int RS = glm_row_doubles((int)(p + ic));
+        const int64_t t0 = glm_table_offset(D, n, p), rows = glm_table_rows(n);
+        mup.assign(t0 + rows * RS, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            if (ic) row[0] = 1.0;
+            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + D + n + i * p + j];
+            row[RS - 2] = model_data[4 + D + i];
         }
     }
     const int64_t mlen = (int64_t)mup.size();

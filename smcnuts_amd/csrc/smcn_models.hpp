@@ -916,4 +916,201 @@ struct GlmHierModel {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Categorical (multinomial logistic) regression, class 0 the reference (SMCN_MODEL_CATEGORICAL): K classes, Dc = p +
+// intercept columns,
+//   eta_i0 = 0, eta_ik = [b_k0 +] X_i b_k (k = 1..K-1),   log p(y_i) = eta_{i,y_i} - logsumexp(0, eta_i1, .., eta_i,K-1)
+//   b_kj ~ N(0, s_c^2) with c = (k - 1) Dc + j;  x = (b_1,1..b_1,Dc, .., b_K-1,Dc) class-major, D = (K - 1) Dc <= 64.
+// The table is GlmModel's (glm_table_offset(D, ..), row width from Dc) with the label in the y slot.  Per observation:
+//   m = max(0, eta_ik), S = sum of e^(eta_ik - m) over every class but the (first) one that attains m -- it contributes
+//   exactly 1 and stays out of S, so nothing cancels -- lse = m + log1p(S), term = (eta_{i,y_i} - m) - log1p(S), and
+//   the residuals d_ik = [y_i = k] - e^(eta_ik - m) / (1 + S).  Non-finite: -inf once a logit is not finite.
+// The K - 1 logits and residuals of a row are arrays with compile-time indices (guards and selects; c -> (k, j) depends
+// on the runtime Dc, and a private array indexed at run time would be placed in scratch).
+//   G = 8 (D <= 8): coordinate c on lane c; lane lg evaluates observations lg, lg + 8, ..  (K - 1) Dc <= 8 leaves 20
+//                   (k, j) pairs that can ever be a coordinate (j < 8 / (k + 1)): the coefficients and the gradient
+//                   partials are held by pair, and reduce-scattered over the group at the end.
+//   G = 64 (D <= 64): one wavefront per particle, coordinate c on lane c, lane l on row k0 + l of each 64-row chunk as
+//                   GlmModel<64, 1>.  Lane c needs the residual of ITS class k(c) for every row of the chunk: the chunk's
+//                   residuals are staged in LDS, [row][class] at a stride of 15 doubles (odd: the writes of one class
+//                   by the 64 lanes fall in distinct banks), and lane c reads d_{i,k(c)} beside X_{i,j(c)} -- one LDS
+//                   read per row, where reading the K - 1 residuals out as scalars and selecting costs K - 1 (DESIGN.md
+//                   4.4).  A wavefront's area is 64 x 15 doubles (7.5 KB); SHARED holds the four of a 256-lane block.
+// ---------------------------------------------------------------------------
+constexpr int kCatMaxClasses = 16;
+
+template <int G_, int DL_>
+struct GlmCatModel {
+    static_assert((G_ == 8 || G_ == 64) && DL_ == 1, "GlmCatModel: 8 or 64 lanes per particle, one coordinate per lane");
+    static constexpr int KM = G_ == 64 ? kCatMaxClasses - 1 : 8;   // non-reference classes the shape holds
+    static constexpr int STRIDE = kCatMaxClasses - 1;              // (G = 64) LDS doubles per staged row
+    static constexpr int WAVE_AREA = 64 * STRIDE;
+    static constexpr int G = G_, DL = DL_, SHARED = G_ == 64 ? 4 * WAVE_AREA : 0, MIN_WAVES = 2, LDS_LEVELS = 2;
+    static constexpr bool DIST = true;
+    static constexpr int NPAIR = 20;                               // (G = 8) the (k, j) pairs with j < 8 / (k + 1)
+    using d2 = double __attribute__((ext_vector_type(2)));
+    using ldsp = __attribute__((address_space(3))) double*;
+    int lg, D, Dc, Km1, DP, RS, n;
+    int kc, jc;                   // the lane's coordinate: class block (0-based) and column
+    const double* T;              // the repacked table
+    ldsp stage;                   // (G = 64) this wavefront's residual area
+    double inv_s2, lc;            // 1 / s_c^2 and -log s_c - log(2 pi) / 2 of the lane's coordinate (0 beyond D)
+
+    // first pair of class block k in the G = 8 pair arrays: 0, 8, 12, 14, 16, 17, 18, 19
+    static constexpr int pair0(int k) { return k == 0 ? 0 : pair0(k - 1) + 8 / k; }
+
+    __device__ int dim() const { return D; }
+    __device__ void init(const double* md, int lg_, double* shared) {
+        lg = lg_;
+        Km1 = (int)md[0] - 1;
+        n = (int)md[1];
+        const int p = (int)md[2];
+        Dc = p + (int)md[3];
+        D = Km1 * Dc;
+        DP = (Dc + 1) & ~1;
+        RS = glm_row_doubles(Dc);
+        T = md + glm_table_offset(D, n, p);
+        kc = lg < D ? lg / Dc : 0;
+        jc = lg < D ? lg - kc * Dc : 0;
+        const double s = lg < D ? md[4 + lg] : 1.0;
+        inv_s2 = lg < D ? 1.0 / (s * s) : 0.0;
+        lc = lg < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
+        stage = G_ == 64 ? (ldsp)shared + (threadIdx.x >> 6) * WAVE_AREA : (ldsp)shared;
+    }
+    // one row's softmax from its K - 1 logits: log-likelihood term, and e^(eta_k - m) / (1 + S) in place of the logits
+    __device__ __forceinline__ double softmax(double (&e)[KM], int y) const {
+        double m = 0.0, ey = 0.0;
+        int ks = 0;
+#pragma unroll
+        for (int k = 0; k < KM; ++k) {
+            if (k < Km1) {
+                const bool gt = e[k] > m;
+                m = gt ? e[k] : m;
+                ks = gt ? k + 1 : ks;
+                ey = y == k + 1 ? e[k] : ey;
+            }
+        }
+        // (exp_fast is exact at 0 -- the maximum's own 1 -- and flushes below -800; a NaN stays NaN)
+        auto ex = [](double a) { return exp_fast(a < -800.0 ? -800.0 : a); };
+        double S = ks == 0 ? 0.0 : ex(-m);
+#pragma unroll
+        for (int k = 0; k < KM; ++k) {
+            if (k < Km1) {
+                e[k] = ex(e[k] - m);
+                S += ks == k + 1 ? 0.0 : e[k];
+            }
+        }
+        double inv;
+        const double l1 = log1p_pos(S, inv);
+#pragma unroll
+        for (int k = 0; k < KM; ++k)
+            if (k < Km1) e[k] *= inv;
+        return (ey - m) - l1;
+    }
+    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
+        gp[0] = -x[0] * inv_s2;
+        const double lp = fma(-0.5 * x[0], x[0] * inv_s2, lc);
+        double ll = 0.0;
+        if constexpr (G_ == 64) {
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            const double xb = lg < D ? x[0] : 0.0;
+            for (int k0 = 0; k0 < n; k0 += 64) {
+                const d2* const row = (const d2*)(T + (int64_t)(k0 + lg) * RS);
+                double e[KM];
+#pragma unroll
+                for (int k = 0; k < KM; ++k) e[k] = 0.0;
+                for (int j = 0; j < DP; j += 2) {              // (j wave-uniform: the coefficients are scalar operands)
+                    const d2 v = row[j >> 1];
+                    const bool pad = j + 1 >= Dc;              // (the pad column's 0 times the next class's coefficient)
+#pragma unroll
+                    for (int k = 0; k < KM; ++k) {
+                        if (k < Km1) {
+                            const double b1 = group_read<64>(xb, k * Dc + j + 1);
+                            e[k] = fma(group_read<64>(xb, k * Dc + j), v.x, e[k]);
+                            e[k] = fma(pad ? 0.0 : b1, v.y, e[k]);
+                        }
+                    }
+                }
+                const int y = (int)row[DP >> 1].x;
+                const double term = softmax(e, y);
+                const bool live = k0 + lg < n;
+                ll += live ? term : 0.0;
+                // the chunk's residuals to LDS, [row][class]; lane c then reads its class's for each of the 64 rows
+#pragma unroll
+                for (int k = 0; k < KM; ++k)
+                    if (k < Km1) stage[lg * STRIDE + k] = live ? (y == k + 1 ? 1.0 : 0.0) - e[k] : 0.0;
+                wave_exchange_fence();
+                const double* const colp = T + (int64_t)k0 * RS + jc;
+                const ldsp dp = stage + kc;
+#pragma unroll 16
+                for (int i = 0; i < 64; ++i) acc[i & 3] = fma(dp[i * STRIDE], colp[(int64_t)i * RS], acc[i & 3]);
+                wave_exchange_fence();                         // (the next chunk's writes after these reads)
+            }
+            gl[0] = lg < D ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.0;
+            double L, P, u0, u1;
+            wave_sum4(ll, lp, 0.0, 0.0, L, P, u0, u1);
+            llik = finite_d(L) ? L : -kInf;
+            lpri = P;
+        } else {
+            // ---- 1. the coefficients to every lane of the group, by (class block, column) pair
+            double b[NPAIR], acc[NPAIR];
+#pragma unroll
+            for (int k = 0; k < KM; ++k) {
+#pragma unroll
+                for (int j = 0; j < 8 / (k + 1); ++j) {
+                    b[pair0(k) + j] = (k < Km1 && j < Dc) ? group_read<G>(x[0], k * Dc + j) : 0.0;
+                    acc[pair0(k) + j] = 0.0;
+                }
+            }
+            // ---- 2. this lane's observations lg, lg + G, ..
+            const int S = (n + G - 1) / G;
+#pragma unroll 1
+            for (int s = 0; s < S; ++s) {
+                const int i = lg + G * s;
+                const double* const row = T + (int64_t)i * RS;
+                double e[KM];
+#pragma unroll
+                for (int k = 0; k < KM; ++k) {
+                    e[k] = 0.0;
+                    if (k < Km1) {
+#pragma unroll
+                        for (int j = 0; j < 8 / (k + 1); ++j)
+                            if (j < Dc) e[k] = fma(b[pair0(k) + j], row[j], e[k]);
+                    }
+                }
+                const int y = (int)row[DP];
+                const double term = softmax(e, y);
+                const bool live = i < n;
+                ll += live ? term : 0.0;
+                // (the row again, from the cache)
+#pragma unroll
+                for (int k = 0; k < KM; ++k) {
+                    if (k < Km1) {
+                        const double d = live ? (y == k + 1 ? 1.0 : 0.0) - e[k] : 0.0;
+#pragma unroll
+                        for (int j = 0; j < 8 / (k + 1); ++j)
+                            if (j < Dc) acc[pair0(k) + j] = fma(d, row[j], acc[pair0(k) + j]);
+                    }
+                }
+            }
+            // ---- 3. reduce-scatter of the gradient partials: lane (k Dc + j) ends with the sum of its pair
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < KM; ++k) {
+#pragma unroll
+                for (int j = 0; j < 8 / (k + 1); ++j) {
+                    if (k < Km1 && j < Dc) {
+                        const double t = group_sum<G>(acc[pair0(k) + j]);
+                        v = lg == k * Dc + j ? t : v;
+                    }
+                }
+            }
+            gl[0] = lg < D ? v : 0.0;
+            const double L = group_sum<G>(ll);
+            llik = finite_d(L) ? L : -kInf;
+            lpri = group_sum<G>(lp);
+        }
+    }
+};
+
 }  // namespace smcn

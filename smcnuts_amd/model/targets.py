@@ -402,6 +402,82 @@ class HierarchicalGLM(DeviceTarget):
         super().__init__(data, D, names)
 
 
+CAT_MAX_CLASSES = 16
+
+
+class CategoricalRegression(DeviceTarget):
+    """Categorical (multinomial logistic) regression on the device, Stan's categorical_logit with class 0 the
+    reference: y_i in {0, .., K-1},
+      eta_i0 = 0,  eta_ik = [b_k0 +] X_i b_k  (k = 1..K-1),  log p(y_i) = eta_{i,y_i} - logsumexp_k eta_ik,
+      b_kj ~ N(0, prior_sd_kj^2).
+    x = (b_1,1..b_1,Dc, b_2,1.., .., b_K-1,Dc) class-major, Dc = p + intercept, D = (K - 1) Dc <= 64 and K <= 16
+    (larger models: HostTarget).  n_classes defaults to max(y) + 1; classes without observations are allowed.
+    prior_sd: a scalar, one value per column (Dc, shared by the classes) or a (K - 1, Dc) array.  constrain() is the
+    identity.
+
+    Data block (include/smcnuts_hip.h, SMCN_MODEL_CATEGORICAL): [K, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p,
+    row-major)]."""
+    model_id = _capi.MODEL_CATEGORICAL
+
+    def __init__(self, X, y, n_classes=None, prior_sd=2.5, intercept=True):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2:
+            raise ValueError("CategoricalRegression: X must be an (n, p) matrix")
+        n, p = X.shape
+        if n < 1:
+            raise ValueError("CategoricalRegression: at least one observation")
+        y = np.asarray(y)
+        if y.ndim != 1 or y.shape[0] != n:
+            raise ValueError(f"CategoricalRegression: y must be a vector of the n = {n} observations X has rows for")
+        if y.dtype == bool or not (np.issubdtype(y.dtype, np.integer) or np.issubdtype(y.dtype, np.floating)):
+            raise ValueError("CategoricalRegression: the labels y must be integers")
+        yf = y.astype(np.float64)
+        if not np.all(np.isfinite(yf) & (yf == np.floor(yf))):
+            raise ValueError("CategoricalRegression: the labels y must be integers")
+        if np.any(yf < 0):
+            raise ValueError("CategoricalRegression: the labels y must be >= 0")
+        K = int(yf.max()) + 1 if n_classes is None else n_classes
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
+            raise ValueError("CategoricalRegression: n_classes must be an integer")
+        K = int(K)
+        if K < 2:
+            raise ValueError("CategoricalRegression: K = n_classes must be >= 2 (one class has no likelihood)")
+        if K > CAT_MAX_CLASSES:
+            raise ValueError(f"CategoricalRegression: K = {K} classes; the device functor holds K <= {CAT_MAX_CLASSES}. "
+                             "Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
+        if yf.max() >= K:
+            raise ValueError(f"CategoricalRegression: the labels y must be in 0..n_classes - 1 = {K - 1}")
+        ic = 1 if intercept else 0
+        Dc = p + ic
+        if Dc < 1:
+            raise ValueError("CategoricalRegression: no coefficients (p = 0 without an intercept)")
+        D = (K - 1) * Dc
+        if D > GLM_MAX_DIM:
+            raise ValueError(f"CategoricalRegression: D = (K - 1) Dc = {K - 1} x {Dc} = {D} coefficients; the device "
+                             f"functor covers D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad "
+                             "in HostTarget instead.")
+        if not np.all(np.isfinite(X)):
+            raise ValueError("CategoricalRegression: X must be finite")
+        s = np.asarray(prior_sd, dtype=np.float64)
+        if s.ndim == 0:
+            s = np.full((K - 1, Dc), float(s))
+        elif s.shape == (Dc,):
+            s = np.tile(s, (K - 1, 1))
+        if s.shape != (K - 1, Dc):
+            raise ValueError(f"CategoricalRegression: prior_sd must be a scalar, one value per column ({Dc}) or a "
+                             f"(K - 1, Dc) = ({K - 1}, {Dc}) array")
+        if not np.all(np.isfinite(s) & (s > 0.0)):
+            raise ValueError("CategoricalRegression: prior_sd must be finite and > 0")
+        self.intercept, self.n_classes = bool(intercept), K
+        self.X, self.y, self.prior_sd = X.copy(), yf.astype(np.int64), s.copy()
+        data = np.concatenate([[float(K), float(n), float(p), float(ic)], s.reshape(-1), yf, X.reshape(-1)])
+        names = [name for k in range(1, K)
+                 for name in (([f"Intercept.{k}"] if ic else []) + [f"beta.{k}.{j + 1}" for j in range(p)])]
+        super().__init__(data, D, names)
+
+
 def LogisticRegression(X, y, prior_sd=2.5, intercept=True):
     """Bayesian logistic regression: GLMTarget(X, y, family="bernoulli_logit", ...)."""
     return GLMTarget(X, y, family="bernoulli_logit", prior_sd=prior_sd, intercept=intercept)

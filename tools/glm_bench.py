@@ -2,7 +2,7 @@
 per case.
 
     python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096] [--families normal,neg_binomial_2_log]
-                              [--models glm,hier]
+                              [--models glm,hier,cat]
 
 GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
 (1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)}, poisson_log at (1 000, 25), and normal and neg_binomial_2_log
@@ -16,6 +16,8 @@ density of tests/_glm.py / tests/_glm_disp.py.
 Hierarchical cases (varying intercepts, D = Dc + J + 1 (+ 1)): bernoulli_logit with n = 1 000, Dc = 5, J = 20 and
 normal with n = 1 000, Dc = 3, J = 50, the same way; the logistic one also against HostTarget with tests/_hglm.py's
 numpy density.  Their flop count is 4 n (Dc + 1) per leapfrog (eta's fixed part and its gradient, plus the group term).
+Categorical cases (CategoricalRegression, D = (K - 1) Dc): (K, n, Dc) in {(3, 100, 4), (5, 1 000, 6), (16, 1 000, 4)},
+the (5, 1 000, 6) one also against HostTarget with tests/_cat.py's numpy density; flop count 4 n D per leapfrog.
 """
 import argparse
 import json
@@ -40,6 +42,9 @@ HOST_CASES = (("bernoulli_logit", 1000, 25), ("normal", 1000, 25), ("neg_binomia
 # hierarchical: (family, n, Dc, J)
 HIER_CASES = [("bernoulli_logit", 1000, 5, 20), ("normal", 1000, 3, 50)]
 HIER_HOST_CASES = (("bernoulli_logit", 1000, 5, 20),)
+# categorical: (classes K, n, Dc); D = (K - 1) Dc: 8 (the 8-lane shape), 24, 60
+CAT_CASES = [(3, 100, 4), (5, 1000, 6), (16, 1000, 4)]
+CAT_HOST_CASES = ((5, 1000, 6),)
 
 
 def pick_step(target, N, seed):
@@ -80,7 +85,8 @@ def main():
     ap.add_argument("--host-N", type=int, default=4096)
     ap.add_argument("--host-K", type=int, default=3)
     ap.add_argument("--families", default=None, help="comma-separated subset of the families (default: all)")
-    ap.add_argument("--models", default="glm,hier", help="glm (GLMTarget cases), hier (HierarchicalGLM cases), or both")
+    ap.add_argument("--models", default="glm,hier,cat",
+                    help="comma-separated: glm (GLMTarget cases), hier (HierarchicalGLM cases), cat (CategoricalRegression)")
     a = ap.parse_args()
     models = set(a.models.split(","))
     import _glm
@@ -114,6 +120,8 @@ def main():
                                   speedup=host["run_s"] / dev["run_s"])), flush=True)
     if "hier" in models:
         hier(a, fams)
+    if "cat" in models:
+        cat(a)
 
 
 def hier(a, fams):
@@ -139,6 +147,29 @@ def hier(a, fams):
             dev = run(t, a.host_N, a.host_K, eps, 8)
             host = run(host_model(), a.host_N, a.host_K, eps, 8)
             print(json.dumps(dict(case=f"hier_{family}_n{n}_Dc{Dc}_J{J}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
+                                  device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
+                                  speedup=host["run_s"] / dev["run_s"])), flush=True)
+
+
+def cat(a):
+    import _cat
+    from smcnuts_amd import CategoricalRegression
+    for K, n, Dc in CAT_CASES:
+        D = (K - 1) * Dc
+        X, y = _cat.synthetic(K, n, Dc - 1, 3000 + D, scale=0.5)
+        t = CategoricalRegression(X, y, n_classes=K, prior_sd=2.0)
+        host_model = lambda: _cat.CategoricalNumpy(X, y, n_classes=K, prior_sd=2.0)
+        eps, pilot = pick_step(t, a.N, 5)
+        run(t, a.N, 2, eps, 6)
+        r = run(t, a.N, a.K, eps, 7)
+        r.update(case=f"cat_K{K}_n{n}_Dc{Dc}", K_classes=K, n=n, Dc=Dc, D=D, N=a.N, K=a.K, step_size=eps,
+                 pilot_nleap=pilot, fp64_tflops=4.0 * n * D * r["leapfrog_per_s"] / 1e12)
+        r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
+        print(json.dumps(r), flush=True)
+        if (K, n, Dc) in CAT_HOST_CASES:
+            dev = run(t, a.host_N, a.host_K, eps, 8)
+            host = run(host_model(), a.host_N, a.host_K, eps, 8)
+            print(json.dumps(dict(case=f"cat_K{K}_n{n}_Dc{Dc}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
                                   device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
                                   speedup=host["run_s"] / dev["run_s"])), flush=True)
 
