@@ -50,6 +50,12 @@ typedef struct smcn_ctx smcn_ctx;
                               log p(y_i) = eta_{i,y_i} - logsumexp_k eta_ik, b_c ~ N(0, s_c^2);
                               x = (b_1,1..b_1,Dc, .., b_K-1,1..b_K-1,Dc) class-major, D = (K - 1) Dc <= 64;
                               constrain is the identity */
+#define SMCN_MODEL_ORDINAL 7   /* ordinal (ordered-logistic) regression, no intercept: data = [K, n, p, s_1..s_p, t_1..t_{K-1},
+                              y_1..y_n (labels in 0..K-1), X (n x p, row-major)], K >= 2, p >= 0; eta_i = X_i b,
+                              cutpoints c_1 = u_1, c_k = c_{k-1} + e^u_k, P(y_i = k) = logit^-1(eta_i - c_k) -
+                              logit^-1(eta_i - c_{k+1}) (c_0 = -inf, c_K = +inf), b_j ~ N(0, s_j^2), c_k ~ N(0, t_k^2) with
+                              the log-Jacobian sum_{k>=2} u_k; x = (b_1..b_p, u_1..u_{K-1}), D = p + K - 1 <= 64;
+                              constrain reports (b, c_1..c_{K-1}) */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

@@ -10,4 +10,4 @@ on this path and no CPU fallback.
 from .smc_sampler import SMCSampler  # noqa: F401
 from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GLMTarget, HierarchicalGLM,  # noqa: F401
                             HostTarget, IsoGaussian, LinearRegression, LogisticRegression, NegativeBinomialRegression,
-                            PoissonRegression, PRMwCDModel, StanModel)
+                            OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel)

@@ -92,7 +92,7 @@ struct smcn_ctx {
     int64_t stage_len = 0;
     double* stage2 = nullptr;
     int64_t stage2_len = 0;
-    double* cstage = nullptr;   // SMCN_MODEL_HGLM: the constrained population the moment kernels read ([ngen][D][N])
+    double* cstage = nullptr;   // SMCN_MODEL_HGLM / ORDINAL: the constrained population the moment kernels read ([ngen][D][N])
     int64_t cstage_len = 0;
     int32_t *nleap = nullptr, *depth = nullptr, *ndraws = nullptr, *flags = nullptr;
     int64_t* idx = nullptr;
@@ -431,6 +431,11 @@ static int with_model(smcn_ctx* c, F&& f) {
         if (c->D <= 8) return f(GlmCatModel<8, 1>{});
         return f(GlmCatModel<64, 1>{});
     }
+    if (c->model == SMCN_MODEL_ORDINAL) {
+        // (checked at creation: K >= 2, D = p + K - 1 <= 64)
+        if (c->D <= 8) return f(GlmOrdModel<8, 1>{});
+        return f(GlmOrdModel<64, 1>{});
+    }
     if (c->model == SMCN_MODEL_HOST) FAIL(c, "host target: this entry point needs a device-native model");
     FAIL(c, "model not available in this build");
 }
@@ -572,6 +577,34 @@ static std::string cat_check(const double* md, int64_t len, int* D_out) {
     return "";
 }
 
+// SMCN_MODEL_ORDINAL: checks the caller's data block; "" and D, or what is wrong with it
+static std::string ord_check(const double* md, int64_t len, int* D_out) {
+    const char* layout = "ordinal target: data = [K, n, p, s_1..s_p, t_1..t_{K-1}, y_1..y_n, X (n x p, row-major)], "
+                         "D = p + K - 1";
+    if (len < 3) return layout;
+    const double Kd = md[0], nd = md[1], pd = md[2];
+    if (!(Kd >= 2.0 && Kd == std::floor(Kd))) return "ordinal target: K must be an integer >= 2";
+    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd)) return "ordinal target: n must be an integer >= 1";
+    if (!(pd >= 0.0 && pd == std::floor(pd))) return "ordinal target: p must be an integer >= 0";
+    if (pd + Kd - 1.0 > 64.0)
+        return "ordinal target: the device functor covers D = p + K - 1 <= 64 coordinates; larger models run "
+               "host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
+               "HostTarget)";
+    const int64_t n = (int64_t)nd, p = (int64_t)pd, D = p + (int64_t)Kd - 1;
+    if (len != 3 + D + n + n * p) return layout;
+    for (int64_t c = 0; c < D; ++c)
+        if (!(md[3 + c] > 0.0 && std::isfinite(md[3 + c])))
+            return "ordinal target: prior sds (s for the coefficients, t for the cutpoints) must be finite and > 0";
+    for (int64_t i = 0; i < n; ++i) {
+        const double y = md[3 + D + i];
+        if (!(y >= 0.0 && y < Kd && y == std::floor(y))) return "ordinal target: every label y must be an integer in [0, K)";
+    }
+    for (int64_t t = 0; t < n * p; ++t)
+        if (!std::isfinite(md[3 + D + n + t])) return "ordinal target: X must be finite";
+    *D_out = (int)D;
+    return "";
+}
+
 extern "C" {
 
 int smcn_version(void) { return 1; }
@@ -691,6 +724,15 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             }
             break;
         }
+        case SMCN_MODEL_ORDINAL: {
+            const std::string why = ord_check(model_data, model_data_len, &c->D);
+            if (!why.empty()) {
+                g_create_error = "smcn_ctx_create: " + why;
+                delete c;
+                return -1;
+            }
+            break;
+        }
         default:
             g_create_error = "smcn_ctx_create: unknown model id";
             delete c;
@@ -700,9 +742,9 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
     // constrain_coord applies to arma's log sigma (the other models keep their own id)
     c->cmodel = (model_id == SMCN_MODEL_GLM && model_data[0] >= 2.0) ? SMCN_MODEL_ARMA : model_id;
-    // hierarchical GLM: its constrained space is not coordinate-wise; the moment kernels read a constrained copy of the
-    // population (hglm_constrained) with the identity
-    if (model_id == SMCN_MODEL_HGLM) c->cmodel = SMCN_MODEL_HOST;
+    // hierarchical GLM, ordinal: the constrained space is not coordinate-wise; the moment kernels read a constrained copy
+    // of the population (model_constrained) with the identity
+    if (model_id == SMCN_MODEL_HGLM || model_id == SMCN_MODEL_ORDINAL) c->cmodel = SMCN_MODEL_HOST;
     auto fail = [&](const char* what, hipError_t er) {
         g_create_error = std::string("smcn_ctx_create: ") + what + ": " + hipGetErrorString(er);
         free_all(c);
@@ -790,6 +832,23 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
             if (ic) row[0] = 1.0;
             for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + D + n + i * p + j];
             row[RS - 2] = model_data[4 + D + i];
+        }
+    }
+    // ordinal: GlmModel's table with the row width from the p columns and the label in the y slot, [X_i1 .. X_ip, 0 .. (to
+    // an even count), y_i, 0], then the K class counts n_0..n_{K-1} (GlmOrdModel)
+    if (model_id == SMCN_MODEL_ORDINAL) {
+        const int64_t K = (int64_t)model_data[0], n = (int64_t)model_data[1], p = (int64_t)model_data[2];
+        const int64_t D = c->D;
+        const int RS = glm_row_doubles((int)p);
+        const int64_t t0 = glm_table_offset(D, n, p), c0 = ord_counts_offset(D, n, p);
+        mup.assign(c0 + K, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            for (int64_t j = 0; j < p; ++j) row[j] = model_data[3 + D + n + i * p + j];
+            const double y = model_data[3 + D + i];
+            row[RS - 2] = y;
+            mup[c0 + (int64_t)y] += 1.0;
         }
     }
     const int64_t mlen = (int64_t)mup.size();
@@ -941,9 +1000,21 @@ static int ensure_stage2(smcn_ctx* c, int64_t n) {
     c->stage2_len = n;
     return 0;
 }
-// SMCN_MODEL_HGLM: the constrained population of ngen consecutive generations ([ngen][D][N] from x) into c->cstage, on
-// the context's stream; *out is what the moment kernels then read with the identity (c->cmodel)
-static int hglm_constrained(smcn_ctx* c, const double* x, int ngen, const double** out) {
+// models whose constrained space is not coordinate-wise: the moment kernels read a constrained copy of the population
+static bool has_constrain_pass(const smcn_ctx* c) { return c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_ORDINAL; }
+// their constrain pass over M particles, particle t's coordinate c at x[(t / Np) * Np * D + (t % Np) * si + c * sc]
+static void launch_constrain_pass(smcn_ctx* c, const double* x, double* out, int64_t M, int64_t Np, int64_t si,
+                                  int64_t sc) {
+    if (c->model == SMCN_MODEL_ORDINAL)
+        ord_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D, (int)c->mdata_h[2], si, sc);
+    else
+        hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D,
+                                                                       (int)c->mdata_h[2] + (int)c->mdata_h[3],
+                                                                       (int)c->mdata_h[4], si, sc);
+}
+// SMCN_MODEL_HGLM / SMCN_MODEL_ORDINAL: the constrained population of ngen consecutive generations ([ngen][D][N] from x)
+// into c->cstage, on the context's stream; *out is what the moment kernels then read with the identity (c->cmodel)
+static int model_constrained(smcn_ctx* c, const double* x, int ngen, const double** out) {
     const int64_t M = (int64_t)ngen * c->N, n = M * c->D;
     if (n > c->cstage_len) {
         if (c->cstage) (void)cached_free(c->cstage);
@@ -951,8 +1022,7 @@ static int hglm_constrained(smcn_ctx* c, const double* x, int ngen, const double
         HIPC(c, dalloc(&c->cstage, n));
         c->cstage_len = n;
     }
-    const int Dc = (int)c->mdata_h[2] + (int)c->mdata_h[3], J = (int)c->mdata_h[4];
-    hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, c->cstage, M, c->N, c->D, Dc, J, 1, c->N);
+    launch_constrain_pass(c, x, c->cstage, M, c->N, 1, c->N);
     HIPC(c, hipGetLastError());
     *out = c->cstage;
     return 0;
@@ -1140,10 +1210,8 @@ int smcn_target_constrain(smcn_ctx* c, const double* x, int64_t M, double* out) 
     if (rc) return rc;
     if ((rc = ensure_stage2(c, n))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    if (c->model == SMCN_MODEL_HGLM)
-        hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, M, c->D,
-                                                                       (int)c->mdata_h[2] + (int)c->mdata_h[3],
-                                                                       (int)c->mdata_h[4], c->D, 1);
+    if (has_constrain_pass(c))
+        launch_constrain_pass(c, c->stage, c->stage2, M, M, c->D, 1);
     else
         constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->cmodel);
     HIPC(c, hipGetLastError());
@@ -1384,8 +1452,8 @@ int smcn_moment_sums(smcn_ctx* c, const double* mean, double* sums) {
         HIPC(c, hipMemcpyAsync(dmean, mean, sizeof(double) * c->Dc, hipMemcpyHostToDevice, c->stream));
     }
     const double* xs = c->x;
-    if (c->model == SMCN_MODEL_HGLM) {
-        const int rc = hglm_constrained(c, c->x, 1, &xs);
+    if (has_constrain_pass(c)) {
+        const int rc = model_constrained(c, c->x, 1, &xs);
         if (rc) return rc;
     }
     moment_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(xs, c->wn, c->N, c->D, c->cmodel, dmean, c->part);
@@ -2401,8 +2469,8 @@ static int enqueue_partials(smcn_ctx* c, const double* logw, const double* x, do
     const int NQB = gen_block_nq(c->Dc);   // block partials: [max, cnt, s1, s2, A.., B.., reference point..]
     while ((int64_t)g * NQB * ngen > (int64_t)kMaxPart * (4 * c->D * c->D + 2 * c->D + 8) && g > 1) g /= 2;
     const int nz = c->D >= 64 ? 8 : 1;
-    if (c->model == SMCN_MODEL_HGLM) {
-        const int rc = hglm_constrained(c, x, ngen, &x);
+    if (has_constrain_pass(c)) {
+        const int rc = model_constrained(c, x, ngen, &x);
         if (rc) return rc;
     }
     gen_partials_kernel<<<dim3(g, ngen, nz), kRedBlock, 0, c->stream>>>(logw, x, N, c->D, c->cmodel, c->part, N,

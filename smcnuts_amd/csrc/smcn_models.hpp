@@ -1113,4 +1113,229 @@ struct GlmCatModel {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Ordinal (ordered-logistic) regression (SMCN_MODEL_ORDINAL): K >= 2 classes, p >= 0 columns, no intercept, eta_i = X_i b,
+// cutpoints c_1 < .. < c_{K-1} from Stan's `ordered` transform of u: c_1 = u_1, c_k = c_{k-1} + e^u_k,
+//   P(y_i = k) = logit^-1(eta_i - c_k) - logit^-1(eta_i - c_{k+1})   (c_0 = -inf, c_K = +inf),
+//   b_j ~ N(0, s_j^2), c_k ~ N(0, t_k^2), with the log-Jacobian sum_{k>=2} u_k;  x = (b_1..b_p, u_1..u_{K-1}), D <= 64.
+// In the stable form, with delta_k = c_{k+1} - c_k = e^u_{k+1} (sigma(a) - sigma(b) = sigma(a) sigma(-b) (1 - e^-(a-b))),
+//   log P(y_i = k) = -softplus(c_k - eta_i) [k >= 1] - softplus(eta_i - c_{k+1}) [k <= K-2] + log(1 - e^-delta_k) [middle k].
+// The last term depends on the parameters only: its sum over observations is n_k log(1 - e^-delta_k), with the class
+// counts n_k that smcn_ctx_create stores behind the table, formed from u on the cutpoint lane of u_{k+1} (= u there for
+// u < -36, where e^u is below the rounding of 1; finite for every finite u), gradient n_k delta_k / expm1(delta_k).
+// The two softplus terms are GlmModel's logistic pattern (exp_fast(-|a|), log1p_pos, the sigmoid from the same
+// exponential).  Gradients: d/d eta = sigma(c_k - eta) - sigma(eta - c_{k+1}); -sigma(c_k - eta) to the lower cutpoint,
+// +sigma(eta - c_{k+1}) to the upper one; the chain to u takes suffix sums over the cutpoint lanes, g_u1 = sum_j g_cj and
+// g_um = e^u_m sum_{j>=m} g_cj, for the likelihood and for the cutpoint prior alike (the Jacobian adds 1 to g_um, m >= 2).
+// The table is GlmModel's with the row width from p and the label in the y slot, [X_i1 .. X_ip, 0 (to an even count),
+// y_i, 0]; the K class counts follow it (ord_counts_offset).  Non-finite: lpri = llik = -inf once a cutpoint is not finite
+// (e^u_m overflows), llik = -inf once an eta_i is not finite.  The cutpoints are the sequential running sum, as
+// `constrain` forms them.
+//   G = 8 (D <= 8): coordinate c on lane c; every lane gathers the coefficients and the increments and forms the
+//                   cutpoints itself, and picks c_y and c_{y+1} of its rows by compile-time selects; the gradient partials
+//                   are held by coordinate slot (column j < p, cutpoint p + m - 1), reduce-scattered over the group.
+//   G = 64 (D <= 64): one wavefront per particle, coordinate c on lane c, lane l on row k0 + l of each 64-row chunk as
+//                   GlmModel<64, 1>.  The row owner fetches c_y and c_{y+1} with cross-lane reads (as GlmHierModel
+//                   fetches z_{g_i}).  In the read-out a cutpoint lane compares the row's label, read out as a scalar,
+//                   with its own index (GlmHierModel's group indicator) and takes the row's lower or upper partial:
+//                   GlmCatModel's LDS staging would need a K-slot row per observation (up to 65 doubles) to let a lane
+//                   read its own slot, where the compare costs a few VALU operations and no LDS.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline int64_t ord_counts_offset(int64_t D, int64_t n, int64_t p) {
+    return glm_table_offset(D, n, p) + glm_table_rows(n) * glm_row_doubles((int)p);
+}
+// sum of v over lanes lg .. G - 1 of the group (Kogge-Stone)
+template <int G>
+__device__ __forceinline__ double group_suffix_sum(double v, int lg) {
+    v += group_shift_down<G, 1>(v, lg);
+    v += group_shift_down<G, 2>(v, lg);
+    v += group_shift_down<G, 4>(v, lg);
+    if constexpr (G >= 16) v += group_shift_down<G, 8>(v, lg);
+    if constexpr (G >= 32) v += group_shift_down<G, 16>(v, lg);
+    if constexpr (G >= 64) v += group_shift_down<G, 32>(v, lg);
+    return v;
+}
+
+template <int G_, int DL_>
+struct GlmOrdModel {
+    static_assert((G_ == 8 || G_ == 64) && DL_ == 1, "GlmOrdModel: 8 or 64 lanes per particle, one coordinate per lane");
+    static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
+    static constexpr bool DIST = true;
+    using d2 = double __attribute__((ext_vector_type(2)));
+    int lg, D, p, Km1, DP, RS, n;
+    int mc;                       // the lane's cutpoint index m (coordinate p + m - 1), -1 on the other lanes
+    const double* T;              // the repacked table
+    double inv_s2, lc;            // 1 / s^2 and -log s - log(2 pi) / 2 of the lane's coordinate's prior (0 beyond D)
+    double cnt;                   // (lanes of u_m, m >= 2) n_{m-1}, the count of the middle class below c_m
+
+    __device__ int dim() const { return D; }
+    __device__ void init(const double* md, int lg_, double*) {
+        lg = lg_;
+        Km1 = (int)md[0] - 1;
+        n = (int)md[1];
+        p = (int)md[2];
+        D = p + Km1;
+        DP = (p + 1) & ~1;
+        RS = glm_row_doubles(p);
+        T = md + glm_table_offset(D, n, p);
+        mc = (lg >= p && lg < D) ? lg - p + 1 : -1;
+        const double s = lg < D ? md[3 + lg] : 1.0;
+        inv_s2 = lg < D ? 1.0 / (s * s) : 0.0;
+        lc = lg < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
+        cnt = mc >= 2 ? md[ord_counts_offset(D, n, p) + mc - 1] : 0.0;
+    }
+    // one observation with label y, lo = c_y (y >= 1) and hi = c_{y+1} (y <= K - 2): log-likelihood term, d / d eta, and
+    // the partials of the lower and the upper cutpoint
+    __device__ __forceinline__ void obs(double eta, int y, double lo, double hi, double& term, double& de, double& glo,
+                                        double& ghi) const {
+        const bool hl = y >= 1, hh = y < Km1;
+        const double a1 = lo - eta, a2 = eta - hi;
+        // (exp_fast flushes below -800; a NaN stays NaN)
+        auto ex = [](double a) { return exp_fast(a < -800.0 ? -800.0 : a); };
+        const double t1 = ex(-fabs(a1)), t2 = ex(-fabs(a2));
+        double i1, i2;
+        const double sp1 = fmax(a1, 0.0) + log1p_pos(t1, i1);   // softplus(a1); i1 = sigmoid(|a1|)
+        const double sp2 = fmax(a2, 0.0) + log1p_pos(t2, i2);
+        const double s1 = a1 >= 0.0 ? i1 : t1 * i1, s2 = a2 >= 0.0 ? i2 : t2 * i2;
+        term = -((hl ? sp1 : 0.0) + (hh ? sp2 : 0.0));
+        term = finite_d(eta) ? term : -kInf;
+        glo = hl ? -s1 : 0.0;
+        ghi = hh ? s2 : 0.0;
+        de = -(glo + ghi);
+    }
+    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
+        const double u = x[0];
+        const bool isc = mc >= 1;
+        const double ev = mc >= 2 ? exp(u) : u;            // (cutpoint lanes) c_m - c_{m-1}, or c_1
+        // ---- the cutpoints: c_m on the lane of u_m, c_{K-1} everywhere
+        double cut = 0.0, cK = 0.0;
+        double ll = 0.0, gx, gc;
+        if constexpr (G_ == 64) {
+#pragma unroll 1
+            for (int j = 0; j < Km1; ++j) {
+                cK += group_read<64>(ev, p + j);
+                cut = lg == p + j ? cK : cut;
+            }
+            // ---- observations, 64 a chunk
+            double ax[4] = {0.0, 0.0, 0.0, 0.0}, ac[2] = {0.0, 0.0};
+            const int col = lg < p ? lg : 0;
+            const double xb = lg < p ? u : 0.0;            // (0 on the pad column)
+            for (int k0 = 0; k0 < n; k0 += 64) {
+                const d2* const row = (const d2*)(T + (int64_t)(k0 + lg) * RS);
+                double e0 = 0.0, e1 = 0.0;
+                for (int j = 0; j < DP; j += 2) {          // (j wave-uniform: the coefficients are scalar operands)
+                    const d2 v = row[j >> 1];
+                    e0 = fma(group_read<64>(xb, j), v.x, e0);
+                    e1 = fma(group_read<64>(xb, j + 1), v.y, e1);
+                }
+                const int y = (int)row[DP >> 1].x;
+                const double lo = __shfl(cut, p + (y >= 1 ? y - 1 : 0), 64);
+                const double hi = __shfl(cut, p + (y < Km1 ? y : Km1 - 1), 64);
+                double term, de, glo, ghi;
+                obs(e0 + e1, y, lo, hi, term, de, glo, ghi);
+                const bool live = k0 + lg < n;
+                ll += live ? term : 0.0;
+                de = live ? de : 0.0;
+                glo = live ? glo : 0.0;
+                ghi = live ? ghi : 0.0;
+                // the chunk's 64 rows read out as scalars: column `lg` weighted by d / d eta, or the row's cutpoint partial
+                // when its label puts this lane's cutpoint below (y = m) or above (y = m - 1) it
+                const double* const colp = T + (int64_t)k0 * RS + col;
+#pragma unroll 16
+                for (int i = 0; i < 64; ++i) {
+                    const int yi = __builtin_amdgcn_readlane(y, i);
+                    ax[i & 3] = fma(lane_value(de, i), colp[(int64_t)i * RS], ax[i & 3]);
+                    ac[i & 1] += mc == yi ? lane_value(glo, i) : (mc == yi + 1 ? lane_value(ghi, i) : 0.0);
+                }
+            }
+            gx = (ax[0] + ax[1]) + (ax[2] + ax[3]);
+            gc = ac[0] + ac[1];
+        } else {
+            // ---- 1. the coefficients and the increments to every lane of the group; the cutpoints, by coordinate slot
+            double b[8], cs[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const double w = j < D ? group_read<G>(ev, j) : 0.0;
+                b[j] = j < p ? w : 0.0;
+                cK += (j >= p && j < D) ? w : 0.0;
+                cs[j] = cK;
+                cut = lg == j ? cK : cut;
+            }
+            // ---- 2. this lane's observations lg, lg + G, ..: gradient partials by slot, column j < p or cutpoint p + m - 1
+            double acc[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] = 0.0;
+            const int S = (n + G - 1) / G;
+#pragma unroll 1
+            for (int s = 0; s < S; ++s) {
+                const int i = lg + G * s;
+                const double* const row = T + (int64_t)i * RS;
+                double e = 0.0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j < p) e = fma(b[j], row[j], e);   // (p wave-uniform)
+                const int y = (int)row[DP];
+                double lo = 0.0, hi = 0.0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    lo = j == p + y - 1 ? cs[j] : lo;
+                    hi = j == p + y ? cs[j] : hi;
+                }
+                double term, de, glo, ghi;
+                obs(e, y, lo, hi, term, de, glo, ghi);
+                const bool live = i < n;
+                ll += live ? term : 0.0;
+                de = live ? de : 0.0;
+                glo = live ? glo : 0.0;
+                ghi = live ? ghi : 0.0;
+                // (the row again, from the cache)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    if (j < p) acc[j] = fma(de, row[j], acc[j]);
+                    else if (j < D) acc[j] += j == p + y - 1 ? glo : (j == p + y ? ghi : 0.0);
+                }
+            }
+            // ---- 3. reduce-scatter of the partials: lane c ends with the sum of slot c
+            double v = 0.0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (j < D) {
+                    const double t = group_sum<G>(acc[j]);
+                    v = lg == j ? t : v;
+                }
+            }
+            gx = v;
+            gc = v;
+        }
+        // ---- priors: b_j, or c_m with the log-Jacobian u_m (m >= 2)
+        const double pv = isc ? cut : u;
+        const double pg = -pv * inv_s2;                    // d lpri / d b_j, or d lpri / d c_m
+        const double lp = fma(-0.5 * pv, pv * inv_s2, lc) + (mc >= 2 ? u : 0.0);
+        // ---- the middle classes' n_k log(1 - e^-delta_k), delta_k = e^u_{k+1}, on the lane of u_{k+1}
+        double cg = 0.0;
+        if (cnt > 0.0) {
+            const bool tiny = u < -36.0;                   // e^u < 2.4e-16: log(1 - e^-e^u) = u, e^u / expm1(e^u) = 1
+            ll += cnt * (tiny ? u : log(-expm1(-ev)));
+            cg = cnt * (tiny ? 1.0 : ev / expm1(ev));
+        }
+        // ---- the chain to u: suffix sums over the cutpoint lanes, times dc_j / du_m (1 for m = 1, e^u_m above)
+        const double sl = group_suffix_sum<G>(isc ? gc : 0.0, lg);
+        const double sp = group_suffix_sum<G>(isc ? pg : 0.0, lg);
+        const double dm = mc >= 2 ? ev : 1.0;
+        gl[0] = lg < p ? gx : (isc ? fma(dm, sl, cg) : 0.0);
+        gp[0] = lg < p ? pg : (isc ? fma(dm, sp, mc >= 2 ? 1.0 : 0.0) : 0.0);
+        double L, P;
+        if constexpr (G_ == 64) {
+            double u0, u1;
+            wave_sum4(ll, lp, 0.0, 0.0, L, P, u0, u1);
+        } else {
+            L = group_sum<G>(ll);
+            P = group_sum<G>(lp);
+        }
+        const bool bad = !finite_d(cK);                    // a cutpoint is not finite
+        llik = bad ? -kInf : (finite_d(L) ? L : -kInf);
+        lpri = bad ? -kInf : P;
+    }
+};
+
 }  // namespace smcn

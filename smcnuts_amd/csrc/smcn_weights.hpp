@@ -128,6 +128,20 @@ __global__ void hglm_constrain_kernel(const double* x, double* out, int64_t M, i
         out[base + (int64_t)c * sc] = c < Dc ? v : (c < Dc + J ? tau * v : exp(v));
     }
 }
+// constrain() of the ordinal regression (SMCN_MODEL_ORDINAL): (b, u_1..u_{K-1}) -> (b, c_1..c_{K-1}), c_1 = u_1,
+// c_k = c_{k-1} + e^u_k -- the running sum GlmOrdModel forms, in the same order.  Addressing as hglm_constrain_kernel's.
+__global__ void ord_constrain_kernel(const double* x, double* out, int64_t M, int64_t Np, int D, int p, int64_t si,
+                                     int64_t sc) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    const int64_t base = (t / Np) * Np * D + (t % Np) * si;
+    double s = 0.0;
+    for (int c = 0; c < D; ++c) {
+        const double v = x[base + (int64_t)c * sc];
+        s += c < p ? 0.0 : (c == p ? v : exp(v));
+        out[base + (int64_t)c * sc] = c < p ? v : s;
+    }
+}
 
 // ---- transposes between host [N][D] and device [D][N] ------------------------
 __global__ void transpose_kernel(const double* in, double* out, int64_t rows, int64_t cols) {

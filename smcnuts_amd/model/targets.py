@@ -478,6 +478,76 @@ class CategoricalRegression(DeviceTarget):
         super().__init__(data, D, names)
 
 
+class OrdinalRegression(DeviceTarget):
+    """Ordinal (ordered-logistic) regression on the device, Stan's ordered_logistic with y shifted to 0..K-1:
+      eta_i = X_i b (no intercept: the cutpoints take its place),
+      P(y_i = k) = logit^-1(eta_i - c_k) - logit^-1(eta_i - c_{k+1})  (c_0 = -inf, c_K = +inf),
+      b_j ~ N(0, prior_sd_j^2),  c_k ~ N(0, cutpoint_prior_sd_k^2)  (the ordering's normalising constant left out).
+    The cutpoints c_1 < .. < c_{K-1} are sampled through Stan's `ordered` transform, c_1 = u_1, c_k = c_{k-1} + e^u_k,
+    with its log-Jacobian sum_{k>=2} u_k: x = (b_1..b_p, u_1..u_{K-1}), D = p + K - 1 <= 64 (larger models: HostTarget).
+    n_classes defaults to max(y) + 1; classes without observations are allowed.  prior_sd: a scalar or one value per
+    column; cutpoint_prior_sd: a scalar or one value per cutpoint.  `constrain` reports (b, c_1..c_{K-1}).
+
+    Data block (include/smcnuts_hip.h, SMCN_MODEL_ORDINAL): [K, n, p, s_1..s_p, t_1..t_{K-1}, y_1..y_n, X (n x p,
+    row-major)]."""
+    model_id = _capi.MODEL_ORDINAL
+
+    def __init__(self, X, y, n_classes=None, prior_sd=2.5, cutpoint_prior_sd=5.0):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2:
+            raise ValueError("OrdinalRegression: X must be an (n, p) matrix")
+        n, p = X.shape
+        if n < 1:
+            raise ValueError("OrdinalRegression: at least one observation")
+        y = np.asarray(y)
+        if y.ndim != 1 or y.shape[0] != n:
+            raise ValueError(f"OrdinalRegression: y must be a vector of the n = {n} observations X has rows for")
+        if y.dtype == bool or not (np.issubdtype(y.dtype, np.integer) or np.issubdtype(y.dtype, np.floating)):
+            raise ValueError("OrdinalRegression: the labels y must be integers")
+        yf = y.astype(np.float64)
+        if not np.all(np.isfinite(yf) & (yf == np.floor(yf))):
+            raise ValueError("OrdinalRegression: the labels y must be integers")
+        if np.any(yf < 0):
+            raise ValueError("OrdinalRegression: the labels y must be >= 0")
+        K = int(yf.max()) + 1 if n_classes is None else n_classes
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
+            raise ValueError("OrdinalRegression: n_classes must be an integer")
+        K = int(K)
+        if K < 2:
+            raise ValueError("OrdinalRegression: K = n_classes must be >= 2 (one class has no likelihood)")
+        if yf.max() >= K:
+            raise ValueError(f"OrdinalRegression: the labels y must be in 0..n_classes - 1 = {K - 1}")
+        D = p + K - 1
+        if D > GLM_MAX_DIM:
+            raise ValueError(f"OrdinalRegression: D = p + K - 1 = {p} + {K - 1} = {D} coordinates; the device functor "
+                             f"covers D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad in "
+                             "HostTarget instead.")
+        if not np.all(np.isfinite(X)):
+            raise ValueError("OrdinalRegression: X must be finite")
+        s = np.asarray(prior_sd, dtype=np.float64)
+        if s.ndim == 0:
+            s = np.full(p, float(s))
+        if s.shape != (p,):
+            raise ValueError(f"OrdinalRegression: prior_sd must be a scalar or one value per column ({p})")
+        if not np.all(np.isfinite(s) & (s > 0.0)):
+            raise ValueError("OrdinalRegression: prior_sd must be finite and > 0")
+        t = np.asarray(cutpoint_prior_sd, dtype=np.float64)
+        if t.ndim == 0:
+            t = np.full(K - 1, float(t))
+        if t.shape != (K - 1,):
+            raise ValueError(f"OrdinalRegression: cutpoint_prior_sd must be a scalar or one value per cutpoint "
+                             f"(K - 1 = {K - 1})")
+        if not np.all(np.isfinite(t) & (t > 0.0)):
+            raise ValueError("OrdinalRegression: cutpoint_prior_sd must be finite and > 0")
+        self.n_classes = K
+        self.X, self.y, self.prior_sd, self.cutpoint_prior_sd = X.copy(), yf.astype(np.int64), s.copy(), t.copy()
+        data = np.concatenate([[float(K), float(n), float(p)], s, t, yf, X.reshape(-1)])
+        names = [f"beta.{j + 1}" for j in range(p)] + [f"cutpoint.{k}" for k in range(1, K)]
+        super().__init__(data, D, names)
+
+
 def LogisticRegression(X, y, prior_sd=2.5, intercept=True):
     """Bayesian logistic regression: GLMTarget(X, y, family="bernoulli_logit", ...)."""
     return GLMTarget(X, y, family="bernoulli_logit", prior_sd=prior_sd, intercept=intercept)

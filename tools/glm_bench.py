@@ -1,8 +1,8 @@
-"""GLM targets (GLMTarget, SMCN_MODEL_GLM; HierarchicalGLM, SMCN_MODEL_HGLM) throughput on one MI355X: one JSON line
-per case.
+"""GLM targets (GLMTarget, SMCN_MODEL_GLM; HierarchicalGLM, SMCN_MODEL_HGLM; CategoricalRegression;
+OrdinalRegression) throughput on one MI355X: one JSON line per case.
 
     python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096] [--families normal,neg_binomial_2_log]
-                              [--models glm,hier,cat]
+                              [--models glm,hier,cat,ord]
 
 GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
 (1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)}, poisson_log at (1 000, 25), and normal and neg_binomial_2_log
@@ -18,6 +18,8 @@ normal with n = 1 000, Dc = 3, J = 50, the same way; the logistic one also again
 numpy density.  Their flop count is 4 n (Dc + 1) per leapfrog (eta's fixed part and its gradient, plus the group term).
 Categorical cases (CategoricalRegression, D = (K - 1) Dc): (K, n, Dc) in {(3, 100, 4), (5, 1 000, 6), (16, 1 000, 4)},
 the (5, 1 000, 6) one also against HostTarget with tests/_cat.py's numpy density; flop count 4 n D per leapfrog.
+Ordinal cases (OrdinalRegression, D = p + K - 1): (K, n, p) in {(5, 100, 3), (5, 1 000, 20), (10, 1 000, 40)}, the
+(5, 1 000, 20) one also against HostTarget with tests/_ord.py's numpy density; flop count 4 n p per leapfrog.
 """
 import argparse
 import json
@@ -45,6 +47,9 @@ HIER_HOST_CASES = (("bernoulli_logit", 1000, 5, 20),)
 # categorical: (classes K, n, Dc); D = (K - 1) Dc: 8 (the 8-lane shape), 24, 60
 CAT_CASES = [(3, 100, 4), (5, 1000, 6), (16, 1000, 4)]
 CAT_HOST_CASES = ((5, 1000, 6),)
+# ordinal: (classes K, n, p); D = p + K - 1: 7 (the 8-lane shape), 24, 49
+ORD_CASES = [(5, 100, 3), (5, 1000, 20), (10, 1000, 40)]
+ORD_HOST_CASES = ((5, 1000, 20),)
 
 
 def pick_step(target, N, seed):
@@ -85,8 +90,9 @@ def main():
     ap.add_argument("--host-N", type=int, default=4096)
     ap.add_argument("--host-K", type=int, default=3)
     ap.add_argument("--families", default=None, help="comma-separated subset of the families (default: all)")
-    ap.add_argument("--models", default="glm,hier,cat",
-                    help="comma-separated: glm (GLMTarget cases), hier (HierarchicalGLM cases), cat (CategoricalRegression)")
+    ap.add_argument("--models", default="glm,hier,cat,ord",
+                    help="comma-separated: glm (GLMTarget cases), hier (HierarchicalGLM cases), cat (CategoricalRegression), "
+                         "ord (OrdinalRegression)")
     a = ap.parse_args()
     models = set(a.models.split(","))
     import _glm
@@ -122,6 +128,8 @@ def main():
         hier(a, fams)
     if "cat" in models:
         cat(a)
+    if "ord" in models:
+        ordinal(a)
 
 
 def hier(a, fams):
@@ -170,6 +178,29 @@ def cat(a):
             dev = run(t, a.host_N, a.host_K, eps, 8)
             host = run(host_model(), a.host_N, a.host_K, eps, 8)
             print(json.dumps(dict(case=f"cat_K{K}_n{n}_Dc{Dc}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
+                                  device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
+                                  speedup=host["run_s"] / dev["run_s"])), flush=True)
+
+
+def ordinal(a):
+    import _ord
+    from smcnuts_amd import OrdinalRegression
+    for K, n, p in ORD_CASES:
+        D = p + K - 1
+        X, y = _ord.synthetic(K, n, p, 4000 + D, scale=0.5)
+        t = OrdinalRegression(X, y, n_classes=K, prior_sd=2.0, cutpoint_prior_sd=5.0)
+        host_model = lambda: _ord.OrdinalNumpy(X, y, n_classes=K, prior_sd=2.0, cutpoint_prior_sd=5.0)
+        eps, pilot = pick_step(t, a.N, 5)
+        run(t, a.N, 2, eps, 6)
+        r = run(t, a.N, a.K, eps, 7)
+        r.update(case=f"ord_K{K}_n{n}_p{p}", K_classes=K, n=n, p=p, D=D, N=a.N, K=a.K, step_size=eps,
+                 pilot_nleap=pilot, fp64_tflops=4.0 * n * p * r["leapfrog_per_s"] / 1e12)
+        r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
+        print(json.dumps(r), flush=True)
+        if (K, n, p) in ORD_HOST_CASES:
+            dev = run(t, a.host_N, a.host_K, eps, 8)
+            host = run(host_model(), a.host_N, a.host_K, eps, 8)
+            print(json.dumps(dict(case=f"ord_K{K}_n{n}_p{p}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
                                   device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
                                   speedup=host["run_s"] / dev["run_s"])), flush=True)
 
