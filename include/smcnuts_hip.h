@@ -453,6 +453,48 @@ int smcn_gres_finish(smcn_ctx* ctx, int world, const double* loglik /* NULL: the
  * state, timed with HIP events on the context's stream (bench.py's roofline entry for resampling). */
 int smcn_bench_resample(smcn_ctx* ctx, int reps, int64_t iteration, double* ms_total);
 
+/* ---- pointwise log-likelihood and predictive criteria (SMCN_MODEL_GLM, all four families, D <= 64, any n) ----
+ * ll[p][i] = log p(y_i | x_p), the per-observation term exactly as the density forms it (sum_i ll[p][i] is the llik of
+ * smcn_target_eval; the -lgamma(y + 1) constants included), finite or -inf.  Contexts of every other model fail with a
+ * message (smcn_last_error) that says so.
+ *
+ * smcn_pointwise_dims: n and the column count Q (= 11) of a partials block.
+ * smcn_pointwise_loglik: ll as [M][n] row-major for M caller-supplied points x[M][D] (the plain form, for problems small
+ * enough to hold the matrix).
+ * smcn_pointwise_partials: the weighted reductions OVER PARTICLES per observation, without the matrix, as MERGEABLE
+ * partials out[1 + n][Q].  x == NULL: the resident particles with their resident log-weights (M must equal the context's N,
+ * logw must be NULL; nothing is uploaded); x != NULL with logw == NULL: equal weights.  Log-weights are unnormalised.  A
+ * particle with a non-finite log-weight contributes to nothing, whatever its terms are; the others are "contributing".
+ * Row 0 (header): [mw, sw, sw2, cnt, 0 ..] = the largest contributing log-weight (-inf: none), sum exp(lw - mw),
+ * sum exp(2 (lw - mw)), the number of contributing particles.  Row 1 + i, observation i, with lw' = lw - mw, w = exp(lw')
+ * and every sum over the contributing particles whose term ll is finite:
+ *   0 ma    max (lw' + ll)                  (-inf: no such particle)
+ *   1 Sa    sum exp(lw' + ll - ma)          lppd_i = ma + log Sa - log sw
+ *   2 mb    max (lw' - ll)
+ *   3 Sb    sum exp(lw' - ll - mb)          elpd_loo_i = -(mb + log Sb - log sw)
+ *   4 Sb2   sum exp(2 (lw' - ll - mb))      loo_ess_i = Sb^2 / Sb2
+ *   5 c     the first such particle's ll    (NaN: none) -- the shift of the two moments, inside the range of the terms
+ *   6 SW    sum w
+ *   7 S1    sum w (ll - c)                  mean_loglik_i = c + S1 / SW
+ *   8 S2    sum w (ll - c)^2                p_waic_i = S2 / SW - (S1 / SW)^2  (never sum w ll^2 - mean^2)
+ *   9 F     sum w E[y_i | x_p]              fitted_i = F / SW  (sigmoid(eta), e^eta, eta, e^eta for families 0..3)
+ *  10 ninf  contributing particles with ll = -inf
+ * Rules of the finished values (smcnuts_amd.criteria.combine_pointwise_partials): an observation with ninf > 0 has
+ * lppd_i as defined (those particles add 0), mean_loglik_i = elpd_loo_i = -inf, loo_ess_i = 0 and p_waic_i, elpd_waic_i,
+ * fitted_i NaN; all other observations are unaffected.  Every log-sum-exp is taken around its running maximum.
+ * Merging two blocks (disjoint particle sets, in order): headers and the pairs (ma, Sa), (mb, Sb, Sb2) merge as max-shifted
+ * sums after adding mw_k - max(mw) to ma / mb and scaling SW, S1, S2, F by exp(mw_k - max(mw)); the moments are re-centred
+ * on the first block's c (d = c_2 - c: S1 += S1_2 + d SW_2, S2 += S2_2 + 2 d S1_2 + d^2 SW_2); ninf adds.  The result of one
+ * call does not depend on the order in which its blocks finish (no atomics; the particle slices of a call follow from M
+ * and n alone and are merged in slice order), so a repeated call returns identical bits.
+ * smcn_pointwise_last_ms: the device time of the last smcn_pointwise_partials' kernels (HIP events on the context's
+ * stream), for measurements. */
+int smcn_pointwise_dims(const smcn_ctx* ctx, int64_t* n_obs, int* n_cols);
+int smcn_pointwise_loglik(smcn_ctx* ctx, const double* x /* [M][D] */, int64_t M, double* out /* [M][n] */);
+int smcn_pointwise_partials(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */,
+                            int64_t M, double* out /* [1 + n][Q] */);
+int smcn_pointwise_last_ms(const smcn_ctx* ctx, double* ms);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build. */

@@ -11,3 +11,4 @@ from .smc_sampler import SMCSampler  # noqa: F401
 from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GLMTarget, HierarchicalGLM,  # noqa: F401
                             HostTarget, IsoGaussian, LinearRegression, LogisticRegression, NegativeBinomialRegression,
                             OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel)
+from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F401

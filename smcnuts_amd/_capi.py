@@ -131,6 +131,10 @@ SIGNATURES = {
     "smcn_gres_reserve": ([_ctx, C.c_int64], C.c_int),
     "smcn_gres_serve": ([_ctx, C.c_int, C.c_int, C.c_int64], C.c_int),
     "smcn_gres_finish": ([_ctx, C.c_int, _dp], C.c_int),
+    "smcn_pointwise_dims": ([_ctx, _lp, C.POINTER(C.c_int)], C.c_int),
+    "smcn_pointwise_loglik": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_pointwise_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_pointwise_last_ms": ([_ctx, _dp], C.c_int),
 }
 
 _lib = None
@@ -347,6 +351,41 @@ class Context:
     def partials_set_gathered(self, g):
         g = np.ascontiguousarray(g, dtype=np.float64)
         self.call("smcn_partials_set_gathered", dptr(g), int(g.shape[0]))
+
+    # ---- pointwise criteria (SMCN_MODEL_GLM) -----------------------------------------
+    def pointwise_dims(self):
+        n, q = C.c_int64(0), C.c_int(0)
+        self.call("smcn_pointwise_dims", C.byref(n), C.byref(q))
+        return n.value, q.value
+
+    def pointwise_loglik(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        n, _ = self.pointwise_dims()
+        out = np.empty((x.shape[0], n))
+        self.call("smcn_pointwise_loglik", dptr(x), x.shape[0], dptr(out))
+        return out
+
+    def pointwise_partials(self, x=None, logw=None):
+        """[1 + n][Q] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
+        n, q = self.pointwise_dims()
+        out = np.empty((1 + n, q))
+        if x is None:
+            self.call("smcn_pointwise_partials", None, None, self.N, dptr(out))
+        else:
+            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+            if lw is not None and lw.shape != (x.shape[0],):
+                raise ValueError("logw must hold one log-weight per row of x")
+            self.call("smcn_pointwise_partials", dptr(x), dptr(lw), x.shape[0], dptr(out))
+        return out
+
+    def pointwise_last_ms(self):
+        """Device time of the last pointwise_partials' kernels (HIP events on the context's stream)."""
+        ms = C.c_double(0.0)
+        rc = self._lib.smcn_pointwise_last_ms(self._h, C.byref(ms))
+        if rc != 0:
+            raise SmcnError("smcn_pointwise_last_ms failed")
+        return ms.value
 
     def timers(self, reset=False):
         t = np.zeros(6)

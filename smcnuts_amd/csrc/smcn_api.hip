@@ -28,6 +28,7 @@
 #include "smcn_glk.hpp"
 #include "smcn_step.hpp"
 #include "smcn_comm.hpp"
+#include "smcn_pointwise.hpp"
 
 using namespace smcn;
 
@@ -163,6 +164,12 @@ struct smcn_ctx {
     int ev_n = 0;
     double nuts_ms = 0.0;
     int64_t nuts_launches = 0;
+
+    // pointwise criteria (smcn_pointwise_*): log-weights, slice partials and the result of a call; its kernels' time
+    double* pw_buf = nullptr;
+    int64_t pw_len = 0;
+    hipEvent_t pw_ev0 = nullptr, pw_ev1 = nullptr;
+    double pw_ms = 0.0;
 };
 
 #define CHECK_CTX(c)             \
@@ -642,10 +649,12 @@ static void free_all(smcn_ctx* c) {
                     c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
                     c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
                     c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage};
+                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf};
     if (c->rows_h) (void)hipHostFree(c->rows_h);
     if (c->hist_h) (void)hipHostFree(c->hist_h);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
+    if (c->pw_ev0) (void)hipEventDestroy(c->pw_ev0);
+    if (c->pw_ev1) (void)hipEventDestroy(c->pw_ev1);
     // ONE wait for everything this context has in flight (its own stream, the history stream); the buffers below were
     // used by these streams only
     if (c->stream) (void)stream_wait(c->stream);
@@ -3298,6 +3307,143 @@ int smcn_selftest_wide(smcn_ctx* c, int lanes, const double* x, int64_t n, doubl
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(out, c->stage2, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- pointwise log-likelihood and its reductions over particles (smcn_pointwise.hpp) ------------------------------------
+static const char* kPwScope =
+    "pointwise criteria cover the SMCN_MODEL_GLM families (bernoulli_logit, poisson_log, normal, neg_binomial_2_log) "
+    "only; hierarchical, categorical, ordinal, arma, PRMwCD, Gaussian and host-evaluated targets are not implemented";
+
+static PwArgs pw_args(const smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
+    PwArgs a;
+    a.md = c->mdata;
+    a.x = x;
+    a.rs = rs;
+    a.cs = cs;
+    a.M = M;
+    a.cps = cps;
+    a.fam = (int)c->mdata_h[0];
+    a.n = (int)c->mdata_h[1];
+    a.p = (int)c->mdata_h[2];
+    a.Dc = a.p + (int)c->mdata_h[3];
+    return a;
+}
+static int pw_ensure(smcn_ctx* c, int64_t n) {
+    if (n <= c->pw_len) return 0;
+    if (c->pw_buf) (void)cached_free(c->pw_buf);
+    c->pw_buf = nullptr;
+    c->pw_len = 0;
+    HIPC(c, dalloc(&c->pw_buf, n));
+    c->pw_len = n;
+    return 0;
+}
+// f(row capacity, dispersion family) for the context's model: rows of DP <= 16 / 32 / 64 doubles
+template <class F>
+static void pw_dispatch(const PwArgs& a, F&& f) {
+    const int DP = (a.Dc + 1) & ~1;
+    const auto fam = [&](auto dp) { a.fam >= 2 ? f(dp, std::true_type{}) : f(dp, std::false_type{}); };
+    if (DP <= 16) fam(std::integral_constant<int, 16>{});
+    else if (DP <= 32) fam(std::integral_constant<int, 32>{});
+    else fam(std::integral_constant<int, 64>{});
+}
+
+extern "C" {
+
+int smcn_pointwise_dims(const smcn_ctx* cc, int64_t* n_obs, int* n_cols) {
+    smcn_ctx* c = const_cast<smcn_ctx*>(cc);
+    if (!c) return -1;
+    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_dims: ") + kPwScope);
+    if (n_obs) *n_obs = (int64_t)c->mdata_h[1];
+    if (n_cols) *n_cols = kPwCols;
+    return 0;
+}
+
+int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
+    CHECK_CTX(c);
+    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_loglik: ") + kPwScope);
+    if (!x || !out || M < 1) FAIL(c, "smcn_pointwise_loglik: bad arguments");
+    const int64_t n = (int64_t)c->mdata_h[1], tiles = (n + 63) / 64;
+    int64_t cps = 1;
+    const int64_t slices = pointwise_slices(M, n, &cps);
+    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_pointwise_loglik: too many observations");
+    int rc = ensure_stage(c, M * c->D);
+    if (rc) return rc;
+    if ((rc = pw_ensure(c, M * n))) return rc;
+    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+    const PwArgs a = pw_args(c, c->stage, c->D, 1, M, cps);
+    pw_dispatch(a, [&](auto dp, auto disp) {
+        pointwise_loglik_kernel<decltype(dp)::value, decltype(disp)::value>
+            <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, c->pw_buf);
+    });
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, c->pw_buf, sizeof(double) * M * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
+int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
+    CHECK_CTX(c);
+    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_partials: ") + kPwScope);
+    if (!out || M < 1) FAIL(c, "smcn_pointwise_partials: bad arguments");
+    if (!x && (M != c->N || logw)) FAIL(c, "smcn_pointwise_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
+    const int64_t n = (int64_t)c->mdata_h[1], tiles = (n + 63) / 64, npad = tiles * 64;
+    int64_t cps = 1;
+    const int64_t slices = pointwise_slices(M, n, &cps);
+    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_pointwise_partials: too many observations");
+    // pw_buf: [header 16 | lw M | slice partials | group partials | result (1 + n) Q]
+    const int64_t groups = (slices + kPwGroup - 1) / kPwGroup;
+    const int64_t o_lw = 16, o_part = o_lw + (M + 15) / 16 * 16, o_grp = o_part + slices * kPwCols * npad;
+    const int64_t o_out = o_grp + groups * kPwCols * npad;
+    int rc = pw_ensure(c, o_out + (1 + n) * kPwCols);
+    if (rc) return rc;
+    double* const head = c->pw_buf;
+    double* lw = c->pw_buf + o_lw;
+    double* const part = c->pw_buf + o_part;
+    double* const grp = c->pw_buf + o_grp;
+    double* const res = c->pw_buf + o_out;
+    const double* xd = c->x;
+    int64_t rs = 1, cs = c->N;
+    if (x) {
+        if ((rc = ensure_stage(c, M * c->D))) return rc;
+        HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+        if (logw) HIPC(c, hipMemcpyAsync(lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        else HIPC(c, hipMemsetAsync(lw, 0, sizeof(double) * M, c->stream));
+        xd = c->stage;
+        rs = c->D;
+        cs = 1;
+    } else {
+        lw = c->logw;
+    }
+    if (!c->pw_ev0) {
+        HIPC(c, hipEventCreate(&c->pw_ev0));
+        HIPC(c, hipEventCreate(&c->pw_ev1));
+    }
+    const PwArgs a = pw_args(c, xd, rs, cs, M, cps);
+    HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
+    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
+    pw_dispatch(a, [&](auto dp, auto disp) {
+        pointwise_stats_kernel<decltype(dp)::value, decltype(disp)::value>
+            <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, lw, head, part);
+    });
+    // (groups <= 256 blocks in y: pointwise_slices keeps the slices near 4096)
+    pointwise_combine_kernel<false><<<dim3((unsigned)grid_for(n, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, n, npad, grp);
+    pointwise_combine_kernel<true><<<grid_for(n, 64), 64, 0, c->stream>>>(grp, head, groups, n, npad, res);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->pw_ev1, c->stream));
+    HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * (1 + n) * kPwCols, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
+    c->pw_ms = (double)ms;
+    return 0;
+}
+
+int smcn_pointwise_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    *ms = c->pw_ms;
     return 0;
 }
 

@@ -69,6 +69,18 @@ class DeviceTarget:
         c = self._context(x2.shape[0]).constrain(x2)
         return c[0] if x.ndim == 1 else c
 
+    # pointwise criteria (smcnuts_amd/criteria.py): GLMTarget only
+    def _no_pointwise(self):
+        raise NotImplementedError(
+            f"{type(self).__name__}: pointwise log-likelihood and the criteria built on it (WAIC, IS-LOO, fitted values) "
+            "are implemented for GLMTarget (bernoulli_logit, poisson_log, normal, neg_binomial_2_log) only")
+
+    def pointwise_loglik(self, x):
+        self._no_pointwise()
+
+    def pointwise(self, x, logw=None):
+        self._no_pointwise()
+
 
 class GaussianTarget(DeviceTarget):
     """prior N(0, prior_sd^2 I) x optional likelihood N(x | lik_mean 1, lik_sd^2 I)."""
@@ -128,6 +140,12 @@ class HostTarget:
     def constrain(self, x, **kw):
         f = getattr(self.target, "constrain", None)
         return f(x) if callable(f) else np.array(x, copy=True)
+
+    def pointwise_loglik(self, x):
+        DeviceTarget._no_pointwise(self)
+
+    def pointwise(self, x, logw=None):
+        DeviceTarget._no_pointwise(self)
 
     def attach(self, ctx):
         """Register the density callback with a context created for this target."""
@@ -294,6 +312,37 @@ class GLMTarget(DeviceTarget):
         if disp:
             names.append(GLM_DISPERSION[family])
         super().__init__(data, D, names)
+
+    _PW_CHUNK = 1 << 25          # doubles of ll the device holds at once (256 MB)
+
+    def _points(self, x):
+        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
+        if x2.ndim != 2 or x2.shape[1] != self.dim:
+            raise ValueError(f"GLMTarget: x must be [{self.dim}] or [M, {self.dim}]")
+        return x2
+
+    def pointwise_loglik(self, x):
+        """ll[p, i] = log p(y_i | x_p): [n] for a 1-D x, [M, n] for 2-D (sum over i: logpdf_parts(x)[1]).  The matrix is
+        formed on the device in slabs of particles; it has to fit on the host."""
+        x2 = self._points(x)
+        M, n = x2.shape[0], self.y.shape[0]
+        step = max(1, min(M, self._PW_CHUNK // n))
+        ctx = self._context(step)
+        out = np.empty((M, n))
+        for m0 in range(0, M, step):
+            out[m0:m0 + step] = ctx.pointwise_loglik(x2[m0:m0 + step])
+        return out[0] if np.ndim(x) == 1 else out
+
+    def pointwise_partials(self, x, logw=None):
+        """The mergeable partials of x's rows ([1 + n][Q], include/smcnuts_hip.h)."""
+        x2 = self._points(x)
+        return self._context(x2.shape[0]).pointwise_partials(x2, logw)
+
+    def pointwise(self, x, logw=None):
+        """Per-observation lppd, WAIC, IS-LOO and fitted values of the weighted points (x [M, D], logw unnormalised or None
+        for equal weights) -> criteria.Pointwise.  The matrix ll is never formed."""
+        from ..criteria import combine_pointwise_partials
+        return combine_pointwise_partials([self.pointwise_partials(x, logw)])
 
 
 class HierarchicalGLM(DeviceTarget):

@@ -129,6 +129,7 @@ class SMCSampler:
                                 and not getattr(target, "host_evaluated", False))
         self._fast_started = False
         self._host_loop_used = False
+        self._finalised = False          # finalise() / finalise_async() has run: pointwise() reads the final generation
         if save_history:
             # (measured and kept, profiles/r05_stall_trace.txt: this pageable copy is the call that stalls for 16-18 ms in the
             #  second sampler of a process, one run out of three -- but leaving generation 0 to the device history instead made
@@ -211,6 +212,7 @@ class SMCSampler:
         s.calculate_ess()
         self.update_sampler(self.K, mean, var, 0)   # x is x_new after the last commit: 0, as in the reference
         self.phi[self.K] = s.phi_new
+        self._finalised = True
         if self.lkernel == "asymptoticLKernel":     # smc_sampler.py:152-153
             if not self.save_history:
                 raise RuntimeError("asymptoticLKernel estimates need save_history=True")
@@ -314,6 +316,7 @@ class SMCSampler:
         self.mean_estimate[:] = hist[:, 6:6 + Dc]
         self.variance_estimate[:] = hist[:, 6 + Dc:6 + 2 * Dc]
         s.log_likelihood, s.ess = self.log_likelihood[K], self.ess[K]
+        self._finalised = True
         if self.save_history and download_history:
             self.x_saved, self.logw_saved = xs, lw
 
@@ -499,6 +502,30 @@ class SMCSampler:
         bar = getattr(self, "_bar", None)
         if bar is not None and self.k > bar.n:
             bar.update(self.k - bar.n)
+
+    def pointwise(self):
+        """Per-observation criteria (criteria.Pointwise: lppd, WAIC, IS-LOO, fitted values) of the final generation and its
+        weights, after sample() / finalise(): computed from the resident particles, nothing is downloaded but the
+        [1 + n][Q] partials.  Several shards: every rank computes its partials, ONE host all-gather moves them, every rank
+        combines them in rank order."""
+        from .criteria import combine_pointwise_partials
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError("pointwise(): the asymptotic L-kernel's estimates pool generations; criteria over the "
+                                      "pooled generations are not implemented")
+        if not hasattr(self.target, "pointwise_partials"):
+            self.target.pointwise(None)         # raises NotImplementedError naming the supported targets
+        if not self._finalised:
+            raise RuntimeError("pointwise(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"pointwise(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
+                               "target the posterior")
+        ctx = self.samples.ctx
+        ctx.call("smcn_synchronize")
+        part = ctx.pointwise_partials()
+        if self.comm.world_size > 1:
+            allp = np.asarray(self.comm.allgather(part.reshape(-1)))
+            return combine_pointwise_partials([p.reshape(part.shape) for p in allp])
+        return combine_pointwise_partials([part])
 
     def sample(self, show_progress=True):
         start_time = time()
