@@ -495,6 +495,53 @@ int smcn_pointwise_partials(smcn_ctx* ctx, const double* x_or_null /* [M][D] */,
                             int64_t M, double* out /* [1 + n][Q] */);
 int smcn_pointwise_last_ms(const smcn_ctx* ctx, double* ms);
 
+/* ---- held-out prediction at new rows (SMCN_MODEL_GLM, SMCN_MODEL_HGLM, SMCN_MODEL_CATEGORICAL, SMCN_MODEL_ORDINAL) ----
+ * Posterior predictive summaries at rows the model was not fitted to, and log p(y_new_i | x_p) when y_new is given.
+ * Contexts of every other model (arma, PRMwCD, Gaussian, host-evaluated) fail with a message that names these four.
+ *
+ * smcn_predict_set_data: the new rows, as the model's own data block WITHOUT the priors:
+ *   SMCN_MODEL_GLM          [family, m, p, intercept, y_1..y_m, X (m x p, row-major)]
+ *   SMCN_MODEL_HGLM         [family, m, p, intercept, J, y_1..y_m, g_1..g_m, X]     (g: existing groups 0..J-1 only)
+ *   SMCN_MODEL_CATEGORICAL  [K, m, p, intercept, y_1..y_m, X]
+ *   SMCN_MODEL_ORDINAL      [K, m, p, y_1..y_m, X]
+ * Every header entry but m must repeat the training block's.  has_y = 0: the y slots hold zeros and the lpd columns of
+ * the partials are meaningless (smcn_predict_loglik refuses).  The block is validated by the rules of smcn_ctx_create
+ * (finite X, labels in 0..K-1, y in {0, 1} / counts, g in 0..J-1) and repacked into the padded row table by the routine
+ * that repacks the training design.  The table is owned by the context and replaced by the next call.
+ * smcn_predict_dims: m, the column count Q of a partials block and has_y.
+ * smcn_predict_loglik: log p(y_new_i | x_p) as [M][m] row-major for M caller-supplied points (the plain form).  At the
+ * training rows its row sums are the llik of smcn_target_eval.
+ * smcn_predict_partials: MERGEABLE partials out[1 + m][Q]; x == NULL: the resident particles with their resident
+ * log-weights (M = N, logw = NULL), as smcn_pointwise_partials.  Row 0 is smcn_pointwise_partials' header
+ * [mw, sw, sw2, cnt, 0 ..].  Row 1 + i, new row i, with lw' = lw - mw, w = exp(lw'), over the contributing particles:
+ *   0 ma    max (lw' + ll) over finite ll      (-inf: none)
+ *   1 Sa    sum exp(lw' + ll - ma)             lpd_i = ma + log Sa - log sw
+ *   2 ninf  particles with ll = -inf (they add 0 to lpd_i)
+ *   3 nbad  particles with a non-finite predictive mean, variance or probability: the row's summaries are NaN
+ *  GLM families and hierarchical (Q = 9), sums over the particles that nbad does not count, mu_p = E[y_i | x_p]:
+ *   4 c     the first such mu_p (NaN: none)    the shift of the moments
+ *   5 SW    sum w
+ *   6 S1    sum w (mu_p - c)                   mean_i = c + S1 / SW
+ *   7 S2    sum w (mu_p - c)^2                 between-particle variance S2 / SW - (S1 / SW)^2 (never sum w mu^2 - mean^2)
+ *   8 V     sum w Var(y_i | x_p)               var_i = V / SW + the between-particle variance
+ *           (Var: p (1 - p), mu, sigma^2, mu + mu^2 / phi for families 0..3)
+ *  categorical (Q = 4 + K):
+ *   4 + k   sum w P(y_i = k | x_p), k = 0..K-1          prob[i][k] = that / sw
+ *  ordinal (Q = 5 + K for K <= 16, Q = 5 above):
+ *   4 EM    sum w sum_k sigma(eta_i - c_k)              mean_i (expected class index) = EM / sw
+ *   5 + k   sum w P(y_i = k | x_p)                      (K <= 16 only)
+ * Merging two blocks (disjoint particle sets, in order) follows smcn_pointwise_partials: headers and (ma, Sa) as
+ * max-shifted sums, the moments re-centred on the first block's c, every other column scaled by exp(mw_k - max(mw)) and
+ * added; ninf and nbad add unscaled.  The particle slices of a call follow from (M, m) alone and are merged in slice order
+ * (no atomics): a repeated call returns identical bits.
+ * smcn_predict_last_ms: the device time of the last smcn_predict_partials' kernels. */
+int smcn_predict_set_data(smcn_ctx* ctx, const double* block, int64_t len, int has_y);
+int smcn_predict_dims(smcn_ctx* ctx, int64_t* n_rows, int* n_cols, int* has_y);
+int smcn_predict_loglik(smcn_ctx* ctx, const double* x /* [M][D] */, int64_t M, double* out /* [M][m] */);
+int smcn_predict_partials(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */,
+                          int64_t M, double* out /* [1 + m][Q] */);
+int smcn_predict_last_ms(const smcn_ctx* ctx, double* ms);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build. */

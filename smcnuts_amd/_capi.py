@@ -135,6 +135,11 @@ SIGNATURES = {
     "smcn_pointwise_loglik": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
     "smcn_pointwise_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
     "smcn_pointwise_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_predict_set_data": ([_ctx, _dp, C.c_int64, C.c_int], C.c_int),
+    "smcn_predict_dims": ([_ctx, _lp, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "smcn_predict_loglik": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_predict_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_predict_last_ms": ([_ctx, _dp], C.c_int),
 }
 
 _lib = None
@@ -385,6 +390,46 @@ class Context:
         rc = self._lib.smcn_pointwise_last_ms(self._h, C.byref(ms))
         if rc != 0:
             raise SmcnError("smcn_pointwise_last_ms failed")
+        return ms.value
+
+    # ---- held-out prediction (GLM, hierarchical, categorical, ordinal) ----------------
+    def predict_set_data(self, block, has_y):
+        """The new rows as the model's data block without the priors (include/smcnuts_hip.h)."""
+        block = np.ascontiguousarray(block, dtype=np.float64)
+        self.call("smcn_predict_set_data", dptr(block), block.size, int(bool(has_y)))
+
+    def predict_dims(self):
+        m, q, hy = C.c_int64(0), C.c_int(0), C.c_int(0)
+        self.call("smcn_predict_dims", C.byref(m), C.byref(q), C.byref(hy))
+        return m.value, q.value, bool(hy.value)
+
+    def predict_loglik(self, x):
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        m, _, _ = self.predict_dims()
+        out = np.empty((x.shape[0], m))
+        self.call("smcn_predict_loglik", dptr(x), x.shape[0], dptr(out))
+        return out
+
+    def predict_partials(self, x=None, logw=None):
+        """[1 + m][Q] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
+        m, q, _ = self.predict_dims()
+        out = np.empty((1 + m, q))
+        if x is None:
+            self.call("smcn_predict_partials", None, None, self.N, dptr(out))
+        else:
+            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+            if lw is not None and lw.shape != (x.shape[0],):
+                raise ValueError("logw must hold one log-weight per row of x")
+            self.call("smcn_predict_partials", dptr(x), dptr(lw), x.shape[0], dptr(out))
+        return out
+
+    def predict_last_ms(self):
+        """Device time of the last predict_partials' kernels (HIP events on the context's stream)."""
+        ms = C.c_double(0.0)
+        rc = self._lib.smcn_predict_last_ms(self._h, C.byref(ms))
+        if rc != 0:
+            raise SmcnError("smcn_predict_last_ms failed")
         return ms.value
 
     def timers(self, reset=False):

@@ -29,6 +29,7 @@
 #include "smcn_step.hpp"
 #include "smcn_comm.hpp"
 #include "smcn_pointwise.hpp"
+#include "smcn_predict.hpp"
 
 using namespace smcn;
 
@@ -170,6 +171,13 @@ struct smcn_ctx {
     int64_t pw_len = 0;
     hipEvent_t pw_ev0 = nullptr, pw_ev1 = nullptr;
     double pw_ms = 0.0;
+
+    // held-out prediction (smcn_predict_*): the new rows' image [block | padding | table] as smcn_ctx_create lays out the
+    // training data, where its table starts, the number of new rows and whether they came with y
+    double* pr_md = nullptr;
+    int64_t pr_md_len = 0, pr_toff = 0, pr_m = 0;
+    int pr_has_y = 0;
+    double pr_ms = 0.0;
 };
 
 #define CHECK_CTX(c)             \
@@ -612,6 +620,85 @@ static std::string ord_check(const double* md, int64_t len, int* D_out) {
     return "";
 }
 
+// The table a GLM-type model's functor reads, behind the caller's data block: `mup` becomes [block | padding | table].
+// smcn_ctx_create repacks the training design with it, smcn_predict_set_data the new rows.
+static void repack_model_table(int model_id, int dim, const double* model_data, int64_t model_data_len,
+                               std::vector<double>& mup) {
+    // GLM: behind the caller's data the table GlmModel / GlmDispModel read (smcn_models.hpp) -- a row per observation,
+    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1)], at a 128-byte boundary, zero rows up to a
+    // multiple of 64 observations.  The row width follows the Dc coefficients; the dispersion families' block has m_tau
+    // and s_tau between the prior sds and y (HD: the doubles before y).
+    if (model_id == SMCN_MODEL_GLM) {
+        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
+        const int64_t Dc = p + ic, HD = model_data[0] >= 2.0 ? Dc + 2 : Dc;
+        const int RS = glm_row_doubles((int)Dc);
+        const int64_t t0 = glm_table_offset(HD, n, p), rows = glm_table_rows(n);
+        mup.assign(t0 + rows * RS, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            if (ic) row[0] = 1.0;
+            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + HD + n + i * p + j];
+            const double y = model_data[4 + HD + i];
+            row[RS - 2] = y;
+            row[RS - 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
+        }
+    }
+    // hierarchical GLM: the table GlmHierModel reads -- GlmModel's row with the group index behind y and lgamma(y + 1),
+    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1), g_i, 0], at a 128-byte boundary, zero
+    // rows up to a multiple of 64 observations
+    if (model_id == SMCN_MODEL_HGLM) {
+        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
+        const int64_t Dc = p + ic, head = hglm_head(Dc, model_data[0] >= 2.0);
+        const int RS = hglm_row_doubles((int)Dc), DP = RS - 4;
+        const int64_t t0 = hglm_table_offset(head, n, p), rows = glm_table_rows(n);
+        mup.assign(t0 + rows * RS, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            if (ic) row[0] = 1.0;
+            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[head + 2 * n + i * p + j];
+            const double y = model_data[head + i];
+            row[DP] = y;
+            row[DP + 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
+            row[DP + 2] = model_data[head + n + i];
+        }
+    }
+    // categorical: GlmModel's table with the row width from the Dc columns and the label in the y slot, [1 (intercept),
+    // X_i1 .. X_ip, 0 .. (to an even count), y_i, 0] (GlmCatModel)
+    if (model_id == SMCN_MODEL_CATEGORICAL) {
+        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
+        const int64_t D = dim;
+        const int RS = glm_row_doubles((int)(p + ic));
+        const int64_t t0 = glm_table_offset(D, n, p), rows = glm_table_rows(n);
+        mup.assign(t0 + rows * RS, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            if (ic) row[0] = 1.0;
+            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + D + n + i * p + j];
+            row[RS - 2] = model_data[4 + D + i];
+        }
+    }
+    // ordinal: GlmModel's table with the row width from the p columns and the label in the y slot, [X_i1 .. X_ip, 0 .. (to
+    // an even count), y_i, 0], then the K class counts n_0..n_{K-1} (GlmOrdModel)
+    if (model_id == SMCN_MODEL_ORDINAL) {
+        const int64_t K = (int64_t)model_data[0], n = (int64_t)model_data[1], p = (int64_t)model_data[2];
+        const int64_t D = dim;
+        const int RS = glm_row_doubles((int)p);
+        const int64_t t0 = glm_table_offset(D, n, p), c0 = ord_counts_offset(D, n, p);
+        mup.assign(c0 + K, 0.0);
+        std::copy(model_data, model_data + model_data_len, mup.begin());
+        for (int64_t i = 0; i < n; ++i) {
+            double* row = mup.data() + t0 + i * RS;
+            for (int64_t j = 0; j < p; ++j) row[j] = model_data[3 + D + n + i * p + j];
+            const double y = model_data[3 + D + i];
+            row[RS - 2] = y;
+            mup[c0 + (int64_t)y] += 1.0;
+        }
+    }
+}
+
 extern "C" {
 
 int smcn_version(void) { return 1; }
@@ -649,7 +736,7 @@ static void free_all(smcn_ctx* c) {
                     c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
                     c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
                     c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf};
+                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->pr_md};
     if (c->rows_h) (void)hipHostFree(c->rows_h);
     if (c->hist_h) (void)hipHostFree(c->hist_h);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
@@ -787,79 +874,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
                     mup.push_back(i < nobs ? (j < C ? model_data[4 + nobs + (size_t)i * C + j] : (j == RS - 1 ? model_data[4 + i] : 0.0)) : 0.0);
         }
     }
-    // GLM: behind the caller's data the table GlmModel / GlmDispModel read (smcn_models.hpp) -- a row per observation,
-    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1)], at a 128-byte boundary, zero rows up to a
-    // multiple of 64 observations.  The row width follows the Dc coefficients; the dispersion families' block has m_tau
-    // and s_tau between the prior sds and y (HD: the doubles before y).
-    if (model_id == SMCN_MODEL_GLM) {
-        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
-        const int64_t Dc = p + ic, HD = model_data[0] >= 2.0 ? Dc + 2 : Dc;
-        const int RS = glm_row_doubles((int)Dc);
-        const int64_t t0 = glm_table_offset(HD, n, p), rows = glm_table_rows(n);
-        mup.assign(t0 + rows * RS, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            if (ic) row[0] = 1.0;
-            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + HD + n + i * p + j];
-            const double y = model_data[4 + HD + i];
-            row[RS - 2] = y;
-            row[RS - 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
-        }
-    }
-    // hierarchical GLM: the table GlmHierModel reads -- GlmModel's row with the group index behind y and lgamma(y + 1),
-    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1), g_i, 0], at a 128-byte boundary, zero
-    // rows up to a multiple of 64 observations
-    if (model_id == SMCN_MODEL_HGLM) {
-        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
-        const int64_t Dc = p + ic, head = hglm_head(Dc, model_data[0] >= 2.0);
-        const int RS = hglm_row_doubles((int)Dc), DP = RS - 4;
-        const int64_t t0 = hglm_table_offset(head, n, p), rows = glm_table_rows(n);
-        mup.assign(t0 + rows * RS, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            if (ic) row[0] = 1.0;
-            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[head + 2 * n + i * p + j];
-            const double y = model_data[head + i];
-            row[DP] = y;
-            row[DP + 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
-            row[DP + 2] = model_data[head + n + i];
-        }
-    }
-    // categorical: GlmModel's table with the row width from the Dc columns and the label in the y slot, [1 (intercept),
-    // X_i1 .. X_ip, 0 .. (to an even count), y_i, 0] (GlmCatModel)
-    if (model_id == SMCN_MODEL_CATEGORICAL) {
-        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
-        const int64_t D = c->D;
-        const int RS = glm_row_doubles((int)(p + ic));
-        const int64_t t0 = glm_table_offset(D, n, p), rows = glm_table_rows(n);
-        mup.assign(t0 + rows * RS, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            if (ic) row[0] = 1.0;
-            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + D + n + i * p + j];
-            row[RS - 2] = model_data[4 + D + i];
-        }
-    }
-    // ordinal: GlmModel's table with the row width from the p columns and the label in the y slot, [X_i1 .. X_ip, 0 .. (to
-    // an even count), y_i, 0], then the K class counts n_0..n_{K-1} (GlmOrdModel)
-    if (model_id == SMCN_MODEL_ORDINAL) {
-        const int64_t K = (int64_t)model_data[0], n = (int64_t)model_data[1], p = (int64_t)model_data[2];
-        const int64_t D = c->D;
-        const int RS = glm_row_doubles((int)p);
-        const int64_t t0 = glm_table_offset(D, n, p), c0 = ord_counts_offset(D, n, p);
-        mup.assign(c0 + K, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            for (int64_t j = 0; j < p; ++j) row[j] = model_data[3 + D + n + i * p + j];
-            const double y = model_data[3 + D + i];
-            row[RS - 2] = y;
-            mup[c0 + (int64_t)y] += 1.0;
-        }
-    }
+    repack_model_table(model_id, c->D, model_data, model_data_len, mup);
     const int64_t mlen = (int64_t)mup.size();
     A_(mdata, mlen + 32);   // padded: the lane kernels read the series one chunk ahead
     A_(x, ND); A_(x_new, ND); A_(x_tmp, ND); A_(r, ND); A_(r_new, ND);
@@ -3444,6 +3459,277 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
 int smcn_pointwise_last_ms(const smcn_ctx* c, double* ms) {
     if (!c || !ms) return -1;
     *ms = c->pw_ms;
+    return 0;
+}
+
+}  // extern "C"
+// ---- held-out prediction at new rows (smcn_predict.hpp) ----------------------------------------------------------------
+static const char* kPrScope =
+    "held-out prediction covers the regression targets (SMCN_MODEL_GLM, SMCN_MODEL_HGLM, SMCN_MODEL_CATEGORICAL, "
+    "SMCN_MODEL_ORDINAL); arma, PRMwCD, Gaussian and host-evaluated targets are not supported";
+static bool pr_model(const smcn_ctx* c) {
+    return c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_CATEGORICAL ||
+           c->model == SMCN_MODEL_ORDINAL;
+}
+static int pr_classes(const smcn_ctx* c) {
+    return (c->model == SMCN_MODEL_CATEGORICAL || c->model == SMCN_MODEL_ORDINAL) ? (int)c->mdata_h[0] : 0;
+}
+static int pr_cols(const smcn_ctx* c) {
+    const int K = pr_classes(c);
+    if (c->model == SMCN_MODEL_CATEGORICAL) return kPrCatP0 + K;
+    if (c->model == SMCN_MODEL_ORDINAL) return kPrOrdP0 + (K <= kPrMaxProb ? K : 0);
+    return kPrColsGlm;
+}
+static PrArgs pr_args(const smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
+    const std::vector<double>& h = c->mdata_h;
+    PrArgs a;
+    a.T = c->pr_md + c->pr_toff;
+    a.x = x;
+    a.rs = rs;
+    a.cs = cs;
+    a.M = M;
+    a.cps = cps;
+    a.m = (int)c->pr_m;
+    a.D = c->D;
+    a.fam = 0;
+    a.J = 0;
+    a.K = pr_classes(c);
+    if (c->model == SMCN_MODEL_HGLM) {
+        a.fam = (int)h[0];
+        a.Dc = (int)h[2] + (int)h[3];
+        a.J = (int)h[4];
+    } else if (c->model == SMCN_MODEL_CATEGORICAL) {
+        a.Dc = (int)h[2] + (int)h[3];
+    } else {
+        a.Dc = (int)h[2];
+    }
+    return a;
+}
+// Dynamic LDS of one wavefront's area V[r][64 particles] (smcn_predict.hpp): J rows (hierarchical), D (categorical),
+// 2 (K - 1) or, with the class probabilities, 3 (K - 1) (ordinal); none for the GLM families.  The largest a model's
+// limits allow is the ordinal model at p = 0, K = 65: 128 rows = kPrMaxLdsBytes exactly, what a launch may ask for
+// without hipFuncSetAttribute.
+constexpr size_t kPrMaxLdsBytes = 64 * 1024;
+static size_t pr_lds_bytes(const smcn_ctx* c, bool stats) {
+    const PrArgs a = pr_args(c, nullptr, 0, 0, 0, 0);
+    size_t rows = 0;
+    if (c->model == SMCN_MODEL_HGLM) rows = (size_t)a.J;
+    else if (c->model == SMCN_MODEL_ORDINAL) rows = (size_t)(a.K - 1) * ((stats && a.K <= kPrMaxProb) ? 3 : 2);
+    else if (c->model == SMCN_MODEL_CATEGORICAL) rows = (size_t)a.D;
+    return sizeof(double) * 64 * rows;
+}
+#define PR_CHECK_LDS(c, stats, who)                                                                                     \
+    if (pr_lds_bytes(c, stats) > kPrMaxLdsBytes)                                                                        \
+        FAIL(c, std::string(who) + ": the model's per-wavefront LDS area (" + std::to_string(pr_lds_bytes(c, stats)) +  \
+                    " B) is above the 65536 B a launch may ask for")
+// Launches the model's matrix (STATS = false: out [M][m]) or statistics kernel over `blocks` wavefronts
+template <bool STATS>
+static void pr_launch(smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps, int64_t tiles,
+                      int64_t blocks, const double* lw, const double* head, double* out) {
+    const int g = (int)blocks;
+    hipStream_t st = c->stream;
+    if (c->model == SMCN_MODEL_GLM) {
+        PwArgs a = pw_args(c, x, rs, cs, M, cps);
+        a.md = c->pr_md;
+        a.n = (int)c->pr_m;
+        pw_dispatch(a, [&](auto dp, auto disp) {
+            constexpr int DP = decltype(dp)::value;
+            constexpr bool DI = decltype(disp)::value;
+            if constexpr (STATS) predict_glm_stats_kernel<DP, DI><<<g, 64, 0, st>>>(a, tiles, lw, head, out);
+            else pointwise_loglik_kernel<DP, DI><<<g, 64, 0, st>>>(a, tiles, out);
+        });
+        return;
+    }
+    const PrArgs a = pr_args(c, x, rs, cs, M, cps);
+    const int DP = (a.Dc + 1) & ~1;
+    if (c->model == SMCN_MODEL_HGLM) {
+        const size_t lds = pr_lds_bytes(c, STATS);
+        const auto go = [&](auto dp, auto disp) {
+            constexpr int DPM = decltype(dp)::value;
+            constexpr bool DI = decltype(disp)::value;
+            if constexpr (STATS) predict_hier_stats_kernel<DPM, DI><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
+            else predict_hier_loglik_kernel<DPM, DI><<<g, 64, lds, st>>>(a, tiles, out);
+        };
+        const auto fam = [&](auto dp) { a.fam >= 2 ? go(dp, std::true_type{}) : go(dp, std::false_type{}); };
+        if (DP <= 16) fam(std::integral_constant<int, 16>{});
+        else if (DP <= 32) fam(std::integral_constant<int, 32>{});
+        else fam(std::integral_constant<int, 64>{});
+    } else if (c->model == SMCN_MODEL_ORDINAL) {
+        const bool prob = a.K <= kPrMaxProb;
+        const size_t lds = pr_lds_bytes(c, STATS);
+        const auto go = [&](auto dp) {
+            constexpr int DPM = decltype(dp)::value;
+            if constexpr (STATS) {
+                if (prob) predict_ord_stats_kernel<DPM, true><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
+                else predict_ord_stats_kernel<DPM, false><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
+            } else {
+                predict_ord_loglik_kernel<DPM><<<g, 64, lds, st>>>(a, tiles, out);
+            }
+        };
+        if (DP <= 16) go(std::integral_constant<int, 16>{});
+        else if (DP <= 32) go(std::integral_constant<int, 32>{});
+        else go(std::integral_constant<int, 64>{});
+    } else {
+        // categorical: (row capacity, non-reference classes) pairs that cover (K - 1) Dc <= 64
+        const size_t lds = pr_lds_bytes(c, STATS);
+        const auto go = [&](auto dc, auto km) {
+            constexpr int DCM = decltype(dc)::value, KM = decltype(km)::value;
+            if constexpr (STATS) predict_cat_stats_kernel<DCM, KM><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
+            else predict_cat_loglik_kernel<DCM, KM><<<g, 64, lds, st>>>(a, tiles, out);
+        };
+        using std::integral_constant;
+        if (a.Dc <= 4) go(integral_constant<int, 4>{}, integral_constant<int, 15>{});
+        else if (a.Dc <= 8) go(integral_constant<int, 8>{}, integral_constant<int, 12>{});
+        else if (a.Dc <= 16) go(integral_constant<int, 16>{}, integral_constant<int, 7>{});
+        else if (a.Dc <= 32) go(integral_constant<int, 32>{}, integral_constant<int, 3>{});
+        else go(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+    }
+}
+
+extern "C" {
+
+int smcn_predict_set_data(smcn_ctx* c, const double* block, int64_t len, int has_y) {
+    CHECK_CTX(c);
+    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_set_data: ") + kPrScope);
+    const std::vector<double>& h = c->mdata_h;
+    const bool ord = c->model == SMCN_MODEL_ORDINAL, hg = c->model == SMCN_MODEL_HGLM;
+    const int64_t nh = ord ? 3 : (hg ? 5 : 4);                   // header doubles
+    if (!block || len < nh) FAIL(c, "smcn_predict_set_data: the block is the model's data block without the priors");
+    for (int64_t q = 0; q < nh; ++q)
+        if (q != 1 && block[q] != h[q])
+            FAIL(c, "smcn_predict_set_data: the new rows' header must repeat the training block's (family or K, p, "
+                    "intercept, J): the column count differs from the training design?");
+    // the priors of the training block spliced in: the block smcn_ctx_create would take, checked by the same routine
+    int64_t npri = c->D;
+    if (c->model == SMCN_MODEL_GLM) npri = (int64_t)h[2] + (int64_t)h[3] + (h[0] >= 2.0 ? 2 : 0);
+    if (hg) npri = hglm_head((int64_t)h[2] + (int64_t)h[3], h[0] >= 2.0) - 5;
+    std::vector<double> full;
+    full.reserve((size_t)(len + npri));
+    full.insert(full.end(), block, block + nh);
+    full.insert(full.end(), h.begin() + nh, h.begin() + nh + npri);
+    full.insert(full.end(), block + nh, block + len);
+    int D = 0;
+    const int64_t fl = (int64_t)full.size();
+    const std::string why = c->model == SMCN_MODEL_GLM ? glm_check(full.data(), fl, &D)
+                            : hg ? hglm_check(full.data(), fl, &D)
+                            : ord ? ord_check(full.data(), fl, &D) : cat_check(full.data(), fl, &D);
+    if (!why.empty()) FAIL(c, "smcn_predict_set_data (new rows, with the training priors spliced in): " + why);
+    if (D != c->D) FAIL(c, "smcn_predict_set_data: the new rows give another dimension than the training data");
+    const int64_t m = (int64_t)full[1], p = (int64_t)full[2];
+    std::vector<double> mup;
+    repack_model_table(c->model, c->D, full.data(), fl, mup);
+    const int64_t toff = c->model == SMCN_MODEL_GLM ? glm_table_offset(npri, m, p)
+                         : hg ? hglm_table_offset(nh + npri, m, p) : glm_table_offset(c->D, m, p);
+    const int64_t need = (int64_t)mup.size();
+    c->pr_m = 0;
+    if (need > c->pr_md_len) {
+        if (c->pr_md) {
+            HIPC(c, stream_wait(c->stream));
+            (void)cached_free(c->pr_md);
+        }
+        c->pr_md = nullptr;
+        c->pr_md_len = 0;
+        HIPC(c, dalloc(&c->pr_md, need));
+        c->pr_md_len = need;
+    }
+    HIPC(c, hipMemcpyAsync(c->pr_md, mup.data(), sizeof(double) * need, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, stream_wait(c->stream));                             // (mup is a local)
+    c->pr_toff = toff;
+    c->pr_m = m;
+    c->pr_has_y = has_y ? 1 : 0;
+    return 0;
+}
+
+int smcn_predict_dims(smcn_ctx* c, int64_t* n_rows, int* n_cols, int* has_y) {
+    CHECK_CTX(c);
+    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_dims: ") + kPrScope);
+    if (c->pr_m < 1) FAIL(c, "smcn_predict_dims: no new rows (smcn_predict_set_data first)");
+    if (n_rows) *n_rows = c->pr_m;
+    if (n_cols) *n_cols = pr_cols(c);
+    if (has_y) *has_y = c->pr_has_y;
+    return 0;
+}
+
+int smcn_predict_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
+    CHECK_CTX(c);
+    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_loglik: ") + kPrScope);
+    if (c->pr_m < 1) FAIL(c, "smcn_predict_loglik: no new rows (smcn_predict_set_data first)");
+    if (!c->pr_has_y) FAIL(c, "smcn_predict_loglik: the new rows were given without y");
+    if (!x || !out || M < 1) FAIL(c, "smcn_predict_loglik: bad arguments");
+    PR_CHECK_LDS(c, false, "smcn_predict_loglik");
+    const int64_t m = c->pr_m, tiles = (m + 63) / 64;
+    int64_t cps = 1;
+    const int64_t slices = pointwise_slices(M, m, &cps);
+    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_predict_loglik: too many rows");
+    int rc = ensure_stage(c, M * c->D);
+    if (rc) return rc;
+    if ((rc = pw_ensure(c, M * m))) return rc;
+    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+    pr_launch<false>(c, c->stage, c->D, 1, M, cps, tiles, tiles * slices, nullptr, nullptr, c->pw_buf);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, c->pw_buf, sizeof(double) * M * m, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
+int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
+    CHECK_CTX(c);
+    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_partials: ") + kPrScope);
+    if (c->pr_m < 1) FAIL(c, "smcn_predict_partials: no new rows (smcn_predict_set_data first)");
+    if (!out || M < 1) FAIL(c, "smcn_predict_partials: bad arguments");
+    PR_CHECK_LDS(c, true, "smcn_predict_partials");
+    if (!x && (M != c->N || logw)) FAIL(c, "smcn_predict_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
+    const int64_t m = c->pr_m, tiles = (m + 63) / 64, mpad = tiles * 64;
+    const int Q = pr_cols(c), mom = (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_HGLM) ? 1 : 0;
+    int64_t cps = 1;
+    const int64_t slices = pointwise_slices(M, m, &cps);
+    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_predict_partials: too many rows");
+    // pw_buf: [header 16 | lw M | slice partials | group partials | result (1 + m) Q]
+    const int64_t groups = (slices + kPwGroup - 1) / kPwGroup;
+    const int64_t o_lw = 16, o_part = o_lw + (M + 15) / 16 * 16, o_grp = o_part + slices * Q * mpad;
+    const int64_t o_out = o_grp + groups * Q * mpad;
+    int rc = pw_ensure(c, o_out + (1 + m) * Q);
+    if (rc) return rc;
+    double* const head = c->pw_buf;
+    double* lw = c->pw_buf + o_lw;
+    double* const part = c->pw_buf + o_part;
+    double* const grp = c->pw_buf + o_grp;
+    double* const res = c->pw_buf + o_out;
+    const double* xd = c->x;
+    int64_t rs = 1, cs = c->N;
+    if (x) {
+        if ((rc = ensure_stage(c, M * c->D))) return rc;
+        HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+        if (logw) HIPC(c, hipMemcpyAsync(lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        else HIPC(c, hipMemsetAsync(lw, 0, sizeof(double) * M, c->stream));
+        xd = c->stage;
+        rs = c->D;
+        cs = 1;
+    } else {
+        lw = c->logw;
+    }
+    if (!c->pw_ev0) {
+        HIPC(c, hipEventCreate(&c->pw_ev0));
+        HIPC(c, hipEventCreate(&c->pw_ev1));
+    }
+    HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
+    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
+    pr_launch<true>(c, xd, rs, cs, M, cps, tiles, tiles * slices, lw, head, part);
+    predict_combine_kernel<false><<<dim3((unsigned)grid_for(m, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, m, mpad, Q, mom, grp);
+    predict_combine_kernel<true><<<grid_for(m, 64), 64, 0, c->stream>>>(grp, head, groups, m, mpad, Q, mom, res);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->pw_ev1, c->stream));
+    HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * (1 + m) * Q, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
+    c->pr_ms = (double)ms;
+    return 0;
+}
+
+int smcn_predict_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    *ms = c->pr_ms;
     return 0;
 }
 

@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from .. import _capi
+from ..predict import PredictMixin
 
 DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
@@ -229,7 +230,7 @@ GLM_MAX_DIM = 64
 _NO_PRIOR = object()
 
 
-class GLMTarget(DeviceTarget):
+class GLMTarget(PredictMixin, DeviceTarget):
     """GLM on the device, eta = [b_0 +] X b, independent N(0, prior_sd_c^2) priors on the Dc = p + intercept
     coefficients (the intercept is coordinate 0):
       bernoulli_logit:    y_i ~ bernoulli_logit(eta_i)
@@ -345,7 +346,7 @@ class GLMTarget(DeviceTarget):
         return combine_pointwise_partials([self.pointwise_partials(x, logw)])
 
 
-class HierarchicalGLM(DeviceTarget):
+class HierarchicalGLM(PredictMixin, DeviceTarget):
     """Varying-intercept GLM on the device, non-centred: observations fall into J groups, group j has the intercept
     alpha_j = tau z_j,
       eta_i = [b_0 +] X_i b + tau z_{g_i},   y_i ~ family(eta_i [, e^ld])   (GLMTarget's four families, same terms)
@@ -454,7 +455,7 @@ class HierarchicalGLM(DeviceTarget):
 CAT_MAX_CLASSES = 16
 
 
-class CategoricalRegression(DeviceTarget):
+class CategoricalRegression(PredictMixin, DeviceTarget):
     """Categorical (multinomial logistic) regression on the device, Stan's categorical_logit with class 0 the
     reference: y_i in {0, .., K-1},
       eta_i0 = 0,  eta_ik = [b_k0 +] X_i b_k  (k = 1..K-1),  log p(y_i) = eta_{i,y_i} - logsumexp_k eta_ik,
@@ -527,7 +528,7 @@ class CategoricalRegression(DeviceTarget):
         super().__init__(data, D, names)
 
 
-class OrdinalRegression(DeviceTarget):
+class OrdinalRegression(PredictMixin, DeviceTarget):
     """Ordinal (ordered-logistic) regression on the device, Stan's ordered_logistic with y shifted to 0..K-1:
       eta_i = X_i b (no intercept: the cutpoints take its place),
       P(y_i = k) = logit^-1(eta_i - c_k) - logit^-1(eta_i - c_{k+1})  (c_0 = -inf, c_K = +inf),

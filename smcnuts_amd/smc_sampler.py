@@ -527,6 +527,35 @@ class SMCSampler:
             return combine_pointwise_partials([p.reshape(part.shape) for p in allp])
         return combine_pointwise_partials([part])
 
+    def predict(self, X_new, y_new=None, groups_new=None):
+        """Posterior predictive summaries at new rows (predict.Prediction: mean / variance or class probabilities, and with
+        y_new the log predictive density of each held-out row) of the final generation and its weights, after sample() /
+        finalise(): computed from the resident particles, nothing is uploaded but the new rows and nothing downloaded but
+        the [1 + m][Q] partials.  Several shards: every rank computes its partials, ONE host all-gather moves them, every
+        rank combines them in rank order."""
+        from .predict import combine_predict_partials
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError("predict(): the asymptotic L-kernel's estimates pool generations; predictions over "
+                                      "the pooled generations are not implemented")
+        if not hasattr(self.target, "predict_partials"):
+            raise NotImplementedError(f"{type(self.target).__name__}: held-out prediction is implemented for GLMTarget, "
+                                      "HierarchicalGLM, CategoricalRegression and OrdinalRegression")
+        block, has_y = self.target._predict_block(X_new, y_new, groups_new)
+        if not self._finalised:
+            raise RuntimeError("predict(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"predict(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
+                               "target the posterior")
+        kind, K = self.target._predict_kind()
+        ctx = self.samples.ctx
+        ctx.call("smcn_synchronize")
+        ctx.predict_set_data(block, has_y)
+        part = ctx.predict_partials()
+        if self.comm.world_size > 1:
+            allp = np.asarray(self.comm.allgather(part.reshape(-1)))
+            return combine_predict_partials([p.reshape(part.shape) for p in allp], kind, K, has_y)
+        return combine_predict_partials([part], kind, K, has_y)
+
     def sample(self, show_progress=True):
         start_time = time()
         if self.device_resident and not self._host_loop_used:
