@@ -542,6 +542,36 @@ int smcn_predict_partials(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, c
                           int64_t M, double* out /* [1 + m][Q] */);
 int smcn_predict_last_ms(const smcn_ctx* ctx, double* ms);
 
+/* ---- posterior predictive draws at the rows of the last smcn_predict_set_data (the same four models) ----
+ * smcn_predict_draws: y_out[j][i] ~ p(. | x_{a_s}, row i) for the slots s = s_first + j, j < s_count, of S: draw s is ONE
+ * replicated data set of the m rows from ONE ancestor particle a_s.  x == NULL: the resident particles with their
+ * resident log-weights (M = N, logw = NULL); logw == NULL with x: equal weights.
+ * Ancestors: systematic resampling with S slots.  W the normalised weights in particle order, C their inclusive
+ * cumulative sum, u0 = philox_uniform(seed, iter 0, particle 0, stream 16, q 0), a_s = min{p : C_p > (s + u0) / S},
+ * clamped to the last particle with a finite log-weight; a particle with a non-finite log-weight is never chosen.
+ * ancestors != NULL ([S], each in 0..M-1) replaces them: the way to draw from chosen particles.
+ * Uniforms: philox_uniform(seed, iter = s, particle = i (the row), stream, q) with streams 17 outcome, 18 gamma,
+ * 19 new-group intercept (particle = the group's label): a draw depends on (seed, s, i) and its ancestor alone, not on
+ * the slot range, the tiling or S.
+ * Samplers: Bernoulli [u < p]; categorical min{k : P_0 + .. + P_k > u}, else K - 1; ordinal #{k : c_k < eta + log u -
+ * log1p(-u)}; normal eta + sigma z, z = sqrt(-2 log1p(-u_0)) cos(2 pi u_1); Poisson by inversion below mu = 10 (at most
+ * 1000 steps) and by Hoermann's PTRS from 10 (attempt t: uniforms 2t, 2t + 1); NB2 as Poisson(mu G / phi) with
+ * G ~ Gamma(phi, 1) by Marsaglia-Tsang on stream 18 (attempt t: uniforms 3t, 3t + 1 (Box-Muller), 3t + 2; phi < 1: shape
+ * phi + 1 and the boost u_192^(1 / phi)); 64 attempts at most.  Above mu of about 1e15 the rounding grid of the doubles
+ * shows in the variance of the PTRS draws.
+ * SMCN_MODEL_HGLM: new_group != NULL ([m]) gives per row the label of a NEW group (>= J; rows that share a label share
+ * the group) or any value below J for a row of the fitted group the block names; a new group's intercept is tau_p z,
+ * z the Box-Muller cosine of stream 19 at (iter = s, particle = label, q = 0, 1).  Rows of new groups carry group 0 in
+ * the block.  NULL for every other model.
+ * Bad draws are NaN and counted in *n_bad_out: a non-finite eta, logit (-inf included), mean or cutpoint, mu > 2^53, a
+ * dispersion coordinate the density refuses, e^eta or e^(2 lt) overflowing, an attempt cap reached.
+ * smcn_predict_draws_last_ms: the device time of the last smcn_predict_draws' kernels. */
+int smcn_predict_draws(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */, int64_t M,
+                       int64_t S, uint64_t seed, const int64_t* ancestors_or_null /* [S] */,
+                       const int64_t* new_group_or_null /* [m] */, int64_t s_first, int64_t s_count,
+                       double* y_out /* [s_count][m] */, int64_t* ancestors_out /* [s_count] */, int64_t* n_bad_out);
+int smcn_predict_draws_last_ms(const smcn_ctx* ctx, double* ms);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build. */

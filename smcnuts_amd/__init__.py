@@ -12,4 +12,4 @@ from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GL
                             HostTarget, IsoGaussian, LinearRegression, LogisticRegression, NegativeBinomialRegression,
                             OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel)
 from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F401
-from .predict import Prediction, combine_predict_partials, compare_heldout  # noqa: F401
+from .predict import Prediction, PredictiveDraws, combine_predict_partials, compare_heldout  # noqa: F401

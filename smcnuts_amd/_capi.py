@@ -140,6 +140,9 @@ SIGNATURES = {
     "smcn_predict_loglik": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
     "smcn_predict_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
     "smcn_predict_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_predict_draws": ([_ctx, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, _lp, _lp, C.c_int64, C.c_int64, _dp, _lp,
+                            _lp], C.c_int),
+    "smcn_predict_draws_last_ms": ([_ctx, _dp], C.c_int),
 }
 
 _lib = None
@@ -430,6 +433,40 @@ class Context:
         rc = self._lib.smcn_predict_last_ms(self._h, C.byref(ms))
         if rc != 0:
             raise SmcnError("smcn_predict_last_ms failed")
+        return ms.value
+
+    def predict_draws(self, S, seed, x=None, logw=None, ancestors=None, new_group=None, s_first=0, s_count=None):
+        """(y [s_count][m], ancestors [s_count], n_bad): posterior predictive draws of the slots s_first .. of S at the
+        rows of the last predict_set_data (include/smcnuts_hip.h); x=None: the resident particles and weights."""
+        m, _, _ = self.predict_dims()
+        S = int(S)
+        n = S - int(s_first) if s_count is None else int(s_count)
+        y, anc, nbad = np.empty((max(n, 0), m)), np.empty(max(n, 0), dtype=np.int64), C.c_int64(0)
+        ip = lambda a: None if a is None else a.ctypes.data_as(_lp)
+        a_in = None if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+        if a_in is not None and a_in.shape != (S,):
+            raise ValueError("ancestors must hold one particle index per draw")
+        g_in = None if new_group is None else np.ascontiguousarray(new_group, dtype=np.int64)
+        if g_in is not None and g_in.shape != (m,):
+            raise ValueError("new_group must hold one label per new row")
+        if x is None:
+            xp, lp_, M = None, None, self.N
+        else:
+            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+            if lw is not None and lw.shape != (x.shape[0],):
+                raise ValueError("logw must hold one log-weight per row of x")
+            xp, lp_, M = dptr(x), dptr(lw), x.shape[0]
+        self.call("smcn_predict_draws", xp, lp_, M, S, C.c_uint64(int(seed) & (2 ** 64 - 1)), ip(a_in), ip(g_in),
+                  int(s_first), n, dptr(y), ip(anc), C.byref(nbad))
+        return y, anc, nbad.value
+
+    def predict_draws_last_ms(self):
+        """Device time of the last predict_draws' kernels (HIP events on the context's stream)."""
+        ms = C.c_double(0.0)
+        rc = self._lib.smcn_predict_draws_last_ms(self._h, C.byref(ms))
+        if rc != 0:
+            raise SmcnError("smcn_predict_draws_last_ms failed")
         return ms.value
 
     def timers(self, reset=False):

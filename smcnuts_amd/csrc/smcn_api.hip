@@ -30,6 +30,7 @@
 #include "smcn_comm.hpp"
 #include "smcn_pointwise.hpp"
 #include "smcn_predict.hpp"
+#include "smcn_predict_draws.hpp"
 
 using namespace smcn;
 
@@ -178,6 +179,11 @@ struct smcn_ctx {
     int64_t pr_md_len = 0, pr_toff = 0, pr_m = 0;
     int pr_has_y = 0;
     double pr_ms = 0.0;
+
+    // posterior predictive draws (smcn_predict_draws): weights, scan, ancestors, gathered particles and the draws of a call
+    double* dr_buf = nullptr;
+    int64_t dr_len = 0;
+    double dr_ms = 0.0;
 };
 
 #define CHECK_CTX(c)             \
@@ -736,7 +742,7 @@ static void free_all(smcn_ctx* c) {
                     c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
                     c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
                     c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->pr_md};
+                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->pr_md, c->dr_buf};
     if (c->rows_h) (void)hipHostFree(c->rows_h);
     if (c->hist_h) (void)hipHostFree(c->hist_h);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
@@ -3730,6 +3736,170 @@ int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int6
 int smcn_predict_last_ms(const smcn_ctx* c, double* ms) {
     if (!c || !ms) return -1;
     *ms = c->pr_ms;
+    return 0;
+}
+
+}  // extern "C"
+// ---- posterior predictive draws (smcn_predict_draws.hpp) ---------------------------------------------------------------
+// Which (model, row capacity) instantiations sample inside the walk; the others store the law's mean and
+// draws_sample_kernel samples it (Posterior predictive draws: the register counts behind the choice)
+template <int DPMAX, bool DISP>
+constexpr bool kDrawsFusedGlm = DPMAX <= 16;
+template <int DPMAX, bool DISP>
+constexpr bool kDrawsFusedHier = DPMAX <= 16;
+
+// Launches the model's draw kernel over the n gathered particles xg [D][n] -> out [n][m]
+static void dr_launch(smcn_ctx* c, const double* xg, int64_t n, const DrawArgs& d, double* out) {
+    const int64_t m = c->pr_m, tiles = (m + 63) / 64;
+    int64_t cps = 1;
+    const int64_t slices = pointwise_slices(n, m, &cps);
+    const int g = (int)(tiles * slices);
+    hipStream_t st = c->stream;
+    const auto second = [&](int fam, bool disp, int tau_coord) {
+        draws_sample_kernel<<<grid_for(n * m, 256), 256, 0, st>>>(fam, m, n, d, disp ? xg + (int64_t)tau_coord * n : nullptr, out);
+    };
+    if (c->model == SMCN_MODEL_GLM) {
+        PwArgs a = pw_args(c, xg, 1, n, n, cps);
+        a.md = c->pr_md;
+        a.n = (int)m;
+        pw_dispatch(a, [&](auto dp, auto disp) {
+            constexpr int DP = decltype(dp)::value;
+            constexpr bool DI = decltype(disp)::value;
+            constexpr bool FU = kDrawsFusedGlm<DP, DI>;
+            draws_glm_kernel<DP, DI, FU><<<g, 64, 0, st>>>(a, tiles, d, out);
+            if (!FU) second(a.fam, DI, a.Dc);
+        });
+        return;
+    }
+    const PrArgs a = pr_args(c, xg, 1, n, n, cps);
+    const int DP = (a.Dc + 1) & ~1;
+    const size_t lds = pr_lds_bytes(c, false);
+    if (c->model == SMCN_MODEL_HGLM) {
+        const auto go = [&](auto dp, auto disp) {
+            constexpr int DPM = decltype(dp)::value;
+            constexpr bool DI = decltype(disp)::value;
+            constexpr bool FU = kDrawsFusedHier<DPM, DI>;
+            draws_hier_kernel<DPM, DI, FU><<<g, 64, lds, st>>>(a, tiles, d, out);
+            if (!FU) second(a.fam, DI, a.Dc + a.J + 1);
+        };
+        const auto fam = [&](auto dp) { a.fam >= 2 ? go(dp, std::true_type{}) : go(dp, std::false_type{}); };
+        if (DP <= 16) fam(std::integral_constant<int, 16>{});
+        else if (DP <= 32) fam(std::integral_constant<int, 32>{});
+        else fam(std::integral_constant<int, 64>{});
+    } else if (c->model == SMCN_MODEL_ORDINAL) {
+        if (DP <= 16) draws_ord_kernel<16><<<g, 64, lds, st>>>(a, tiles, d, out);
+        else if (DP <= 32) draws_ord_kernel<32><<<g, 64, lds, st>>>(a, tiles, d, out);
+        else draws_ord_kernel<64><<<g, 64, lds, st>>>(a, tiles, d, out);
+    } else {
+        if (a.Dc <= 4) draws_cat_kernel<4, 15><<<g, 64, lds, st>>>(a, tiles, d, out);
+        else if (a.Dc <= 8) draws_cat_kernel<8, 12><<<g, 64, lds, st>>>(a, tiles, d, out);
+        else if (a.Dc <= 16) draws_cat_kernel<16, 7><<<g, 64, lds, st>>>(a, tiles, d, out);
+        else if (a.Dc <= 32) draws_cat_kernel<32, 3><<<g, 64, lds, st>>>(a, tiles, d, out);
+        else draws_cat_kernel<64, 1><<<g, 64, lds, st>>>(a, tiles, d, out);
+    }
+}
+
+extern "C" {
+
+int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t M, int64_t S, uint64_t seed,
+                       const int64_t* ancestors, const int64_t* new_group, int64_t s_first, int64_t s_count, double* y_out,
+                       int64_t* ancestors_out, int64_t* n_bad_out) {
+    CHECK_CTX(c);
+    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_draws: ") + kPrScope);
+    if (c->pr_m < 1) FAIL(c, "smcn_predict_draws: no new rows (smcn_predict_set_data first)");
+    if (M < 1) FAIL(c, "smcn_predict_draws: M must be at least 1");
+    if (S < 1 || S > 2147483647LL) FAIL(c, "smcn_predict_draws: the number of draws S must be in 1..2^31-1");
+    if (s_first < 0 || s_count < 1 || s_first + s_count > S)
+        FAIL(c, "smcn_predict_draws: the slot range [s_first, s_first + s_count) must be non-empty and lie in 0..S");
+    if (!y_out) FAIL(c, "smcn_predict_draws: y_out is null");
+    if (!x && (M != c->N || logw)) FAIL(c, "smcn_predict_draws: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
+    if (new_group && c->model != SMCN_MODEL_HGLM) FAIL(c, "smcn_predict_draws: new_group is for SMCN_MODEL_HGLM only");
+    const int64_t m = c->pr_m, tiles = (m + 63) / 64, n = s_count;
+    if (new_group)
+        for (int64_t i = 0; i < m; ++i)
+            if (new_group[i] < 0 || new_group[i] > 4294967295LL)
+                FAIL(c, "smcn_predict_draws: new_group[" + std::to_string(i) + "] is not a label in 0..2^32-1");
+    if (ancestors)
+        for (int64_t s = 0; s < S; ++s)
+            if (ancestors[s] < 0 || ancestors[s] >= M)
+                FAIL(c, "smcn_predict_draws: ancestors[" + std::to_string(s) + "] is not a particle in 0..M-1");
+    PR_CHECK_LDS(c, false, "smcn_predict_draws");
+    int64_t cps = 1;
+    if (tiles * pointwise_slices(n, m, &cps) > 2147483647LL) FAIL(c, "smcn_predict_draws: too many rows");
+    // dr_buf: [header 16 | lw M | w M | scan M | tile totals nt | tile offsets nt + 1 | ancestors n | labels m | xg D n | y n m]
+    const int nt = (int)((M + kScanTile - 1) / kScanTile);
+    const auto pad = [](int64_t v) { return (v + 15) / 16 * 16; };
+    const int64_t o_lw = 16, o_w = o_lw + pad(M), o_loc = o_w + pad(M), o_tt = o_loc + pad(M), o_to = o_tt + pad(nt);
+    const int64_t o_anc = o_to + pad(nt + 1), o_ng = o_anc + pad(n), o_xg = o_ng + pad(m), o_y = o_xg + pad(n * c->D);
+    const int64_t need = o_y + n * m;
+    if (need > c->dr_len) {
+        if (c->dr_buf) {
+            HIPC(c, stream_wait(c->stream));
+            (void)cached_free(c->dr_buf);
+        }
+        c->dr_buf = nullptr;
+        c->dr_len = 0;
+        HIPC(c, dalloc(&c->dr_buf, need));
+        c->dr_len = need;
+    }
+    double* const B = c->dr_buf;
+    double* const head = B;
+    double* lw = B + o_lw;
+    int64_t* const anc = (int64_t*)(B + o_anc);
+    int64_t* const ng = (int64_t*)(B + o_ng);
+    const double* xd = c->x;
+    int64_t rs = 1, cs = c->N;
+    if (x) {
+        int rc = ensure_stage(c, M * c->D);
+        if (rc) return rc;
+        HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+        if (logw) HIPC(c, hipMemcpyAsync(lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        else HIPC(c, hipMemsetAsync(lw, 0, sizeof(double) * M, c->stream));
+        xd = c->stage;
+        rs = c->D;
+        cs = 1;
+    } else {
+        lw = c->logw;
+    }
+    if (new_group) HIPC(c, hipMemcpyAsync(ng, new_group, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
+    if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
+    if (!c->pw_ev0) {
+        HIPC(c, hipEventCreate(&c->pw_ev0));
+        HIPC(c, hipEventCreate(&c->pw_ev1));
+    }
+    HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
+    if (!ancestors) {
+        pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
+        draws_weights_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(lw, head, M, B + o_w);
+        scan_tile_kernel<<<nt, 256, 0, c->stream>>>(B + o_w, M, B + o_loc, B + o_tt);
+        scan_offsets_kernel<<<1, 64, 0, c->stream>>>(B + o_tt, nt, B + o_to);
+        draws_ancestors_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(B + o_loc, B + o_to, nt, M, lw, S, s_first, n, seed, anc);
+    }
+    draws_gather_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(xd, rs, cs, anc, n, c->D, B + o_xg);
+    const DrawArgs d{seed, s_first, new_group ? ng : nullptr};
+    dr_launch(c, B + o_xg, n, d, B + o_y);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->pw_ev1, c->stream));
+    double cnt = 1.0;
+    if (!ancestors) HIPC(c, hipMemcpyAsync(&cnt, head + 3, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (ancestors_out) HIPC(c, hipMemcpyAsync(ancestors_out, anc, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(y_out, B + o_y, sizeof(double) * n * m, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
+    c->dr_ms = (double)ms;
+    if (cnt == 0.0) FAIL(c, "smcn_predict_draws: no particle has a finite log-weight");
+    if (n_bad_out) {
+        int64_t nb = 0;
+        for (int64_t e = 0; e < n * m; ++e) nb += y_out[e] != y_out[e] ? 1 : 0;
+        *n_bad_out = nb;
+    }
+    return 0;
+}
+
+int smcn_predict_draws_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    *ms = c->dr_ms;
     return 0;
 }
 

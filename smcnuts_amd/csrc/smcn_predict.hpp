@@ -156,9 +156,11 @@ __global__ void __launch_bounds__(64) predict_glm_stats_kernel(PwArgs a, int64_t
 }
 
 // ---- hierarchical ------------------------------------------------------------------------------------------------------
-// f(t, lwq, wq, term, mean, var): one (row, particle) pair, t, lwq, wq wave-uniform
-template <int DPMAX, bool DISP, class Chunk, class Term>
-__device__ __forceinline__ void pr_walk_hier(const PrArgs& a, int64_t tile, int64_t slice, Chunk&& chunk, Term&& f) {
+// f(t, lwq, wq, term, mean, var): one (row, particle) pair, t, lwq, wq wave-uniform; alpha(t, tau, z_{g_i}) gives the
+// row's intercept (pr_walk_hier: tau z_{g_i}, the fitted group's)
+template <int DPMAX, bool DISP, class Chunk, class Term, class Alpha>
+__device__ __forceinline__ void pr_walk_hier_alpha(const PrArgs& a, int64_t tile, int64_t slice, Chunk&& chunk, Term&& f,
+                                                   Alpha&& alpha) {
     using d2 = double __attribute__((ext_vector_type(2)));
     double* const zb = pr_area();                  // z[j][particle]
     const int lane = (int)(threadIdx.x & 63u);
@@ -212,7 +214,7 @@ __device__ __forceinline__ void pr_walk_hier(const PrArgs& a, int64_t tile, int6
                 }
             }
             const double zq = zb[pr_slot(gi, q)];
-            const double al = group_read<64>(tauv, q) * zq;   // alpha_{g_i}
+            const double al = alpha(p0 + q, group_read<64>(tauv, q), zq);   // alpha_{g_i}
             const double eta = (e0 + e1) + al;
             const int fl = group_read_i<64>(flv, q);
             double term, mean;
@@ -236,6 +238,11 @@ __device__ __forceinline__ void pr_walk_hier(const PrArgs& a, int64_t tile, int6
         }
         wave_exchange_fence();                             // (the next chunk's writes after these reads)
     }
+}
+
+template <int DPMAX, bool DISP, class Chunk, class Term>
+__device__ __forceinline__ void pr_walk_hier(const PrArgs& a, int64_t tile, int64_t slice, Chunk&& chunk, Term&& f) {
+    pr_walk_hier_alpha<DPMAX, DISP>(a, tile, slice, chunk, f, [](int64_t, double tauq, double zq) { return tauq * zq; });
 }
 
 template <int DPMAX, bool DISP>
@@ -273,7 +280,7 @@ __device__ __forceinline__ void pr_sigmoid(double a, double& s, double& sc) {
     s = a >= 0.0 ? inv : ti;
     sc = a >= 0.0 ? ti : inv;
 }
-// f(t, lwq, wq, term, em, P, ok): em = sum_k sigma(eta - c_k), P[k] = P(y = k | x_p) (PROB), ok: all of them finite
+// f(t, lwq, wq, term, em, P, ok, eta): em = sum_k sigma(eta - c_k), P[k] = P(y = k | x_p) (PROB), ok: all of them finite
 template <int DPMAX, bool PROB, bool STATS, class Chunk, class Term>
 __device__ __forceinline__ void pr_walk_ord(const PrArgs& a, int64_t tile, int64_t slice, Chunk&& chunk, Term&& f) {
     using d2 = double __attribute__((ext_vector_type(2)));
@@ -370,7 +377,7 @@ __device__ __forceinline__ void pr_walk_ord(const PrArgs& a, int64_t tile, int64
                     em += s;
                 }
             }
-            f(p0 + q, lwq, group_read<64>(wv, q), term, em, P, finite_d(em));
+            f(p0 + q, lwq, group_read<64>(wv, q), term, em, P, finite_d(em), eta);
         }
         wave_exchange_fence();                             // (the next chunk's writes after these reads)
     }
@@ -382,7 +389,7 @@ __global__ void __launch_bounds__(64) predict_ord_loglik_kernel(PrArgs a, int64_
     const int64_t i = tile * 64 + (threadIdx.x & 63u);
     pr_walk_ord<DPMAX, false, false>(
         a, tile, slice, [](int64_t, bool) { return 0.0; },
-        [&](int64_t t, double, double, double term, double, const double (&)[1], bool) {
+        [&](int64_t t, double, double, double term, double, const double (&)[1], bool, double) {
             if (i < a.m) out[t * a.m + i] = term;
         });
 }
@@ -400,7 +407,7 @@ __global__ void __launch_bounds__(64) predict_ord_stats_kernel(PrArgs a, int64_t
     for (int k = 0; k < KP; ++k) PS[k] = 0.0;
     pr_walk_ord<DPMAX, PROB, true>(
         a, tile, slice, [&](int64_t t, bool have) { return have ? lw[t] - mw : -kInf; },
-        [&](int64_t, double lwq, double wq, double term, double em, const double (&P)[KP], bool ok) {
+        [&](int64_t, double lwq, double wq, double term, double em, const double (&P)[KP], bool ok, double) {
             L.add(lwq, term);
             nbad += ok ? 0.0 : 1.0;
             const double w = ok ? wq : 0.0;
@@ -460,8 +467,9 @@ __device__ __forceinline__ double pr_cat_softmax(double (&e)[KM], int y, int Km1
     ok = finite_d(term) && finite_d(inv);
     return ok ? term : -kInf;                      // (GlmCatModel: -inf once a logit is not finite)
 }
-// f(t, lwq, wq, term, p0, P, ok): P[k] = P(y = k + 1 | x_p)
-template <int DCMAX, int KM, class Chunk, class Term>
+// f(t, lwq, wq, term, p0, P, ok): P[k] = P(y = k + 1 | x_p).  LFIN: f takes one more argument, whether
+// every logit is finite (a -inf logit leaves the softmax, and so `ok`, finite)
+template <int DCMAX, int KM, bool LFIN = false, class Chunk, class Term>
 __device__ __forceinline__ void pr_walk_cat(const PrArgs& a, int64_t tile, int64_t slice, Chunk&& chunk, Term&& f) {
     using d2 = double __attribute__((ext_vector_type(2)));
     double* const xb = pr_area();                  // x[c][particle]
@@ -504,10 +512,17 @@ __device__ __forceinline__ void pr_walk_cat(const PrArgs& a, int64_t tile, int64
                         if (k < Km1) e[k] = fma(group_read<64>(xq, k * Dc + j), row[j], e[k]);
                 }
             }
+            [[maybe_unused]] bool lfin = true;
+            if constexpr (LFIN) {
+#pragma unroll
+                for (int k = 0; k < KM; ++k)
+                    if (k < Km1) lfin = lfin && finite_d(e[k]);
+            }
             double pz;
             bool ok;
             const double term = pr_cat_softmax<KM>(e, y, Km1, pz, ok);
-            f(p0 + q, lwq, group_read<64>(wv, q), term, pz, e, ok);
+            if constexpr (LFIN) f(p0 + q, lwq, group_read<64>(wv, q), term, pz, e, ok, lfin);
+            else f(p0 + q, lwq, group_read<64>(wv, q), term, pz, e, ok);
         }
         wave_exchange_fence();                             // (the next chunk's writes after these reads)
     }

@@ -15,8 +15,15 @@ whose term is -inf adds 0 to lpd_i and is counted in n_inf_i.  A row for which s
 non-finite mean, variance or probability reports NaN there.  The between-particle variance is accumulated around a shift
 (the first particle's mean) and merged by re-centring, never as sum w m^2 - mean^2.
 
-HierarchicalGLM predicts for EXISTING groups only (groups_new in 0..J-1): a new group's intercept would have to be drawn
-from its prior, which needs a random-number path this pass does not have.
+HierarchicalGLM's predict() is for EXISTING groups only (groups_new in 0..J-1): the moments of a new group's rows would
+have to integrate over its unseen intercept.  predict_draws() does take new groups (labels >= J): it DRAWS the intercept
+from its prior, tau_p z, per replicated data set.
+
+Posterior predictive draws (predict_draws -> PredictiveDraws; include/smcnuts_hip.h, smcn_predict_draws): draw s of S is
+one replicated data set y_rep[s, :] ~ p(. | x_{a_s}) of the m rows from ONE particle a_s, the ancestors a from systematic
+resampling of the weights with S slots (or given by the caller).  Every uniform is keyed by (seed, s, row), so a draw
+does not depend on how the work was tiled, sliced or sharded.  A draw whose law is undefined (non-finite eta, mean or
+cutpoint, mu > 2^53, an attempt cap of a rejection sampler reached) is NaN and counted in n_bad.
 """
 import numpy as np
 
@@ -157,6 +164,93 @@ def compare_heldout(a, b):
     return dict(elpd_diff=float(np.sum(d)), se_elpd_diff=_se(d), n_new=a.n_new)
 
 
+def _philox_uniform(seed, it, particle, stream, q):
+    """The library's philox_uniform (Philox4x32-10, 53-bit uniforms) for ONE key, on the host: the ancestor offset u0
+    that several shards must agree on."""
+    c = [q >> 1, particle, it, stream]
+    k0, k1, M = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & M, (p0 >> 32) ^ c[3] ^ k1, p0 & M]
+        k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+    a, b = (c[2], c[3]) if q & 1 else (c[0], c[1])
+    return ((a >> 5) * 67108864.0 + (b >> 6)) / 9007199254740992.0
+
+
+ANCESTOR_STREAM = 16
+
+
+def shard_slots(lw, S, seed, comm):
+    """Several shards, one systematic comb: (s_first, s_count, local ancestors [S] (0 outside the range), rank offsets).
+    Every rank all-gathers (largest finite log-weight, sum of exp(lw - that)); A, the ranks' cumulative weight bounds, is
+    summed on the host in rank order with the last bound +inf; rank r owns the slots whose position (s + u0) / S falls in
+    [A_r, A_r+1) and searches its own cumulative sum, offset by A_r, for them."""
+    lw = np.asarray(lw, dtype=np.float64)
+    fin = np.isfinite(lw)
+    mw = float(np.max(lw[fin])) if fin.any() else -np.inf
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        w = np.where(fin, np.exp(np.where(fin, lw - mw, 0.0)), 0.0)
+    allp = np.asarray(comm.allgather(np.array([mw, float(np.sum(w)), float(lw.shape[0])]))).reshape(-1, 3)
+    gm = float(np.max(allp[:, 0]))
+    if not np.isfinite(gm):
+        raise RuntimeError("predict_draws: no particle has a finite log-weight")
+    with np.errstate(under="ignore"):
+        tot = np.where(np.isfinite(allp[:, 0]), allp[:, 1] * np.exp(allp[:, 0] - gm), 0.0)
+    A = np.concatenate([[0.0], np.cumsum(tot)])
+    total = A[-1]
+    r = comm.rank
+    pos = (np.arange(S) + _philox_uniform(int(seed), 0, 0, ANCESTOR_STREAM, 0)) / S
+    bounds = A / total
+    bounds[-1] = np.inf
+    own = np.nonzero((pos >= bounds[r]) & (pos < bounds[r + 1]))[0]
+    anc = np.zeros(S, dtype=np.int64)
+    if own.size:
+        with np.errstate(under="ignore"):
+            cl = (A[r] + np.cumsum(w * np.exp(mw - gm))) / total
+        a = np.searchsorted(cl, pos[own], side="right")
+        last = int(np.nonzero(fin)[0][-1])
+        anc[own] = np.minimum(a, last)
+    offs = np.concatenate([[0], np.cumsum(allp[:, 2])]).astype(np.int64)
+    return (int(own[0]) if own.size else 0), int(own.size), anc, offs
+
+
+class PredictiveDraws:
+    """Posterior predictive draws at m rows: y [S][m] (row s: one replicated data set, from particle ancestors[s]),
+    n_bad the number of NaN draws (the law was undefined or a sampler gave up)."""
+
+    def __init__(self, y, ancestors, n_bad):
+        self.y = np.asarray(y, dtype=np.float64)
+        self.ancestors = np.asarray(ancestors, dtype=np.int64)
+        self.n_bad = int(n_bad)
+        self.n_draws = int(self.y.shape[0])
+
+    def mean(self):
+        """Row-wise mean over the draws (NaN draws left out; NaN for a row without any other)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ok = ~np.isnan(self.y)
+            return np.where(ok, self.y, 0.0).sum(0) / ok.sum(0)
+
+    def interval(self, level=0.9):
+        """(lo, hi): the row-wise equal-tailed `level` interval over the draws (NaN draws left out)."""
+        if not 0.0 < level < 1.0:
+            raise ValueError("PredictiveDraws.interval: level must lie in (0, 1)")
+        a = 0.5 * (1.0 - level)
+        out = np.full((2, self.y.shape[1]), np.nan)
+        for i in range(self.y.shape[1]):
+            col = self.y[:, i]
+            col = col[~np.isnan(col)]
+            if col.size:
+                out[:, i] = np.quantile(col, [a, 1.0 - a])
+        return out[0], out[1]
+
+    def pvalue(self, stat, y_obs):
+        """The share of the draws with stat(y_rep) >= stat(y_obs) (draws whose statistic is NaN left out)."""
+        t = np.array([float(stat(r)) for r in self.y])
+        t0 = float(stat(np.asarray(y_obs, dtype=np.float64)))
+        ok = ~np.isnan(t)
+        return float(np.mean(t[ok] >= t0)) if ok.any() else float("nan")
+
+
 class PredictMixin:
     """predict / predict_loglik / predict_partials of GLMTarget, HierarchicalGLM, CategoricalRegression and
     OrdinalRegression.  Every argument check runs on the host, before a context exists."""
@@ -168,8 +262,9 @@ class PredictMixin:
             return "ord", self.n_classes
         return "glm", 0
 
-    def _predict_block(self, X_new, y_new=None, groups_new=None):
-        """(block, has_y): the new rows as the model's data block without the priors, checked."""
+    def _predict_block(self, X_new, y_new=None, groups_new=None, new_groups=False):
+        """(block, has_y): the new rows as the model's data block without the priors, checked.  new_groups (predict_draws):
+        labels >= J name new groups; such rows carry group 0 in the block and (block, has_y, labels) is returned."""
         name = type(self).__name__
         hier = self.model_id == _capi.MODEL_HGLM
         X = np.asarray(X_new, dtype=np.float64)
@@ -192,7 +287,13 @@ class PredictMixin:
                     not (np.issubdtype(g.dtype, np.integer) or np.issubdtype(g.dtype, np.floating)):
                 raise ValueError(f"{name}.predict: groups_new must be a vector of m = {m} integers")
             gf = g.astype(np.float64)
-            if not np.all(np.isfinite(gf) & (gf == np.floor(gf)) & (gf >= 0) & (gf < self.n_groups)):
+            if new_groups:
+                if not np.all(np.isfinite(gf) & (gf == np.floor(gf)) & (gf >= 0) & (gf < 2.0 ** 32)):
+                    raise ValueError(f"{name}.predict_draws: groups_new must be labels in 0..2^32-1 (below "
+                                     f"{self.n_groups}: a fitted group; from {self.n_groups}: a new group)")
+                labels = gf.astype(np.int64)
+                gf = np.where(gf < self.n_groups, gf, 0.0)
+            elif not np.all(np.isfinite(gf) & (gf == np.floor(gf)) & (gf >= 0) & (gf < self.n_groups)):
                 raise ValueError(f"{name}.predict: groups_new must be existing groups 0..{self.n_groups - 1} "
                                  "(predictions for new, unseen groups are not implemented)")
         elif groups_new is not None:
@@ -223,7 +324,10 @@ class PredictMixin:
         nh = 3 if self.model_id == _capi.MODEL_ORDINAL else (5 if hier else 4)
         head = np.array(self.model_data[:nh], dtype=np.float64)
         head[1] = float(m)
-        return np.concatenate([head, y, gf if hier else [], X.reshape(-1)]), has_y
+        block = np.concatenate([head, y, gf if hier else [], X.reshape(-1)])
+        if new_groups:
+            return block, has_y, (labels if hier else None)
+        return block, has_y
 
     def _predict_points(self, x):
         x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
@@ -263,3 +367,36 @@ class PredictMixin:
         part = self.predict_partials(x, X_new, y_new, groups_new, logw)
         kind, K = self._predict_kind()
         return combine_predict_partials([part], kind, K, y_new is not None)
+
+    def _draws_args(self, X_new, n_draws, groups_new, ancestors, M):
+        """predict_draws' host checks -> (block, labels, S, ancestors)."""
+        name = type(self).__name__
+        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or not 1 <= n_draws < 2 ** 31:
+            raise ValueError(f"{name}.predict_draws: n_draws must be an integer in 1..2^31-1")
+        S = int(n_draws)
+        if groups_new is not None and self.model_id != _capi.MODEL_HGLM:
+            raise ValueError(f"{name}.predict_draws: groups_new is for HierarchicalGLM only")
+        block, _, labels = self._predict_block(X_new, None, groups_new, new_groups=True)
+        if labels is not None and not np.any(labels >= self.n_groups):
+            labels = None
+        if ancestors is not None:
+            a = np.asarray(ancestors)
+            if a.ndim != 1 or a.shape[0] != S or a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"{name}.predict_draws: ancestors must be a vector of n_draws = {S} integers")
+            if M is not None and not np.all((a >= 0) & (a < M)):
+                raise ValueError(f"{name}.predict_draws: ancestors must be particles 0..{M - 1}")
+            ancestors = a.astype(np.int64)
+        return block, labels, S, ancestors
+
+    def predict_draws(self, x, X_new, n_draws, seed=0, groups_new=None, logw=None, ancestors=None):
+        """n_draws replicated data sets at the new rows from the weighted points (x [M, D], logw unnormalised or None
+        for equal weights; ancestors: the particle of each draw instead of the systematic resampling) ->
+        PredictiveDraws.  HierarchicalGLM: groups_new labels >= J are NEW groups, their intercept drawn per data set."""
+        x2 = self._predict_points(x)
+        M = x2.shape[0]
+        block, labels, S, ancestors = self._draws_args(X_new, n_draws, groups_new, ancestors, M)
+        if logw is not None and np.shape(logw) != (M,):
+            raise ValueError(f"{type(self).__name__}.predict_draws: logw must hold one log-weight per row of x")
+        ctx = self._context(M)
+        ctx.predict_set_data(block, False)
+        return PredictiveDraws(*ctx.predict_draws(S, seed, x2, logw, ancestors, labels))

@@ -556,6 +556,53 @@ class SMCSampler:
             return combine_predict_partials([p.reshape(part.shape) for p in allp], kind, K, has_y)
         return combine_predict_partials([part], kind, K, has_y)
 
+    def predict_draws(self, X_new=None, n_draws=1000, seed=None, groups_new=None):
+        """Posterior predictive draws (predict.PredictiveDraws: n_draws replicated data sets at the rows X_new, each from
+        one particle of the final generation chosen by systematic resampling of its weights), after sample() /
+        finalise().  X_new=None: the training rows (for HierarchicalGLM with their groups).  seed=None: derived from the
+        sampler's rng.  Several shards: one host all-gather of the ranks' weight totals assigns every rank the slots of
+        the comb that fall in its share, each rank draws its own, one host all-gather assembles [S][m]."""
+        from .predict import PredictiveDraws, shard_slots
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError("predict_draws(): the asymptotic L-kernel's estimates pool generations; predictions "
+                                      "over the pooled generations are not implemented")
+        if not hasattr(self.target, "predict_draws"):
+            raise NotImplementedError(f"{type(self.target).__name__}: posterior predictive draws are implemented for "
+                                      "GLMTarget, HierarchicalGLM, CategoricalRegression and OrdinalRegression")
+        if X_new is None:
+            X_new = self.target.X
+            if groups_new is None and hasattr(self.target, "groups"):
+                groups_new = self.target.groups
+        block, labels, S, _ = self.target._draws_args(X_new, n_draws, groups_new, None, None)
+        if not self._finalised:
+            raise RuntimeError("predict_draws(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"predict_draws(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles "
+                               "do not target the posterior")
+        if seed is None:                    # (every rank holds the same rng / seed: the same value everywhere)
+            if self.rng is not None:
+                seed = int(self.rng.integers(0, 2 ** 63))
+            else:
+                self._draws_calls = getattr(self, "_draws_calls", 0) + 1
+                seed = (self.seed * 0x9E3779B97F4A7C15 + self._draws_calls) % 2 ** 64
+        ctx = self.samples.ctx
+        ctx.call("smcn_synchronize")
+        ctx.predict_set_data(block, False)
+        if self.comm.world_size == 1:
+            return PredictiveDraws(*ctx.predict_draws(S, seed, new_group=labels))
+        m = int(block[1])
+        _, lw, _ = ctx.get_state(x=False)
+        s0, n, anc, offs = shard_slots(lw, S, seed, self.comm)
+        mine = np.zeros(S * m + S + 1)
+        if n:
+            y, _, nbad = ctx.predict_draws(S, seed, ancestors=anc, new_group=labels, s_first=s0, s_count=n)
+            mine[s0 * m:(s0 + n) * m] = y.reshape(-1)
+            mine[S * m + s0:S * m + s0 + n] = anc[s0:s0 + n] + offs[self.comm.rank]
+            mine[-1] = nbad
+        allp = np.asarray(self.comm.allgather(mine)).reshape(self.comm.world_size, -1)
+        tot = allp.sum(0)           # (every slot has one owner; the others hold zeros there)
+        return PredictiveDraws(tot[:S * m].reshape(S, m), tot[S * m:S * m + S].astype(np.int64), int(tot[-1]))
+
     def sample(self, show_progress=True):
         start_time = time()
         if self.device_resident and not self._host_loop_used:
