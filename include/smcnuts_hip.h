@@ -572,6 +572,48 @@ int smcn_predict_draws(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, cons
                        double* y_out /* [s_count][m] */, int64_t* ancestors_out /* [s_count] */, int64_t* n_bad_out);
 int smcn_predict_draws_last_ms(const smcn_ctx* ctx, double* ms);
 
+/* ---- posterior summaries: weighted quantiles and tail masses of the constrained coordinates (every model) ----
+ * Definition.  For a constrained coordinate with values v_i and weights w_i >= 0 of total W, and p in (0, 1]:
+ *   Q(p) = min { v_j : sum over {i : v_i <= v_j} of w_i >= p W }     (the inverse of the weighted empirical CDF)
+ *   F(t) = (sum over {i : v_i <= t} of w_i) / W
+ * A quantile is one of the particles' own values.  Particles of zero weight never contribute; +-inf sort at the ends;
+ * -0.0 and +0.0 are equal; a NaN in a particle of positive weight is reported by a flag per coordinate.
+ * Masses are integers: w_i / W is converted once to units of 2^-52 (rounded to nearest, at least one unit for a positive
+ * weight), and every sum is an unsigned 64-bit integer sum -- exact in any order, below 2^53 for any population, so also
+ * exact as the doubles these entry points return.  A result therefore depends on the multiset of (value, weight) pairs
+ * alone: not on the order of the particles or the launch geometry; every shard of a run returns the same bits.
+ * Selection is a radix select on the order-preserving key of a double (non-negative: sign bit flipped; negative: all
+ * bits inverted), most significant byte first: 8 passes, digit k of a key being its byte 7 - k.
+ *
+ * smcn_summary_begin stages a population: x == v == NULL the resident particles and log-weights (M = N, logw = NULL)
+ * through the model's constrain path; x [M][D] unconstrained points through the same path; v [M][Dv] values that are
+ * already constrained (host-evaluated targets).  logw == NULL with x or v: equal weights.  head_out: [largest finite
+ * log-weight mw, sum exp(lw - mw), sum exp(2 (lw - mw)), particles with a finite log-weight] of THIS shard.
+ * smcn_summary_weights converts the staged log-weights against the maximum and the total of ALL shards (one shard: head_out's
+ * own; several: mw = max_r mw_r, sum = sum_r s_r exp(mw_r - mw)) and returns this shard's mass in units.
+ * One shard: smcn_summary_select runs the eight passes on the device with one wait at the end.  thresholds[q] =
+ * ceil(p_q * total mass), ascending, the same for every coordinate.
+ * Several shards: per pass k = 0..7, smcn_summary_hist returns this shard's histograms, out[Dc][nl][256] doubles with
+ * nl = 1 in pass 0 (no prefix: shared by the probabilities) and nl = nq after, followed by the Dc NaN flags; the caller
+ * sums them over the shards, takes per (coordinate, probability) the first digit whose cumulative mass reaches the
+ * remaining threshold, and hands every shard the same digits and the thresholds less the mass below the digit
+ * (smcn_summary_descend, [Dc][nq] each).  Probabilities in ascending order.
+ * smcn_summary_values: the selected values out[Dc][nq] after the eighth pass and the Dc NaN flags of this shard.
+ * smcn_summary_cdf: this shard's mass at or below at[c][j], out[Dc][T] in units, followed by the Dc NaN flags.
+ * smcn_summary_last_ms: device time of the kernels since the last smcn_summary_begin (HIP events on the context's
+ * stream); smcn_summary_pass_ms: of each of the eight passes of the last selection (histogram and pick). */
+int smcn_summary_begin(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */,
+                       const double* v_or_null /* [M][Dv] */, int64_t M, int Dv, double* head_out /* [4] */);
+int smcn_summary_weights(smcn_ctx* ctx, double lw_max, double lw_sum, double* mass_out);
+int smcn_summary_select(smcn_ctx* ctx, int nq, const double* thresholds /* [nq] */);
+int smcn_summary_hist(smcn_ctx* ctx, int pass, int nq, double* out /* [Dc][nl][256] + [Dc] */);
+int smcn_summary_descend(smcn_ctx* ctx, int pass, int nq, const int32_t* digits /* [Dc][nq] */,
+                         const double* residual /* [Dc][nq] */);
+int smcn_summary_values(smcn_ctx* ctx, int nq, double* out /* [Dc][nq] */, double* nan_flags_out /* [Dc] */);
+int smcn_summary_cdf(smcn_ctx* ctx, int T, const double* at /* [Dc][T] */, double* out /* [Dc][T] + [Dc] */);
+int smcn_summary_last_ms(const smcn_ctx* ctx, double* ms);
+int smcn_summary_pass_ms(const smcn_ctx* ctx, double* ms /* [8] */);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build. */

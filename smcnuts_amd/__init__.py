@@ -13,3 +13,4 @@ from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GL
                             OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel)
 from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F401
 from .predict import Prediction, PredictiveDraws, combine_predict_partials, compare_heldout  # noqa: F401
+from .summary import PosteriorSummary  # noqa: F401

@@ -143,6 +143,15 @@ SIGNATURES = {
     "smcn_predict_draws": ([_ctx, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, _lp, _lp, C.c_int64, C.c_int64, _dp, _lp,
                             _lp], C.c_int),
     "smcn_predict_draws_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_summary_begin": ([_ctx, _dp, _dp, _dp, C.c_int64, C.c_int, _dp], C.c_int),
+    "smcn_summary_weights": ([_ctx, C.c_double, C.c_double, _dp], C.c_int),
+    "smcn_summary_select": ([_ctx, C.c_int, _dp], C.c_int),
+    "smcn_summary_hist": ([_ctx, C.c_int, C.c_int, _dp], C.c_int),
+    "smcn_summary_descend": ([_ctx, C.c_int, C.c_int, _ip, _dp], C.c_int),
+    "smcn_summary_values": ([_ctx, C.c_int, _dp, _dp], C.c_int),
+    "smcn_summary_cdf": ([_ctx, C.c_int, _dp, _dp], C.c_int),
+    "smcn_summary_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_summary_pass_ms": ([_ctx, _dp], C.c_int),
 }
 
 _lib = None
@@ -468,6 +477,68 @@ class Context:
         if rc != 0:
             raise SmcnError("smcn_predict_draws_last_ms failed")
         return ms.value
+
+    # ---- posterior summaries (every model) ---------------------------------------------
+    def summary_begin(self, x=None, logw=None, v=None):
+        """Stage a population (include/smcnuts_hip.h): x=None and v=None: the resident particles and log-weights; x [M][D]
+        unconstrained points; v [M][Dv] constrained values.  Returns (header [4] of this shard's log-weights, columns)."""
+        head = np.empty(4)
+        if x is None and v is None:
+            self.call("smcn_summary_begin", None, None, None, self.N, 0, dptr(head))
+            return head, self.Dc
+        a = np.ascontiguousarray(np.atleast_2d(x if v is None else v), dtype=np.float64)
+        lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+        if lw is not None and lw.shape != (a.shape[0],):
+            raise ValueError("logw must hold one log-weight per row of x")
+        if v is None:
+            self.call("smcn_summary_begin", dptr(a), dptr(lw), None, a.shape[0], 0, dptr(head))
+            return head, self.Dc
+        self.call("smcn_summary_begin", None, dptr(lw), dptr(a), a.shape[0], a.shape[1], dptr(head))
+        return head, a.shape[1]
+
+    def summary_weights(self, lw_max, lw_sum):
+        m = C.c_double(0.0)
+        self.call("smcn_summary_weights", float(lw_max), float(lw_sum), C.byref(m))
+        return int(m.value)
+
+    def summary_select(self, thresholds):
+        t = np.ascontiguousarray(thresholds, dtype=np.float64)
+        self.call("smcn_summary_select", t.size, dptr(t))
+
+    def summary_hist(self, k, nq, Dc):
+        out = np.empty(Dc * (1 if k == 0 else nq) * 256 + Dc)
+        self.call("smcn_summary_hist", int(k), int(nq), dptr(out))
+        return out
+
+    def summary_descend(self, k, digits, residual):
+        d = np.ascontiguousarray(digits, dtype=np.int32)
+        r = np.ascontiguousarray(residual, dtype=np.float64)
+        self.call("smcn_summary_descend", int(k), d.shape[1], iptr(d), dptr(r))
+
+    def summary_values(self, nq, Dc):
+        out, flags = np.empty((Dc, nq)), np.empty(Dc)
+        self.call("smcn_summary_values", int(nq), dptr(out), dptr(flags))
+        return out, flags
+
+    def summary_cdf(self, at):
+        at = np.ascontiguousarray(at, dtype=np.float64)
+        Dc, T = at.shape
+        out = np.empty(Dc * T + Dc)
+        self.call("smcn_summary_cdf", T, dptr(at), dptr(out))
+        return out
+
+    def summary_last_ms(self):
+        """Device time of the summary kernels since the last summary_begin (HIP events on the context's stream)."""
+        ms = C.c_double(0.0)
+        if self._lib.smcn_summary_last_ms(self._h, C.byref(ms)) != 0:
+            raise SmcnError("smcn_summary_last_ms failed")
+        return ms.value
+
+    def summary_pass_ms(self):
+        ms = np.zeros(8)
+        if self._lib.smcn_summary_pass_ms(self._h, dptr(ms)) != 0:
+            raise SmcnError("smcn_summary_pass_ms failed")
+        return ms
 
     def timers(self, reset=False):
         t = np.zeros(6)

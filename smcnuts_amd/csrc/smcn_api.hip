@@ -31,6 +31,7 @@
 #include "smcn_pointwise.hpp"
 #include "smcn_predict.hpp"
 #include "smcn_predict_draws.hpp"
+#include "smcn_quantile.hpp"
 
 using namespace smcn;
 
@@ -184,6 +185,18 @@ struct smcn_ctx {
     double* dr_buf = nullptr;
     int64_t dr_len = 0;
     double dr_ms = 0.0;
+
+    // posterior summaries (smcn_summary_*): the staged population of a call (constrained values, fixed-point weights,
+    // selection state), its histograms, and the device time of its kernels
+    double* sm_buf = nullptr;
+    int64_t sm_len = 0;
+    unsigned long long* sm_hist = nullptr;
+    int64_t sm_hist_len = 0;
+    int64_t sm_M = 0;
+    int sm_Dc = 0, sm_cur = 0, sm_stage_state = 0;    // (state: 0 nothing staged, 1 values, 2 values and weights)
+    std::vector<unsigned long long> sm_pfx_h, sm_thr_h;
+    hipEvent_t sm_ev[10] = {};
+    double sm_ms = 0.0, sm_pass_ms[8] = {};
 };
 
 #define CHECK_CTX(c)             \
@@ -742,12 +755,14 @@ static void free_all(smcn_ctx* c) {
                     c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
                     c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
                     c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->pr_md, c->dr_buf};
+                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->pr_md, c->dr_buf, c->sm_buf, c->sm_hist};
     if (c->rows_h) (void)hipHostFree(c->rows_h);
     if (c->hist_h) (void)hipHostFree(c->hist_h);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
     if (c->pw_ev0) (void)hipEventDestroy(c->pw_ev0);
     if (c->pw_ev1) (void)hipEventDestroy(c->pw_ev1);
+    for (hipEvent_t e : c->sm_ev)
+        if (e) (void)hipEventDestroy(e);
     // ONE wait for everything this context has in flight (its own stream, the history stream); the buffers below were
     // used by these streams only
     if (c->stream) (void)stream_wait(c->stream);
@@ -3465,6 +3480,292 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
 int smcn_pointwise_last_ms(const smcn_ctx* c, double* ms) {
     if (!c || !ms) return -1;
     *ms = c->pw_ms;
+    return 0;
+}
+
+}  // extern "C"
+// ---- posterior summaries: weighted quantiles and tail masses (smcn_quantile.hpp) -------------------------------------------
+namespace {
+struct SmLayout {
+    double *vals, *lw, *head, *thr_at, *out, *cdf_out;
+    u64 *fw, *tot, *pfx[2], *thr[2], *thr0, *cnt;
+    int *nan, *nan_cdf;
+};
+int64_t sm_words(int64_t M, int Dc) { return (int64_t)Dc * M + 2 * M + 48 + (int64_t)Dc * (4 + 8 * kSmMaxQ); }
+SmLayout sm_layout(const smcn_ctx* c) {
+    const int64_t M = c->sm_M, S = (int64_t)c->sm_Dc * kSmMaxQ;
+    const int Dc = c->sm_Dc;
+    SmLayout L;
+    double* p = c->sm_buf;
+    L.vals = p; p += (int64_t)Dc * M;
+    L.fw = (u64*)p; p += M;
+    L.lw = p; p += M;
+    L.head = p; p += 16;
+    L.tot = (u64*)p; p += 16;
+    L.thr0 = (u64*)p; p += 16;
+    L.nan = (int*)p; p += Dc;
+    for (int i = 0; i < 2; ++i) { L.pfx[i] = (u64*)p; p += S; }
+    for (int i = 0; i < 2; ++i) { L.thr[i] = (u64*)p; p += S; }
+    L.thr_at = p; p += S;
+    L.cnt = (u64*)p; p += S;
+    L.out = p; p += S + Dc;
+    L.nan_cdf = (int*)p; p += Dc;
+    L.cdf_out = p;                  // S + Dc
+    return L;
+}
+}  // namespace
+static int sm_events(smcn_ctx* c) {
+    for (hipEvent_t& e : c->sm_ev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    return 0;
+}
+// waits for the stream and adds the time between sm_ev[0] and sm_ev[last] to the call's device time
+static int sm_finish(smcn_ctx* c, int last) {
+    HIPC(c, stream_wait(c->stream));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->sm_ev[0], c->sm_ev[last]));
+    c->sm_ms += (double)ms;
+    return 0;
+}
+static int sm_hist_ensure(smcn_ctx* c) {
+    const int64_t n = (int64_t)c->sm_Dc * kSmMaxQ * 256 * 2 + c->sm_Dc;
+    if (n <= c->sm_hist_len) return 0;
+    if (c->sm_hist) (void)cached_free(c->sm_hist);
+    c->sm_hist = nullptr;
+    c->sm_hist_len = 0;
+    HIPC(c, dalloc(&c->sm_hist, n));
+    c->sm_hist_len = n;
+    return 0;
+}
+static dim3 sm_grid(const smcn_ctx* c) {
+    return dim3((unsigned)grid_for(c->sm_M, kSmBlock * kSmElems), (unsigned)c->sm_Dc);
+}
+// one histogram pass over the staged population with the prefixes of state set c->sm_cur
+static int sm_launch_hist(smcn_ctx* c, const SmLayout& L, int nq, int pass) {
+    const int64_t bins = (int64_t)c->sm_Dc * nq * 256;
+    HIPC(c, hipMemsetAsync(c->sm_hist, 0, sizeof(u64) * bins, c->stream));
+    sm_hist_kernel<<<sm_grid(c), kSmBlock, sizeof(u64) * nq * 256, c->stream>>>(L.vals, c->sm_M, L.fw, L.pfx[c->sm_cur], nq,
+                                                                                 pass, c->sm_hist, L.nan);
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+int smcn_summary_begin(smcn_ctx* c, const double* x, const double* logw, const double* v, int64_t M, int Dv, double* head) {
+    CHECK_CTX(c);
+    if (!head || M < 1) FAIL(c, "smcn_summary_begin: bad arguments");
+    if (x && v) FAIL(c, "smcn_summary_begin: pass x (unconstrained) or v (constrained), not both");
+    if (!x && !v && (M != c->N || logw))
+        FAIL(c, "smcn_summary_begin: the resident particles come with their resident log-weights (x = v = NULL: logw = NULL, M = N)");
+    if (v && (Dv < 1 || Dv > 65535)) FAIL(c, "smcn_summary_begin: v needs its number of columns (1 .. 65535)");
+    if (M > (int64_t)1 << 40) FAIL(c, "smcn_summary_begin: too many particles");
+    const int Dc = v ? Dv : c->Dc;
+    c->sm_stage_state = 0;
+    if (sm_words(M, Dc) > c->sm_len) {
+        if (c->sm_buf) (void)cached_free(c->sm_buf);
+        c->sm_buf = nullptr;
+        c->sm_len = 0;
+        HIPC(c, dalloc(&c->sm_buf, sm_words(M, Dc)));
+        c->sm_len = sm_words(M, Dc);
+    }
+    c->sm_M = M;
+    c->sm_Dc = Dc;
+    int rc = sm_events(c);
+    if (rc) return rc;
+    const SmLayout L = sm_layout(c);
+    const int64_t n = M * Dc;
+    if (x || v) {
+        if ((rc = ensure_stage(c, n))) return rc;
+        if (x && (rc = ensure_stage2(c, n))) return rc;
+        HIPC(c, hipMemcpyAsync(c->stage, x ? x : v, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        if (logw) HIPC(c, hipMemcpyAsync(L.lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+        else HIPC(c, hipMemsetAsync(L.lw, 0, sizeof(double) * M, c->stream));
+    }
+    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    if (x) {                    // [M][D] through the model's constrain path, then coordinate-major
+        if (has_constrain_pass(c))
+            launch_constrain_pass(c, c->stage, c->stage2, M, M, c->D, 1);
+        else
+            constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->cmodel);
+        transpose_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage2, L.vals, M, Dc);
+    } else if (v) {
+        transpose_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, L.vals, M, Dc);
+    } else {                    // the resident generation, already [D][N]
+        if (has_constrain_pass(c))
+            launch_constrain_pass(c, c->x, L.vals, M, M, 1, M);
+        else
+            sm_stage_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->x, L.vals, M, c->D, c->cmodel);
+        HIPC(c, hipMemcpyAsync(L.lw, c->logw, sizeof(double) * M, hipMemcpyDeviceToDevice, c->stream));
+    }
+    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(L.lw, M, L.head);
+    // the header's sum once more, as an integer sum: the same bits for every order of the particles
+    HIPC(c, hipMemsetAsync(L.tot, 0, sizeof(u64) * 4, c->stream));
+    sm_total_kernel<<<grid_for(M, kSmBlock), kSmBlock, 0, c->stream>>>(L.lw, M, L.head, L.tot + 2);
+    sm_total_final_kernel<<<1, 64, 0, c->stream>>>(L.tot + 2, L.head);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    HIPC(c, hipMemcpyAsync(head, L.head, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+    c->sm_ms = 0.0;
+    for (double& p : c->sm_pass_ms) p = 0.0;
+    if ((rc = sm_finish(c, 1))) return rc;
+    c->sm_stage_state = 1;
+    return 0;
+}
+
+int smcn_summary_weights(smcn_ctx* c, double lw_max, double lw_sum, double* mass) {
+    CHECK_CTX(c);
+    if (c->sm_stage_state < 1) FAIL(c, "smcn_summary_weights: call smcn_summary_begin first");
+    if (!mass || !std::isfinite(lw_max) || !(lw_sum > 0.0) || !std::isfinite(lw_sum))
+        FAIL(c, "smcn_summary_weights: bad arguments (no particle with positive weight?)");
+    const SmLayout L = sm_layout(c);
+    HIPC(c, hipMemsetAsync(L.tot, 0, sizeof(u64) * 2, c->stream));
+    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    sm_fixed_kernel<<<grid_for(c->sm_M, kSmBlock), kSmBlock, 0, c->stream>>>(L.lw, c->sm_M, lw_max, lw_sum, L.fw, L.tot);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    u64 tot = 0;
+    HIPC(c, hipMemcpyAsync(&tot, L.tot, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    int rc = sm_finish(c, 1);
+    if (rc) return rc;
+    *mass = (double)tot;
+    c->sm_stage_state = 2;
+    return 0;
+}
+
+static int sm_check_nq(smcn_ctx* c, const char* who, int nq) {
+    if (c->sm_stage_state < 2) FAIL(c, std::string(who) + ": call smcn_summary_begin and smcn_summary_weights first");
+    if (nq < 1 || nq > kSmMaxQ) FAIL(c, std::string(who) + ": 1 .. 16 probabilities");
+    return sm_hist_ensure(c);
+}
+
+int smcn_summary_select(smcn_ctx* c, int nq, const double* thr) {
+    CHECK_CTX(c);
+    int rc = sm_check_nq(c, "smcn_summary_select", nq);
+    if (rc) return rc;
+    if (!thr) FAIL(c, "smcn_summary_select: bad arguments");
+    c->sm_thr_h.assign(kSmMaxQ, 0);
+    for (int q = 0; q < nq; ++q) {
+        if (!(thr[q] >= 1.0 && thr[q] <= 9007199254740992.0) || (q && thr[q] < thr[q - 1]))
+            FAIL(c, "smcn_summary_select: thresholds are masses in 1 .. 2^53, in ascending order");
+        c->sm_thr_h[q] = (u64)thr[q];
+    }
+    const SmLayout L = sm_layout(c);
+    HIPC(c, hipMemcpyAsync(L.thr0, c->sm_thr_h.data(), sizeof(u64) * kSmMaxQ, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemsetAsync(L.nan, 0, sizeof(int) * c->sm_Dc, c->stream));
+    c->sm_cur = 0;
+    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    for (int pass = 0; pass < 8; ++pass) {
+        if ((rc = sm_launch_hist(c, L, nq, pass))) return rc;
+        sm_pick_kernel<<<c->sm_Dc * nq, 256, 0, c->stream>>>(c->sm_hist, L.pfx[c->sm_cur], L.thr[c->sm_cur], L.thr0,
+                                                             L.pfx[c->sm_cur ^ 1], L.thr[c->sm_cur ^ 1], nq, pass);
+        HIPC(c, hipGetLastError());
+        c->sm_cur ^= 1;
+        HIPC(c, hipEventRecord(c->sm_ev[pass + 1], c->stream));
+    }
+    if ((rc = sm_finish(c, 8))) return rc;
+    for (int pass = 0; pass < 8; ++pass) {
+        float ms = 0.f;
+        HIPC(c, hipEventElapsedTime(&ms, c->sm_ev[pass], c->sm_ev[pass + 1]));
+        c->sm_pass_ms[pass] = (double)ms;
+    }
+    return 0;
+}
+
+int smcn_summary_hist(smcn_ctx* c, int pass, int nq, double* out) {
+    CHECK_CTX(c);
+    int rc = sm_check_nq(c, "smcn_summary_hist", nq);
+    if (rc) return rc;
+    if (!out || pass < 0 || pass > 7) FAIL(c, "smcn_summary_hist: bad arguments");
+    const SmLayout L = sm_layout(c);
+    if (pass == 0) {
+        HIPC(c, hipMemsetAsync(L.nan, 0, sizeof(int) * c->sm_Dc, c->stream));
+        c->sm_cur = 0;
+        c->sm_pfx_h.assign((size_t)c->sm_Dc * nq, 0);
+    } else if (c->sm_pfx_h.size() != (size_t)c->sm_Dc * nq) {
+        FAIL(c, "smcn_summary_hist: passes 1 .. 7 follow smcn_summary_descend of the pass before, with the same probabilities");
+    }
+    const int64_t n = (int64_t)c->sm_Dc * (pass == 0 ? 1 : nq) * 256 + c->sm_Dc;
+    double* const dout = (double*)(c->sm_hist + (int64_t)c->sm_Dc * kSmMaxQ * 256);
+    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    if ((rc = sm_launch_hist(c, L, nq, pass))) return rc;
+    sm_export_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->sm_hist, L.pfx[c->sm_cur], L.nan, c->sm_Dc, nq, pass, dout);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    HIPC(c, hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = sm_finish(c, 1))) return rc;
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->sm_ev[0], c->sm_ev[1]));
+    c->sm_pass_ms[pass] = (double)ms;
+    return 0;
+}
+
+int smcn_summary_descend(smcn_ctx* c, int pass, int nq, const int32_t* digits, const double* residual) {
+    CHECK_CTX(c);
+    int rc = sm_check_nq(c, "smcn_summary_descend", nq);
+    if (rc) return rc;
+    const size_t S = (size_t)c->sm_Dc * nq;
+    if (!digits || !residual || pass < 0 || pass > 7 || c->sm_pfx_h.size() != S)
+        FAIL(c, "smcn_summary_descend: follows smcn_summary_hist of the same pass");
+    c->sm_thr_h.assign(S, 0);
+    for (size_t i = 0; i < S; ++i) {
+        if (digits[i] < 0 || digits[i] > 255 || !(residual[i] >= 0.0 && residual[i] <= 9007199254740992.0))
+            FAIL(c, "smcn_summary_descend: digits are 0 .. 255, residual masses 0 .. 2^53");
+        c->sm_pfx_h[i] = (pass == 0 ? 0ull : c->sm_pfx_h[i] << 8) | (u64)digits[i];
+        c->sm_thr_h[i] = (u64)residual[i];
+    }
+    const SmLayout L = sm_layout(c);
+    HIPC(c, hipMemcpyAsync(L.pfx[c->sm_cur], c->sm_pfx_h.data(), sizeof(u64) * S, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(L.thr[c->sm_cur], c->sm_thr_h.data(), sizeof(u64) * S, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
+int smcn_summary_values(smcn_ctx* c, int nq, double* out, double* nan_flags) {
+    CHECK_CTX(c);
+    int rc = sm_check_nq(c, "smcn_summary_values", nq);
+    if (rc) return rc;
+    if (!out || !nan_flags) FAIL(c, "smcn_summary_values: bad arguments");
+    const SmLayout L = sm_layout(c);
+    const int S = c->sm_Dc * nq;
+    sm_values_kernel<<<grid_for(S, 256), 256, 0, c->stream>>>(L.pfx[c->sm_cur], S, L.out);
+    sm_counts_kernel<<<grid_for(c->sm_Dc, 256), 256, 0, c->stream>>>(L.cnt, L.nan, 0, c->sm_Dc, L.out + S);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, L.out, sizeof(double) * S, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(nan_flags, L.out + S, sizeof(double) * c->sm_Dc, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
+int smcn_summary_cdf(smcn_ctx* c, int T, const double* at, double* out) {
+    CHECK_CTX(c);
+    if (c->sm_stage_state < 2) FAIL(c, "smcn_summary_cdf: call smcn_summary_begin and smcn_summary_weights first");
+    if (T < 1 || T > kSmMaxQ || !at || !out) FAIL(c, "smcn_summary_cdf: 1 .. 16 thresholds per coordinate");
+    const SmLayout L = sm_layout(c);
+    const int S = c->sm_Dc * T;
+    int* const nan = L.nan_cdf;      // (its own NaN flags: the call does not depend on a selection before it)
+    HIPC(c, hipMemcpyAsync(L.thr_at, at, sizeof(double) * S, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemsetAsync(L.cnt, 0, sizeof(u64) * S, c->stream));
+    HIPC(c, hipMemsetAsync(nan, 0, sizeof(int) * c->sm_Dc, c->stream));
+    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    sm_cdf_kernel<<<sm_grid(c), kSmBlock, 0, c->stream>>>(L.vals, c->sm_M, L.fw, L.thr_at, T, L.cnt, nan);
+    double* const dout = L.cdf_out;
+    sm_counts_kernel<<<grid_for(S + c->sm_Dc, 256), 256, 0, c->stream>>>(L.cnt, nan, S, c->sm_Dc, dout);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    HIPC(c, hipMemcpyAsync(out, dout, sizeof(double) * (S + c->sm_Dc), hipMemcpyDeviceToHost, c->stream));
+    return sm_finish(c, 1);
+}
+
+int smcn_summary_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    *ms = c->sm_ms;
+    return 0;
+}
+
+int smcn_summary_pass_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    for (int i = 0; i < 8; ++i) ms[i] = c->sm_pass_ms[i];
     return 0;
 }
 

@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from .. import _capi
+from .. import summary as _summary
 from ..predict import PredictMixin
 
 DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
@@ -82,6 +83,17 @@ class DeviceTarget:
     def pointwise(self, x, logw=None):
         self._no_pointwise()
 
+    def summary(self, x, logw=None, probs=_summary.DEFAULT_PROBS, at=None):
+        """summary.PosteriorSummary of the points x [M][D] (unconstrained) with log-weights logw (None: equal): weighted
+        quantiles at `probs` (at most 16, each in (0, 1]) and, with `at` (a scalar, [T] or [Dc][T], T <= 16), the mass at
+        or below each threshold, of every constrained coordinate -- constrained and selected on the device."""
+        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
+        if x2.ndim != 2 or x2.shape[1] != self.dim:
+            raise ValueError(f"{type(self).__name__}: x must be [{self.dim}] or [M, {self.dim}]")
+        lw = _summary.check_logw(logw, x2.shape[0])
+        probs, at = _summary.check_probs(probs), _summary.check_at(at, self.constrained_dim)
+        return _summary.target_summary(self, self._context(x2.shape[0]), np.ascontiguousarray(x2), lw, probs, at)
+
 
 class GaussianTarget(DeviceTarget):
     """prior N(0, prior_sd^2 I) x optional likelihood N(x | lik_mean 1, lik_sd^2 I)."""
@@ -147,6 +159,21 @@ class HostTarget:
 
     def pointwise(self, x, logw=None):
         DeviceTarget._no_pointwise(self)
+
+    def summary(self, x, logw=None, probs=_summary.DEFAULT_PROBS, at=None):
+        """DeviceTarget.summary with the wrapped model's own constrain() on the host and the selection on the device."""
+        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
+        if x2.ndim != 2 or x2.shape[1] != self.dim:
+            raise ValueError(f"HostTarget: x must be [{self.dim}] or [M, {self.dim}]")
+        lw = _summary.check_logw(logw, x2.shape[0])
+        probs, at = _summary.check_probs(probs), _summary.check_at(at, self.constrained_dim)
+        v = np.ascontiguousarray(np.atleast_2d(self.constrain(x2)), dtype=np.float64)
+        if v.shape != (x2.shape[0], self.constrained_dim):
+            raise ValueError(f"HostTarget: constrain() returned shape {v.shape}, not {(x2.shape[0], self.constrained_dim)}")
+        ctx = getattr(self, "_sum_ctx", None)
+        if ctx is None:
+            ctx = self._sum_ctx = _capi.Context(256, self.model_id, self.model_data, device=self.device)
+        return _summary.target_summary(self, ctx, x2, lw, probs, at, v=v)
 
     def attach(self, ctx):
         """Register the density callback with a context created for this target."""

@@ -527,6 +527,37 @@ class SMCSampler:
             return combine_pointwise_partials([p.reshape(part.shape) for p in allp])
         return combine_pointwise_partials([part])
 
+    def summary(self, probs=(0.025, 0.25, 0.5, 0.75, 0.975), at=None):
+        """Posterior summary (summary.PosteriorSummary: mean, sd, weighted quantiles at `probs`, and with `at` the mass at
+        or below each threshold, per constrained parameter) of the final generation and its weights, after sample() /
+        finalise(): selected on the device from the resident particles, nothing is downloaded but [Dc][nq] quantiles and
+        [Dc][T] masses.  Several shards: the ranks' histograms are summed through one host all-gather per pass; every
+        rank returns the same object.  A host-evaluated target's own constrain() runs on the host (as for the moments)."""
+        from . import summary as sm
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError("summary(): the asymptotic L-kernel's estimates pool generations; summaries over the "
+                                      "pooled generations are not implemented")
+        Dc = self.mean_estimate.shape[1]
+        probs, at = sm.check_probs(probs), sm.check_at(at, Dc)
+        if not self._finalised:
+            raise RuntimeError("summary(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"summary(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
+                               "target the posterior")
+        ctx, t = self.samples.ctx, self.target
+        ctx.call("smcn_synchronize")
+        if getattr(t, "host_evaluated", False) and callable(getattr(t.target, "constrain", None)):
+            x, lw, _ = ctx.get_state()
+            v = np.ascontiguousarray(t.constrain(x), dtype=np.float64)
+            q, cdf, _ = sm.device_summary(ctx, self.comm, probs, at, v=v, logw=lw)
+        else:
+            q, cdf, _ = sm.device_summary(ctx, self.comm, probs, at)
+        names = list(t.param_names())
+        if len(names) != Dc:
+            names = [f"x.{i + 1}" for i in range(Dc)]
+        return sm.PosteriorSummary(names, self.mean_estimate[self.K].copy(), np.sqrt(self.variance_estimate[self.K]),
+                                   probs, q, cdf, at, self.ess[self.K], self.N)
+
     def predict(self, X_new, y_new=None, groups_new=None):
         """Posterior predictive summaries at new rows (predict.Prediction: mean / variance or class probabilities, and with
         y_new the log predictive density of each held-out row) of the final generation and its weights, after sample() /
