@@ -73,6 +73,7 @@ struct smcn_ctx {
     uint64_t seed = 0;
     std::string err;
     std::vector<double> mdata_h;
+    RegLayout reg;              // the regression models: where things sit in mdata_h and in its image mdata (smcn_regdata.hpp)
 
     // device state, all fp64; vectors are [D][N]
     double *mdata = nullptr, *x = nullptr, *x_new = nullptr, *x_tmp = nullptr, *r = nullptr, *r_new = nullptr;
@@ -175,9 +176,10 @@ struct smcn_ctx {
     double pw_ms = 0.0;
 
     // held-out prediction (smcn_predict_*): the new rows' image [block | padding | table] as smcn_ctx_create lays out the
-    // training data, where its table starts, the number of new rows and whether they came with y
+    // training data, its layout (pr.n new rows, 0: none set) and whether they came with y
     double* pr_md = nullptr;
-    int64_t pr_md_len = 0, pr_toff = 0, pr_m = 0;
+    int64_t pr_md_len = 0;
+    RegLayout pr;
     int pr_has_y = 0;
     double pr_ms = 0.0;
 
@@ -450,7 +452,7 @@ static int with_model(smcn_ctx* c, F&& f) {
     }
     if (c->model == SMCN_MODEL_GLM) {
         // (smcn_ctx_create has checked the data and refused D > 64)
-        if (c->mdata_h[0] >= 2.0) {                       // normal / neg_binomial_2_log: D counts tau
+        if (c->reg.disp()) {                              // normal / neg_binomial_2_log: D counts tau
             // (G = 8 up to D = 8 only: GlmDispModel<8, 2>'s NUTS kernel needs 256 VGPRs + 152 B of scratch)
             if (c->D <= 8) return f(GlmDispModel<8, 1>{});
             return f(GlmDispModel<64, 1>{});
@@ -472,250 +474,6 @@ static int with_model(smcn_ctx* c, F&& f) {
     }
     if (c->model == SMCN_MODEL_HOST) FAIL(c, "host target: this entry point needs a device-native model");
     FAIL(c, "model not available in this build");
-}
-
-// SMCN_MODEL_GLM: checks the caller's data block; "" and D (tau included), or what is wrong with it
-static std::string glm_check(const double* md, int64_t len, int* D_out) {
-    const char* layout = "GLM target: data = [family, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)]";
-    const char* layout_disp = "GLM target: data = [family, n, p, intercept, s_1..s_Dc, m_tau, s_tau, y_1..y_n, "
-                              "X (n x p, row-major)] for families 2 (normal) and 3 (neg_binomial_2_log)";
-    if (len < 4) return layout;
-    const double fam = md[0], nd = md[1], pd = md[2], icd = md[3];
-    if (!(fam == 0.0 || fam == 1.0 || fam == 2.0 || fam == 3.0))
-        return "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log), or 2 (normal) or 3 (neg_binomial_2_log) "
-               "with a dispersion prior";
-    const bool disp = fam >= 2.0;
-    if (!(icd == 0.0 || icd == 1.0)) return "GLM target: intercept must be 0 or 1";
-    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd)) return "GLM target: n must be an integer >= 1";
-    if (!(pd >= 0.0 && pd <= 1048576.0 && pd == (double)(int64_t)pd)) return "GLM target: p must be an integer >= 0";
-    const int64_t n = (int64_t)nd, p = (int64_t)pd, Dc = p + (int64_t)icd, D = Dc + (disp ? 1 : 0);
-    if (Dc < 1) return "GLM target: no coefficients (p = 0 without an intercept)";
-    if (D > 64)
-        return "GLM target: the device functor covers D <= 64 coefficients; larger models run host-evaluated "
-               "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)";
-    const int64_t y0 = 4 + Dc + (disp ? 2 : 0);        // where y starts
-    if (len != y0 + n + n * p) {
-        // a block laid out for families 0 / 1 but naming a dispersion family
-        if (disp && len == 4 + Dc + n + n * p)
-            return "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log) for a block without m_tau, s_tau; "
-                   "families 2 (normal) and 3 (neg_binomial_2_log) take data = [family, n, p, intercept, s_1..s_Dc, "
-                   "m_tau, s_tau, y_1..y_n, X]";
-        return disp ? layout_disp : layout;
-    }
-    for (int64_t c = 0; c < Dc; ++c)
-        if (!(md[4 + c] > 0.0 && std::isfinite(md[4 + c]))) return "GLM target: prior sds must be finite and > 0";
-    if (disp) {
-        if (!std::isfinite(md[4 + Dc])) return "GLM target: m_tau must be finite";
-        if (!(md[5 + Dc] > 0.0 && std::isfinite(md[5 + Dc]))) return "GLM target: s_tau must be finite and > 0";
-    }
-    for (int64_t i = 0; i < n; ++i) {
-        const double y = md[y0 + i];
-        if (fam == 0.0) {
-            if (!(y == 0.0 || y == 1.0)) return "GLM target: bernoulli_logit needs y in {0, 1}";
-        } else if (fam == 2.0) {
-            if (!std::isfinite(y)) return "GLM target: normal needs finite y";
-        } else if (!(y >= 0.0 && y <= 9007199254740992.0 && y == std::floor(y))) {
-            return fam == 1.0 ? "GLM target: poisson_log needs y in {0, 1, 2, ..}"
-                              : "GLM target: neg_binomial_2_log needs y in {0, 1, 2, .., 2^53}";
-        }
-    }
-    for (int64_t t = 0; t < n * p; ++t)
-        if (!std::isfinite(md[y0 + n + t])) return "GLM target: X must be finite";
-    *D_out = (int)D;
-    return "";
-}
-
-// SMCN_MODEL_HGLM: checks the caller's data block; "" and D, or what is wrong with it
-static std::string hglm_check(const double* md, int64_t len, int* D_out) {
-    const char* layout = "hierarchical GLM target: data = [family, n, p, intercept, J, s_1..s_Dc, s_tau, (m_d, s_d: families "
-                         "2, 3), y_1..y_n, g_1..g_n, X (n x p, row-major)]";
-    if (len < 5) return layout;
-    const double fam = md[0], nd = md[1], pd = md[2], icd = md[3], Jd = md[4];
-    if (!(fam == 0.0 || fam == 1.0 || fam == 2.0 || fam == 3.0))
-        return "hierarchical GLM target: family must be 0 (bernoulli_logit), 1 (poisson_log), 2 (normal) or 3 "
-               "(neg_binomial_2_log)";
-    const bool disp = fam >= 2.0;
-    if (!(icd == 0.0 || icd == 1.0)) return "hierarchical GLM target: intercept must be 0 or 1";
-    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd))
-        return "hierarchical GLM target: n must be an integer >= 1";
-    if (!(pd >= 0.0 && pd <= 1048576.0 && pd == (double)(int64_t)pd))
-        return "hierarchical GLM target: p must be an integer >= 0";
-    if (!(Jd >= 1.0 && Jd <= 1048576.0 && Jd == (double)(int64_t)Jd))
-        return "hierarchical GLM target: J must be an integer >= 1 (the number of groups)";
-    const int64_t n = (int64_t)nd, p = (int64_t)pd, Dc = p + (int64_t)icd, J = (int64_t)Jd;
-    const int64_t D = Dc + J + 1 + (disp ? 1 : 0);
-    if (D > 64)
-        return "hierarchical GLM target: the device functor covers D = Dc + J + 1 (+ 1) <= 64 coordinates; larger models "
-               "run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
-               "HostTarget)";
-    const int64_t head = hglm_head(Dc, disp);
-    if (len != head + 2 * n + n * p) return layout;
-    for (int64_t c = 0; c < Dc; ++c)
-        if (!(md[5 + c] > 0.0 && std::isfinite(md[5 + c]))) return "hierarchical GLM target: prior sds must be finite and > 0";
-    if (!(md[5 + Dc] > 0.0 && std::isfinite(md[5 + Dc]))) return "hierarchical GLM target: s_tau must be finite and > 0";
-    if (disp) {
-        if (!std::isfinite(md[6 + Dc])) return "hierarchical GLM target: m_d must be finite";
-        if (!(md[7 + Dc] > 0.0 && std::isfinite(md[7 + Dc]))) return "hierarchical GLM target: s_d must be finite and > 0";
-    }
-    for (int64_t i = 0; i < n; ++i) {
-        const double y = md[head + i];
-        if (fam == 0.0) {
-            if (!(y == 0.0 || y == 1.0)) return "hierarchical GLM target: bernoulli_logit needs y in {0, 1}";
-        } else if (fam == 2.0) {
-            if (!std::isfinite(y)) return "hierarchical GLM target: normal needs finite y";
-        } else if (!(y >= 0.0 && y <= 9007199254740992.0 && y == std::floor(y))) {
-            return fam == 1.0 ? "hierarchical GLM target: poisson_log needs y in {0, 1, 2, ..}"
-                              : "hierarchical GLM target: neg_binomial_2_log needs y in {0, 1, 2, .., 2^53}";
-        }
-    }
-    for (int64_t i = 0; i < n; ++i) {
-        const double g = md[head + n + i];
-        if (!(g >= 0.0 && g < Jd && g == std::floor(g)))
-            return "hierarchical GLM target: every group index g must be an integer in [0, J)";
-    }
-    for (int64_t t = 0; t < n * p; ++t)
-        if (!std::isfinite(md[head + 2 * n + t])) return "hierarchical GLM target: X must be finite";
-    *D_out = (int)D;
-    return "";
-}
-
-// SMCN_MODEL_CATEGORICAL: checks the caller's data block; "" and D, or what is wrong with it
-static std::string cat_check(const double* md, int64_t len, int* D_out) {
-    const char* layout = "categorical target: data = [K, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], "
-                         "D = (K - 1) (p + intercept)";
-    if (len < 4) return layout;
-    const double Kd = md[0], nd = md[1], pd = md[2], icd = md[3];
-    if (!(Kd >= 2.0 && Kd <= (double)kCatMaxClasses && Kd == std::floor(Kd)))
-        return "categorical target: K must be an integer in [2, 16] (the device functor holds up to 16 classes; more "
-               "run host-evaluated: SMCN_MODEL_HOST + smcn_set_host_target, any object with logpdf / logpdfgrad "
-               "through HostTarget)";
-    if (!(icd == 0.0 || icd == 1.0)) return "categorical target: intercept must be 0 or 1";
-    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd)) return "categorical target: n must be an integer >= 1";
-    if (!(pd >= 0.0 && pd <= 1048576.0 && pd == (double)(int64_t)pd)) return "categorical target: p must be an integer >= 0";
-    const int64_t n = (int64_t)nd, p = (int64_t)pd, Dc = p + (int64_t)icd, D = ((int64_t)Kd - 1) * Dc;
-    if (Dc < 1) return "categorical target: no coefficients (p = 0 without an intercept)";
-    if (D > 64)
-        return "categorical target: the device functor covers D = (K - 1) (p + intercept) <= 64 coefficients; larger "
-               "models run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad "
-               "through HostTarget)";
-    if (len != 4 + D + n + n * p) return layout;
-    for (int64_t c = 0; c < D; ++c)
-        if (!(md[4 + c] > 0.0 && std::isfinite(md[4 + c]))) return "categorical target: prior sds must be finite and > 0";
-    for (int64_t i = 0; i < n; ++i) {
-        const double y = md[4 + D + i];
-        if (!(y >= 0.0 && y < Kd && y == std::floor(y))) return "categorical target: every label y must be an integer in [0, K)";
-    }
-    for (int64_t t = 0; t < n * p; ++t)
-        if (!std::isfinite(md[4 + D + n + t])) return "categorical target: X must be finite";
-    *D_out = (int)D;
-    return "";
-}
-
-// SMCN_MODEL_ORDINAL: checks the caller's data block; "" and D, or what is wrong with it
-static std::string ord_check(const double* md, int64_t len, int* D_out) {
-    const char* layout = "ordinal target: data = [K, n, p, s_1..s_p, t_1..t_{K-1}, y_1..y_n, X (n x p, row-major)], "
-                         "D = p + K - 1";
-    if (len < 3) return layout;
-    const double Kd = md[0], nd = md[1], pd = md[2];
-    if (!(Kd >= 2.0 && Kd == std::floor(Kd))) return "ordinal target: K must be an integer >= 2";
-    if (!(nd >= 1.0 && nd <= 2147483647.0 && nd == (double)(int64_t)nd)) return "ordinal target: n must be an integer >= 1";
-    if (!(pd >= 0.0 && pd == std::floor(pd))) return "ordinal target: p must be an integer >= 0";
-    if (pd + Kd - 1.0 > 64.0)
-        return "ordinal target: the device functor covers D = p + K - 1 <= 64 coordinates; larger models run "
-               "host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
-               "HostTarget)";
-    const int64_t n = (int64_t)nd, p = (int64_t)pd, D = p + (int64_t)Kd - 1;
-    if (len != 3 + D + n + n * p) return layout;
-    for (int64_t c = 0; c < D; ++c)
-        if (!(md[3 + c] > 0.0 && std::isfinite(md[3 + c])))
-            return "ordinal target: prior sds (s for the coefficients, t for the cutpoints) must be finite and > 0";
-    for (int64_t i = 0; i < n; ++i) {
-        const double y = md[3 + D + i];
-        if (!(y >= 0.0 && y < Kd && y == std::floor(y))) return "ordinal target: every label y must be an integer in [0, K)";
-    }
-    for (int64_t t = 0; t < n * p; ++t)
-        if (!std::isfinite(md[3 + D + n + t])) return "ordinal target: X must be finite";
-    *D_out = (int)D;
-    return "";
-}
-
-// The table a GLM-type model's functor reads, behind the caller's data block: `mup` becomes [block | padding | table].
-// smcn_ctx_create repacks the training design with it, smcn_predict_set_data the new rows.
-static void repack_model_table(int model_id, int dim, const double* model_data, int64_t model_data_len,
-                               std::vector<double>& mup) {
-    // GLM: behind the caller's data the table GlmModel / GlmDispModel read (smcn_models.hpp) -- a row per observation,
-    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1)], at a 128-byte boundary, zero rows up to a
-    // multiple of 64 observations.  The row width follows the Dc coefficients; the dispersion families' block has m_tau
-    // and s_tau between the prior sds and y (HD: the doubles before y).
-    if (model_id == SMCN_MODEL_GLM) {
-        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
-        const int64_t Dc = p + ic, HD = model_data[0] >= 2.0 ? Dc + 2 : Dc;
-        const int RS = glm_row_doubles((int)Dc);
-        const int64_t t0 = glm_table_offset(HD, n, p), rows = glm_table_rows(n);
-        mup.assign(t0 + rows * RS, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            if (ic) row[0] = 1.0;
-            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + HD + n + i * p + j];
-            const double y = model_data[4 + HD + i];
-            row[RS - 2] = y;
-            row[RS - 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
-        }
-    }
-    // hierarchical GLM: the table GlmHierModel reads -- GlmModel's row with the group index behind y and lgamma(y + 1),
-    // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1), g_i, 0], at a 128-byte boundary, zero
-    // rows up to a multiple of 64 observations
-    if (model_id == SMCN_MODEL_HGLM) {
-        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
-        const int64_t Dc = p + ic, head = hglm_head(Dc, model_data[0] >= 2.0);
-        const int RS = hglm_row_doubles((int)Dc), DP = RS - 4;
-        const int64_t t0 = hglm_table_offset(head, n, p), rows = glm_table_rows(n);
-        mup.assign(t0 + rows * RS, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            if (ic) row[0] = 1.0;
-            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[head + 2 * n + i * p + j];
-            const double y = model_data[head + i];
-            row[DP] = y;
-            row[DP + 1] = model_data[0] == 2.0 ? 0.0 : std::lgamma(y + 1.0);   // (normal: unused, and y may be negative)
-            row[DP + 2] = model_data[head + n + i];
-        }
-    }
-    // categorical: GlmModel's table with the row width from the Dc columns and the label in the y slot, [1 (intercept),
-    // X_i1 .. X_ip, 0 .. (to an even count), y_i, 0] (GlmCatModel)
-    if (model_id == SMCN_MODEL_CATEGORICAL) {
-        const int64_t n = (int64_t)model_data[1], p = (int64_t)model_data[2], ic = (int64_t)model_data[3];
-        const int64_t D = dim;
-        const int RS = glm_row_doubles((int)(p + ic));
-        const int64_t t0 = glm_table_offset(D, n, p), rows = glm_table_rows(n);
-        mup.assign(t0 + rows * RS, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            if (ic) row[0] = 1.0;
-            for (int64_t j = 0; j < p; ++j) row[ic + j] = model_data[4 + D + n + i * p + j];
-            row[RS - 2] = model_data[4 + D + i];
-        }
-    }
-    // ordinal: GlmModel's table with the row width from the p columns and the label in the y slot, [X_i1 .. X_ip, 0 .. (to
-    // an even count), y_i, 0], then the K class counts n_0..n_{K-1} (GlmOrdModel)
-    if (model_id == SMCN_MODEL_ORDINAL) {
-        const int64_t K = (int64_t)model_data[0], n = (int64_t)model_data[1], p = (int64_t)model_data[2];
-        const int64_t D = dim;
-        const int RS = glm_row_doubles((int)p);
-        const int64_t t0 = glm_table_offset(D, n, p), c0 = ord_counts_offset(D, n, p);
-        mup.assign(c0 + K, 0.0);
-        std::copy(model_data, model_data + model_data_len, mup.begin());
-        for (int64_t i = 0; i < n; ++i) {
-            double* row = mup.data() + t0 + i * RS;
-            for (int64_t j = 0; j < p; ++j) row[j] = model_data[3 + D + n + i * p + j];
-            const double y = model_data[3 + D + i];
-            row[RS - 2] = y;
-            mup[c0 + (int64_t)y] += 1.0;
-        }
-    }
 }
 
 extern "C" {
@@ -814,40 +572,17 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
         case SMCN_MODEL_ARMA: c->D = 4; break;
         case SMCN_MODEL_PRMWCD: c->D = (int)model_data[1] + 1; break;
         case SMCN_MODEL_HOST: c->D = (int)model_data[0]; break;
-        case SMCN_MODEL_GLM: {
-            const std::string why = glm_check(model_data, model_data_len, &c->D);
-            if (!why.empty()) {
-                g_create_error = "smcn_ctx_create: " + why;
-                delete c;
-                return -1;
-            }
-            break;
-        }
-        case SMCN_MODEL_HGLM: {
-            const std::string why = hglm_check(model_data, model_data_len, &c->D);
-            if (!why.empty()) {
-                g_create_error = "smcn_ctx_create: " + why;
-                delete c;
-                return -1;
-            }
-            break;
-        }
-        case SMCN_MODEL_CATEGORICAL: {
-            const std::string why = cat_check(model_data, model_data_len, &c->D);
-            if (!why.empty()) {
-                g_create_error = "smcn_ctx_create: " + why;
-                delete c;
-                return -1;
-            }
-            break;
-        }
+        case SMCN_MODEL_GLM:
+        case SMCN_MODEL_HGLM:
+        case SMCN_MODEL_CATEGORICAL:
         case SMCN_MODEL_ORDINAL: {
-            const std::string why = ord_check(model_data, model_data_len, &c->D);
+            const std::string why = reg_check(model_id, model_data, model_data_len, &c->reg);
             if (!why.empty()) {
                 g_create_error = "smcn_ctx_create: " + why;
                 delete c;
                 return -1;
             }
+            c->D = c->reg.D;
             break;
         }
         default:
@@ -858,7 +593,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     c->Dc = c->D;
     // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
     // constrain_coord applies to arma's log sigma (the other models keep their own id)
-    c->cmodel = (model_id == SMCN_MODEL_GLM && model_data[0] >= 2.0) ? SMCN_MODEL_ARMA : model_id;
+    c->cmodel = (model_id == SMCN_MODEL_GLM && c->reg.disp()) ? SMCN_MODEL_ARMA : model_id;
     // hierarchical GLM, ordinal: the constrained space is not coordinate-wise; the moment kernels read a constrained copy
     // of the population (model_constrained) with the identity
     if (model_id == SMCN_MODEL_HGLM || model_id == SMCN_MODEL_ORDINAL) c->cmodel = SMCN_MODEL_HOST;
@@ -895,7 +630,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
                     mup.push_back(i < nobs ? (j < C ? model_data[4 + nobs + (size_t)i * C + j] : (j == RS - 1 ? model_data[4 + i] : 0.0)) : 0.0);
         }
     }
-    repack_model_table(model_id, c->D, model_data, model_data_len, mup);
+    if (c->reg.rlen) reg_repack(c->reg, model_data, mup);   // (a regression model: reg_check has filled its layout)
     const int64_t mlen = (int64_t)mup.size();
     A_(mdata, mlen + 32);   // padded: the lane kernels read the series one chunk ahead
     A_(x, ND); A_(x_new, ND); A_(x_tmp, ND); A_(r, ND); A_(r_new, ND);
@@ -1051,11 +786,10 @@ static bool has_constrain_pass(const smcn_ctx* c) { return c->model == SMCN_MODE
 static void launch_constrain_pass(smcn_ctx* c, const double* x, double* out, int64_t M, int64_t Np, int64_t si,
                                   int64_t sc) {
     if (c->model == SMCN_MODEL_ORDINAL)
-        ord_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D, (int)c->mdata_h[2], si, sc);
+        ord_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D, (int)c->reg.p, si, sc);
     else
         hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D,
-                                                                       (int)c->mdata_h[2] + (int)c->mdata_h[3],
-                                                                       (int)c->mdata_h[4], si, sc);
+                                                                       c->reg.Dc, (int)c->reg.J, si, sc);
 }
 // SMCN_MODEL_HGLM / SMCN_MODEL_ORDINAL: the constrained population of ngen consecutive generations ([ngen][D][N] from x)
 // into c->cstage, on the context's stream; *out is what the moment kernels then read with the identity (c->cmodel)
@@ -1655,12 +1389,14 @@ struct resume_model;
 template <int NOBS, int C_, int RED, int LEVELS, bool FAST>
 struct resume_model<PrmwcdDistModel<8, NOBS, C_, RED, LEVELS, FAST>> { using type = PrmwcdDistModel<64, NOBS, C_, 2, 5, FAST>; };
 
-// Grows one of the context's scratch buffers (nuts_scratch, n2_ovf) to at least `need` doubles.
+// Grows one of the context's scratch buffers (nuts_scratch, n2_ovf, pw_buf, pr_md, dr_buf) to at least `need` doubles;
+// holds nothing (len = 0) if the allocation fails.
 static int grow_scratch(smcn_ctx* c, double*& buf, int64_t& len, int64_t need) {
     if (need <= len) return 0;
     HIPC(c, stream_wait(c->stream));     // (the old buffer may still be in use)
     if (buf) (void)cached_free(buf);
     buf = nullptr;
+    len = 0;
     HIPC(c, dalloc(&buf, need));
     len = need;
     return 0;
@@ -3353,37 +3089,64 @@ static const char* kPwScope =
     "pointwise criteria cover the SMCN_MODEL_GLM families (bernoulli_logit, poisson_log, normal, neg_binomial_2_log) "
     "only; hierarchical, categorical, ordinal, arma, PRMwCD, Gaussian and host-evaluated targets are not implemented";
 
-static PwArgs pw_args(const smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
+// the GLM walk's arguments over the image `md` of the block L describes (the training data, or the new rows)
+static PwArgs pw_args(const RegLayout& L, const double* md, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
     PwArgs a;
-    a.md = c->mdata;
+    a.md = md;
     a.x = x;
     a.rs = rs;
     a.cs = cs;
     a.M = M;
     a.cps = cps;
-    a.fam = (int)c->mdata_h[0];
-    a.n = (int)c->mdata_h[1];
-    a.p = (int)c->mdata_h[2];
-    a.Dc = a.p + (int)c->mdata_h[3];
+    a.fam = L.fam;
+    a.n = (int)L.n;
+    a.p = (int)L.p;
+    a.Dc = L.Dc;
     return a;
 }
-static int pw_ensure(smcn_ctx* c, int64_t n) {
-    if (n <= c->pw_len) return 0;
-    if (c->pw_buf) (void)cached_free(c->pw_buf);
-    c->pw_buf = nullptr;
-    c->pw_len = 0;
-    HIPC(c, dalloc(&c->pw_buf, n));
-    c->pw_len = n;
-    return 0;
-}
-// f(row capacity, dispersion family) for the context's model: rows of DP <= 16 / 32 / 64 doubles
+static int pw_ensure(smcn_ctx* c, int64_t n) { return grow_scratch(c, c->pw_buf, c->pw_len, n); }
+// f(row capacity) for table rows of Dc columns: DP <= 16 / 32 / 64 doubles
 template <class F>
-static void pw_dispatch(const PwArgs& a, F&& f) {
-    const int DP = (a.Dc + 1) & ~1;
-    const auto fam = [&](auto dp) { a.fam >= 2 ? f(dp, std::true_type{}) : f(dp, std::false_type{}); };
-    if (DP <= 16) fam(std::integral_constant<int, 16>{});
-    else if (DP <= 32) fam(std::integral_constant<int, 32>{});
-    else fam(std::integral_constant<int, 64>{});
+static void row_cap(int Dc, F&& f) {
+    const int DP = (Dc + 1) & ~1;
+    if (DP <= 16) f(std::integral_constant<int, 16>{});
+    else if (DP <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+// f(row capacity, dispersion family)
+template <class F>
+static void row_cap_disp(int Dc, int fam, F&& f) {
+    row_cap(Dc, [&](auto dp) { fam >= 2 ? f(dp, std::true_type{}) : f(dp, std::false_type{}); });
+}
+// categorical: f(row capacity, non-reference classes), the pairs that cover (K - 1) Dc <= 64
+template <class F>
+static void cat_cap(int Dc, F&& f) {
+    using std::integral_constant;
+    if (Dc <= 4) f(integral_constant<int, 4>{}, integral_constant<int, 15>{});
+    else if (Dc <= 8) f(integral_constant<int, 8>{}, integral_constant<int, 12>{});
+    else if (Dc <= 16) f(integral_constant<int, 16>{}, integral_constant<int, 7>{});
+    else if (Dc <= 32) f(integral_constant<int, 32>{}, integral_constant<int, 3>{});
+    else f(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+}
+// The particles a post-fit entry point works on: the caller's x [M][D] uploaded to c->stage, with logw (or zeros) in
+// `lw_stage` -- or, x = NULL, the resident ones with their resident log-weights.
+struct Particles {
+    const double* xd;
+    int64_t rs, cs;
+    double* lw;
+};
+static int stage_particles(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* lw_stage, Particles* P) {
+    if (!x) {
+        *P = {c->x, 1, c->N, c->logw};
+        return 0;
+    }
+    const int rc = ensure_stage(c, M * c->D);
+    if (rc) return rc;
+    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+    if (logw) HIPC(c, hipMemcpyAsync(lw_stage, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+    else HIPC(c, hipMemsetAsync(lw_stage, 0, sizeof(double) * M, c->stream));
+    *P = {c->stage, c->D, 1, lw_stage};
+    return 0;
 }
 
 extern "C" {
@@ -3392,7 +3155,7 @@ int smcn_pointwise_dims(const smcn_ctx* cc, int64_t* n_obs, int* n_cols) {
     smcn_ctx* c = const_cast<smcn_ctx*>(cc);
     if (!c) return -1;
     if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_dims: ") + kPwScope);
-    if (n_obs) *n_obs = (int64_t)c->mdata_h[1];
+    if (n_obs) *n_obs = c->reg.n;
     if (n_cols) *n_cols = kPwCols;
     return 0;
 }
@@ -3401,7 +3164,7 @@ int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) 
     CHECK_CTX(c);
     if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_loglik: ") + kPwScope);
     if (!x || !out || M < 1) FAIL(c, "smcn_pointwise_loglik: bad arguments");
-    const int64_t n = (int64_t)c->mdata_h[1], tiles = (n + 63) / 64;
+    const int64_t n = c->reg.n, tiles = (n + 63) / 64;
     int64_t cps = 1;
     const int64_t slices = pointwise_slices(M, n, &cps);
     if (tiles * slices > 2147483647LL) FAIL(c, "smcn_pointwise_loglik: too many observations");
@@ -3409,8 +3172,8 @@ int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) 
     if (rc) return rc;
     if ((rc = pw_ensure(c, M * n))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
-    const PwArgs a = pw_args(c, c->stage, c->D, 1, M, cps);
-    pw_dispatch(a, [&](auto dp, auto disp) {
+    const PwArgs a = pw_args(c->reg, c->mdata, c->stage, c->D, 1, M, cps);
+    row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
         pointwise_loglik_kernel<decltype(dp)::value, decltype(disp)::value>
             <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, c->pw_buf);
     });
@@ -3425,7 +3188,7 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
     if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_partials: ") + kPwScope);
     if (!out || M < 1) FAIL(c, "smcn_pointwise_partials: bad arguments");
     if (!x && (M != c->N || logw)) FAIL(c, "smcn_pointwise_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    const int64_t n = (int64_t)c->mdata_h[1], tiles = (n + 63) / 64, npad = tiles * 64;
+    const int64_t n = c->reg.n, tiles = (n + 63) / 64, npad = tiles * 64;
     int64_t cps = 1;
     const int64_t slices = pointwise_slices(M, n, &cps);
     if (tiles * slices > 2147483647LL) FAIL(c, "smcn_pointwise_partials: too many observations");
@@ -3436,31 +3199,20 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
     int rc = pw_ensure(c, o_out + (1 + n) * kPwCols);
     if (rc) return rc;
     double* const head = c->pw_buf;
-    double* lw = c->pw_buf + o_lw;
     double* const part = c->pw_buf + o_part;
     double* const grp = c->pw_buf + o_grp;
     double* const res = c->pw_buf + o_out;
-    const double* xd = c->x;
-    int64_t rs = 1, cs = c->N;
-    if (x) {
-        if ((rc = ensure_stage(c, M * c->D))) return rc;
-        HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
-        if (logw) HIPC(c, hipMemcpyAsync(lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        else HIPC(c, hipMemsetAsync(lw, 0, sizeof(double) * M, c->stream));
-        xd = c->stage;
-        rs = c->D;
-        cs = 1;
-    } else {
-        lw = c->logw;
-    }
+    Particles P;
+    if ((rc = stage_particles(c, x, logw, M, c->pw_buf + o_lw, &P))) return rc;
+    const double* const lw = P.lw;
     if (!c->pw_ev0) {
         HIPC(c, hipEventCreate(&c->pw_ev0));
         HIPC(c, hipEventCreate(&c->pw_ev1));
     }
-    const PwArgs a = pw_args(c, xd, rs, cs, M, cps);
+    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, cps);
     HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
     pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
-    pw_dispatch(a, [&](auto dp, auto disp) {
+    row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
         pointwise_stats_kernel<decltype(dp)::value, decltype(disp)::value>
             <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, lw, head, part);
     });
@@ -3778,38 +3530,27 @@ static bool pr_model(const smcn_ctx* c) {
     return c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_CATEGORICAL ||
            c->model == SMCN_MODEL_ORDINAL;
 }
-static int pr_classes(const smcn_ctx* c) {
-    return (c->model == SMCN_MODEL_CATEGORICAL || c->model == SMCN_MODEL_ORDINAL) ? (int)c->mdata_h[0] : 0;
-}
 static int pr_cols(const smcn_ctx* c) {
-    const int K = pr_classes(c);
+    const int K = c->reg.K;
     if (c->model == SMCN_MODEL_CATEGORICAL) return kPrCatP0 + K;
     if (c->model == SMCN_MODEL_ORDINAL) return kPrOrdP0 + (K <= kPrMaxProb ? K : 0);
     return kPrColsGlm;
 }
+// the arguments of the hierarchical, categorical and ordinal kernels over the new rows (c->pr)
 static PrArgs pr_args(const smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
-    const std::vector<double>& h = c->mdata_h;
     PrArgs a;
-    a.T = c->pr_md + c->pr_toff;
+    a.T = c->pr_md + c->pr.t0;
     a.x = x;
     a.rs = rs;
     a.cs = cs;
     a.M = M;
     a.cps = cps;
-    a.m = (int)c->pr_m;
+    a.m = (int)c->pr.n;
     a.D = c->D;
-    a.fam = 0;
-    a.J = 0;
-    a.K = pr_classes(c);
-    if (c->model == SMCN_MODEL_HGLM) {
-        a.fam = (int)h[0];
-        a.Dc = (int)h[2] + (int)h[3];
-        a.J = (int)h[4];
-    } else if (c->model == SMCN_MODEL_CATEGORICAL) {
-        a.Dc = (int)h[2] + (int)h[3];
-    } else {
-        a.Dc = (int)h[2];
-    }
+    a.fam = c->reg.fam;
+    a.J = (int)c->reg.J;
+    a.K = c->reg.K;
+    a.Dc = c->reg.Dc;
     return a;
 }
 // Dynamic LDS of one wavefront's area V[r][64 particles] (smcn_predict.hpp): J rows (hierarchical), D (categorical),
@@ -3818,11 +3559,11 @@ static PrArgs pr_args(const smcn_ctx* c, const double* x, int64_t rs, int64_t cs
 // without hipFuncSetAttribute.
 constexpr size_t kPrMaxLdsBytes = 64 * 1024;
 static size_t pr_lds_bytes(const smcn_ctx* c, bool stats) {
-    const PrArgs a = pr_args(c, nullptr, 0, 0, 0, 0);
+    const RegLayout& L = c->reg;
     size_t rows = 0;
-    if (c->model == SMCN_MODEL_HGLM) rows = (size_t)a.J;
-    else if (c->model == SMCN_MODEL_ORDINAL) rows = (size_t)(a.K - 1) * ((stats && a.K <= kPrMaxProb) ? 3 : 2);
-    else if (c->model == SMCN_MODEL_CATEGORICAL) rows = (size_t)a.D;
+    if (c->model == SMCN_MODEL_HGLM) rows = (size_t)L.J;
+    else if (c->model == SMCN_MODEL_ORDINAL) rows = (size_t)(L.K - 1) * ((stats && L.K <= kPrMaxProb) ? 3 : 2);
+    else if (c->model == SMCN_MODEL_CATEGORICAL) rows = (size_t)L.D;
     return sizeof(double) * 64 * rows;
 }
 #define PR_CHECK_LDS(c, stats, who)                                                                                     \
@@ -3836,10 +3577,8 @@ static void pr_launch(smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int6
     const int g = (int)blocks;
     hipStream_t st = c->stream;
     if (c->model == SMCN_MODEL_GLM) {
-        PwArgs a = pw_args(c, x, rs, cs, M, cps);
-        a.md = c->pr_md;
-        a.n = (int)c->pr_m;
-        pw_dispatch(a, [&](auto dp, auto disp) {
+        const PwArgs a = pw_args(c->pr, c->pr_md, x, rs, cs, M, cps);
+        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
             constexpr int DP = decltype(dp)::value;
             constexpr bool DI = decltype(disp)::value;
             if constexpr (STATS) predict_glm_stats_kernel<DP, DI><<<g, 64, 0, st>>>(a, tiles, lw, head, out);
@@ -3848,23 +3587,17 @@ static void pr_launch(smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int6
         return;
     }
     const PrArgs a = pr_args(c, x, rs, cs, M, cps);
-    const int DP = (a.Dc + 1) & ~1;
+    const size_t lds = pr_lds_bytes(c, STATS);
     if (c->model == SMCN_MODEL_HGLM) {
-        const size_t lds = pr_lds_bytes(c, STATS);
-        const auto go = [&](auto dp, auto disp) {
+        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
             constexpr int DPM = decltype(dp)::value;
             constexpr bool DI = decltype(disp)::value;
             if constexpr (STATS) predict_hier_stats_kernel<DPM, DI><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
             else predict_hier_loglik_kernel<DPM, DI><<<g, 64, lds, st>>>(a, tiles, out);
-        };
-        const auto fam = [&](auto dp) { a.fam >= 2 ? go(dp, std::true_type{}) : go(dp, std::false_type{}); };
-        if (DP <= 16) fam(std::integral_constant<int, 16>{});
-        else if (DP <= 32) fam(std::integral_constant<int, 32>{});
-        else fam(std::integral_constant<int, 64>{});
+        });
     } else if (c->model == SMCN_MODEL_ORDINAL) {
         const bool prob = a.K <= kPrMaxProb;
-        const size_t lds = pr_lds_bytes(c, STATS);
-        const auto go = [&](auto dp) {
+        row_cap(a.Dc, [&](auto dp) {
             constexpr int DPM = decltype(dp)::value;
             if constexpr (STATS) {
                 if (prob) predict_ord_stats_kernel<DPM, true><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
@@ -3872,24 +3605,13 @@ static void pr_launch(smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int6
             } else {
                 predict_ord_loglik_kernel<DPM><<<g, 64, lds, st>>>(a, tiles, out);
             }
-        };
-        if (DP <= 16) go(std::integral_constant<int, 16>{});
-        else if (DP <= 32) go(std::integral_constant<int, 32>{});
-        else go(std::integral_constant<int, 64>{});
+        });
     } else {
-        // categorical: (row capacity, non-reference classes) pairs that cover (K - 1) Dc <= 64
-        const size_t lds = pr_lds_bytes(c, STATS);
-        const auto go = [&](auto dc, auto km) {
+        cat_cap(a.Dc, [&](auto dc, auto km) {
             constexpr int DCM = decltype(dc)::value, KM = decltype(km)::value;
             if constexpr (STATS) predict_cat_stats_kernel<DCM, KM><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
             else predict_cat_loglik_kernel<DCM, KM><<<g, 64, lds, st>>>(a, tiles, out);
-        };
-        using std::integral_constant;
-        if (a.Dc <= 4) go(integral_constant<int, 4>{}, integral_constant<int, 15>{});
-        else if (a.Dc <= 8) go(integral_constant<int, 8>{}, integral_constant<int, 12>{});
-        else if (a.Dc <= 16) go(integral_constant<int, 16>{}, integral_constant<int, 7>{});
-        else if (a.Dc <= 32) go(integral_constant<int, 32>{}, integral_constant<int, 3>{});
-        else go(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+        });
     }
 }
 
@@ -3898,51 +3620,21 @@ extern "C" {
 int smcn_predict_set_data(smcn_ctx* c, const double* block, int64_t len, int has_y) {
     CHECK_CTX(c);
     if (!pr_model(c)) FAIL(c, std::string("smcn_predict_set_data: ") + kPrScope);
-    const std::vector<double>& h = c->mdata_h;
-    const bool ord = c->model == SMCN_MODEL_ORDINAL, hg = c->model == SMCN_MODEL_HGLM;
-    const int64_t nh = ord ? 3 : (hg ? 5 : 4);                   // header doubles
-    if (!block || len < nh) FAIL(c, "smcn_predict_set_data: the block is the model's data block without the priors");
-    for (int64_t q = 0; q < nh; ++q)
-        if (q != 1 && block[q] != h[q])
-            FAIL(c, "smcn_predict_set_data: the new rows' header must repeat the training block's (family or K, p, "
-                    "intercept, J): the column count differs from the training design?");
     // the priors of the training block spliced in: the block smcn_ctx_create would take, checked by the same routine
-    int64_t npri = c->D;
-    if (c->model == SMCN_MODEL_GLM) npri = (int64_t)h[2] + (int64_t)h[3] + (h[0] >= 2.0 ? 2 : 0);
-    if (hg) npri = hglm_head((int64_t)h[2] + (int64_t)h[3], h[0] >= 2.0) - 5;
-    std::vector<double> full;
-    full.reserve((size_t)(len + npri));
-    full.insert(full.end(), block, block + nh);
-    full.insert(full.end(), h.begin() + nh, h.begin() + nh + npri);
-    full.insert(full.end(), block + nh, block + len);
-    int D = 0;
-    const int64_t fl = (int64_t)full.size();
-    const std::string why = c->model == SMCN_MODEL_GLM ? glm_check(full.data(), fl, &D)
-                            : hg ? hglm_check(full.data(), fl, &D)
-                            : ord ? ord_check(full.data(), fl, &D) : cat_check(full.data(), fl, &D);
+    std::vector<double> full, mup;
+    std::string why = reg_splice(c->reg, c->mdata_h.data(), block, len, full);
+    if (!why.empty()) FAIL(c, why);
+    RegLayout L;
+    why = reg_check(c->model, full.data(), (int64_t)full.size(), &L);
     if (!why.empty()) FAIL(c, "smcn_predict_set_data (new rows, with the training priors spliced in): " + why);
-    if (D != c->D) FAIL(c, "smcn_predict_set_data: the new rows give another dimension than the training data");
-    const int64_t m = (int64_t)full[1], p = (int64_t)full[2];
-    std::vector<double> mup;
-    repack_model_table(c->model, c->D, full.data(), fl, mup);
-    const int64_t toff = c->model == SMCN_MODEL_GLM ? glm_table_offset(npri, m, p)
-                         : hg ? hglm_table_offset(nh + npri, m, p) : glm_table_offset(c->D, m, p);
-    const int64_t need = (int64_t)mup.size();
-    c->pr_m = 0;
-    if (need > c->pr_md_len) {
-        if (c->pr_md) {
-            HIPC(c, stream_wait(c->stream));
-            (void)cached_free(c->pr_md);
-        }
-        c->pr_md = nullptr;
-        c->pr_md_len = 0;
-        HIPC(c, dalloc(&c->pr_md, need));
-        c->pr_md_len = need;
-    }
-    HIPC(c, hipMemcpyAsync(c->pr_md, mup.data(), sizeof(double) * need, hipMemcpyHostToDevice, c->stream));
+    if (L.D != c->D) FAIL(c, "smcn_predict_set_data: the new rows give another dimension than the training data");
+    reg_repack(L, full.data(), mup);
+    c->pr.n = 0;
+    const int rc = grow_scratch(c, c->pr_md, c->pr_md_len, L.rlen);
+    if (rc) return rc;
+    HIPC(c, hipMemcpyAsync(c->pr_md, mup.data(), sizeof(double) * L.rlen, hipMemcpyHostToDevice, c->stream));
     HIPC(c, stream_wait(c->stream));                             // (mup is a local)
-    c->pr_toff = toff;
-    c->pr_m = m;
+    c->pr = L;
     c->pr_has_y = has_y ? 1 : 0;
     return 0;
 }
@@ -3950,8 +3642,8 @@ int smcn_predict_set_data(smcn_ctx* c, const double* block, int64_t len, int has
 int smcn_predict_dims(smcn_ctx* c, int64_t* n_rows, int* n_cols, int* has_y) {
     CHECK_CTX(c);
     if (!pr_model(c)) FAIL(c, std::string("smcn_predict_dims: ") + kPrScope);
-    if (c->pr_m < 1) FAIL(c, "smcn_predict_dims: no new rows (smcn_predict_set_data first)");
-    if (n_rows) *n_rows = c->pr_m;
+    if (c->pr.n < 1) FAIL(c, "smcn_predict_dims: no new rows (smcn_predict_set_data first)");
+    if (n_rows) *n_rows = c->pr.n;
     if (n_cols) *n_cols = pr_cols(c);
     if (has_y) *has_y = c->pr_has_y;
     return 0;
@@ -3960,11 +3652,11 @@ int smcn_predict_dims(smcn_ctx* c, int64_t* n_rows, int* n_cols, int* has_y) {
 int smcn_predict_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
     CHECK_CTX(c);
     if (!pr_model(c)) FAIL(c, std::string("smcn_predict_loglik: ") + kPrScope);
-    if (c->pr_m < 1) FAIL(c, "smcn_predict_loglik: no new rows (smcn_predict_set_data first)");
+    if (c->pr.n < 1) FAIL(c, "smcn_predict_loglik: no new rows (smcn_predict_set_data first)");
     if (!c->pr_has_y) FAIL(c, "smcn_predict_loglik: the new rows were given without y");
     if (!x || !out || M < 1) FAIL(c, "smcn_predict_loglik: bad arguments");
     PR_CHECK_LDS(c, false, "smcn_predict_loglik");
-    const int64_t m = c->pr_m, tiles = (m + 63) / 64;
+    const int64_t m = c->pr.n, tiles = (m + 63) / 64;
     int64_t cps = 1;
     const int64_t slices = pointwise_slices(M, m, &cps);
     if (tiles * slices > 2147483647LL) FAIL(c, "smcn_predict_loglik: too many rows");
@@ -3982,11 +3674,11 @@ int smcn_predict_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
 int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
     CHECK_CTX(c);
     if (!pr_model(c)) FAIL(c, std::string("smcn_predict_partials: ") + kPrScope);
-    if (c->pr_m < 1) FAIL(c, "smcn_predict_partials: no new rows (smcn_predict_set_data first)");
+    if (c->pr.n < 1) FAIL(c, "smcn_predict_partials: no new rows (smcn_predict_set_data first)");
     if (!out || M < 1) FAIL(c, "smcn_predict_partials: bad arguments");
     PR_CHECK_LDS(c, true, "smcn_predict_partials");
     if (!x && (M != c->N || logw)) FAIL(c, "smcn_predict_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    const int64_t m = c->pr_m, tiles = (m + 63) / 64, mpad = tiles * 64;
+    const int64_t m = c->pr.n, tiles = (m + 63) / 64, mpad = tiles * 64;
     const int Q = pr_cols(c), mom = (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_HGLM) ? 1 : 0;
     int64_t cps = 1;
     const int64_t slices = pointwise_slices(M, m, &cps);
@@ -3998,30 +3690,19 @@ int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int6
     int rc = pw_ensure(c, o_out + (1 + m) * Q);
     if (rc) return rc;
     double* const head = c->pw_buf;
-    double* lw = c->pw_buf + o_lw;
     double* const part = c->pw_buf + o_part;
     double* const grp = c->pw_buf + o_grp;
     double* const res = c->pw_buf + o_out;
-    const double* xd = c->x;
-    int64_t rs = 1, cs = c->N;
-    if (x) {
-        if ((rc = ensure_stage(c, M * c->D))) return rc;
-        HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
-        if (logw) HIPC(c, hipMemcpyAsync(lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        else HIPC(c, hipMemsetAsync(lw, 0, sizeof(double) * M, c->stream));
-        xd = c->stage;
-        rs = c->D;
-        cs = 1;
-    } else {
-        lw = c->logw;
-    }
+    Particles P;
+    if ((rc = stage_particles(c, x, logw, M, c->pw_buf + o_lw, &P))) return rc;
+    const double* const lw = P.lw;
     if (!c->pw_ev0) {
         HIPC(c, hipEventCreate(&c->pw_ev0));
         HIPC(c, hipEventCreate(&c->pw_ev1));
     }
     HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
     pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
-    pr_launch<true>(c, xd, rs, cs, M, cps, tiles, tiles * slices, lw, head, part);
+    pr_launch<true>(c, P.xd, P.rs, P.cs, M, cps, tiles, tiles * slices, lw, head, part);
     predict_combine_kernel<false><<<dim3((unsigned)grid_for(m, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, m, mpad, Q, mom, grp);
     predict_combine_kernel<true><<<grid_for(m, 64), 64, 0, c->stream>>>(grp, head, groups, m, mpad, Q, mom, res);
     HIPC(c, hipGetLastError());
@@ -4051,7 +3732,7 @@ constexpr bool kDrawsFusedHier = DPMAX <= 16;
 
 // Launches the model's draw kernel over the n gathered particles xg [D][n] -> out [n][m]
 static void dr_launch(smcn_ctx* c, const double* xg, int64_t n, const DrawArgs& d, double* out) {
-    const int64_t m = c->pr_m, tiles = (m + 63) / 64;
+    const int64_t m = c->pr.n, tiles = (m + 63) / 64;
     int64_t cps = 1;
     const int64_t slices = pointwise_slices(n, m, &cps);
     const int g = (int)(tiles * slices);
@@ -4060,10 +3741,8 @@ static void dr_launch(smcn_ctx* c, const double* xg, int64_t n, const DrawArgs& 
         draws_sample_kernel<<<grid_for(n * m, 256), 256, 0, st>>>(fam, m, n, d, disp ? xg + (int64_t)tau_coord * n : nullptr, out);
     };
     if (c->model == SMCN_MODEL_GLM) {
-        PwArgs a = pw_args(c, xg, 1, n, n, cps);
-        a.md = c->pr_md;
-        a.n = (int)m;
-        pw_dispatch(a, [&](auto dp, auto disp) {
+        const PwArgs a = pw_args(c->pr, c->pr_md, xg, 1, n, n, cps);
+        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
             constexpr int DP = decltype(dp)::value;
             constexpr bool DI = decltype(disp)::value;
             constexpr bool FU = kDrawsFusedGlm<DP, DI>;
@@ -4073,30 +3752,21 @@ static void dr_launch(smcn_ctx* c, const double* xg, int64_t n, const DrawArgs& 
         return;
     }
     const PrArgs a = pr_args(c, xg, 1, n, n, cps);
-    const int DP = (a.Dc + 1) & ~1;
     const size_t lds = pr_lds_bytes(c, false);
     if (c->model == SMCN_MODEL_HGLM) {
-        const auto go = [&](auto dp, auto disp) {
+        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
             constexpr int DPM = decltype(dp)::value;
             constexpr bool DI = decltype(disp)::value;
             constexpr bool FU = kDrawsFusedHier<DPM, DI>;
             draws_hier_kernel<DPM, DI, FU><<<g, 64, lds, st>>>(a, tiles, d, out);
             if (!FU) second(a.fam, DI, a.Dc + a.J + 1);
-        };
-        const auto fam = [&](auto dp) { a.fam >= 2 ? go(dp, std::true_type{}) : go(dp, std::false_type{}); };
-        if (DP <= 16) fam(std::integral_constant<int, 16>{});
-        else if (DP <= 32) fam(std::integral_constant<int, 32>{});
-        else fam(std::integral_constant<int, 64>{});
+        });
     } else if (c->model == SMCN_MODEL_ORDINAL) {
-        if (DP <= 16) draws_ord_kernel<16><<<g, 64, lds, st>>>(a, tiles, d, out);
-        else if (DP <= 32) draws_ord_kernel<32><<<g, 64, lds, st>>>(a, tiles, d, out);
-        else draws_ord_kernel<64><<<g, 64, lds, st>>>(a, tiles, d, out);
+        row_cap(a.Dc, [&](auto dp) { draws_ord_kernel<decltype(dp)::value><<<g, 64, lds, st>>>(a, tiles, d, out); });
     } else {
-        if (a.Dc <= 4) draws_cat_kernel<4, 15><<<g, 64, lds, st>>>(a, tiles, d, out);
-        else if (a.Dc <= 8) draws_cat_kernel<8, 12><<<g, 64, lds, st>>>(a, tiles, d, out);
-        else if (a.Dc <= 16) draws_cat_kernel<16, 7><<<g, 64, lds, st>>>(a, tiles, d, out);
-        else if (a.Dc <= 32) draws_cat_kernel<32, 3><<<g, 64, lds, st>>>(a, tiles, d, out);
-        else draws_cat_kernel<64, 1><<<g, 64, lds, st>>>(a, tiles, d, out);
+        cat_cap(a.Dc, [&](auto dc, auto km) {
+            draws_cat_kernel<decltype(dc)::value, decltype(km)::value><<<g, 64, lds, st>>>(a, tiles, d, out);
+        });
     }
 }
 
@@ -4107,7 +3777,7 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
                        int64_t* ancestors_out, int64_t* n_bad_out) {
     CHECK_CTX(c);
     if (!pr_model(c)) FAIL(c, std::string("smcn_predict_draws: ") + kPrScope);
-    if (c->pr_m < 1) FAIL(c, "smcn_predict_draws: no new rows (smcn_predict_set_data first)");
+    if (c->pr.n < 1) FAIL(c, "smcn_predict_draws: no new rows (smcn_predict_set_data first)");
     if (M < 1) FAIL(c, "smcn_predict_draws: M must be at least 1");
     if (S < 1 || S > 2147483647LL) FAIL(c, "smcn_predict_draws: the number of draws S must be in 1..2^31-1");
     if (s_first < 0 || s_count < 1 || s_first + s_count > S)
@@ -4115,7 +3785,7 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
     if (!y_out) FAIL(c, "smcn_predict_draws: y_out is null");
     if (!x && (M != c->N || logw)) FAIL(c, "smcn_predict_draws: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
     if (new_group && c->model != SMCN_MODEL_HGLM) FAIL(c, "smcn_predict_draws: new_group is for SMCN_MODEL_HGLM only");
-    const int64_t m = c->pr_m, tiles = (m + 63) / 64, n = s_count;
+    const int64_t m = c->pr.n, tiles = (m + 63) / 64, n = s_count;
     if (new_group)
         for (int64_t i = 0; i < m; ++i)
             if (new_group[i] < 0 || new_group[i] > 4294967295LL)
@@ -4133,35 +3803,15 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
     const int64_t o_lw = 16, o_w = o_lw + pad(M), o_loc = o_w + pad(M), o_tt = o_loc + pad(M), o_to = o_tt + pad(nt);
     const int64_t o_anc = o_to + pad(nt + 1), o_ng = o_anc + pad(n), o_xg = o_ng + pad(m), o_y = o_xg + pad(n * c->D);
     const int64_t need = o_y + n * m;
-    if (need > c->dr_len) {
-        if (c->dr_buf) {
-            HIPC(c, stream_wait(c->stream));
-            (void)cached_free(c->dr_buf);
-        }
-        c->dr_buf = nullptr;
-        c->dr_len = 0;
-        HIPC(c, dalloc(&c->dr_buf, need));
-        c->dr_len = need;
-    }
+    int rc = grow_scratch(c, c->dr_buf, c->dr_len, need);
+    if (rc) return rc;
     double* const B = c->dr_buf;
     double* const head = B;
-    double* lw = B + o_lw;
     int64_t* const anc = (int64_t*)(B + o_anc);
     int64_t* const ng = (int64_t*)(B + o_ng);
-    const double* xd = c->x;
-    int64_t rs = 1, cs = c->N;
-    if (x) {
-        int rc = ensure_stage(c, M * c->D);
-        if (rc) return rc;
-        HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
-        if (logw) HIPC(c, hipMemcpyAsync(lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        else HIPC(c, hipMemsetAsync(lw, 0, sizeof(double) * M, c->stream));
-        xd = c->stage;
-        rs = c->D;
-        cs = 1;
-    } else {
-        lw = c->logw;
-    }
+    Particles P;
+    if ((rc = stage_particles(c, x, logw, M, B + o_lw, &P))) return rc;
+    const double* const lw = P.lw;
     if (new_group) HIPC(c, hipMemcpyAsync(ng, new_group, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
     if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
     if (!c->pw_ev0) {
@@ -4176,7 +3826,7 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
         scan_offsets_kernel<<<1, 64, 0, c->stream>>>(B + o_tt, nt, B + o_to);
         draws_ancestors_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(B + o_loc, B + o_to, nt, M, lw, S, s_first, n, seed, anc);
     }
-    draws_gather_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(xd, rs, cs, anc, n, c->D, B + o_xg);
+    draws_gather_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(P.xd, P.rs, P.cs, anc, n, c->D, B + o_xg);
     const DrawArgs d{seed, s_first, new_group ? ng : nullptr};
     dr_launch(c, B + o_xg, n, d, B + o_y);
     HIPC(c, hipGetLastError());

@@ -22,6 +22,7 @@
 //   void eval(x[DL], lpri, llik, gpri[DL], glik[DL])   all lanes of the group
 #pragma once
 #include "smcn_device.hpp"
+#include "smcn_regdata.hpp"   // where the regression models' tables lie (glm_table_offset and its kin)
 
 namespace smcn {
 
@@ -402,7 +403,7 @@ struct PrmwcdDistModel {
 // ---------------------------------------------------------------------------
 // Canonical-link GLM (SMCN_MODEL_GLM): Bernoulli-logit or Poisson-log likelihood of a linear predictor
 // eta = X beta (+ intercept), independent Gaussian priors N(0, s_c^2) on the D <= 64 coefficients.
-// The density works on the table smcn_ctx_create repacks behind the caller's data (glm_table_offset): a row per
+// The density works on the table reg_repack (smcn_regdata.hpp) lays behind the caller's data (glm_table_offset): a row per
 // observation, [1 (intercept only), X_i1 .. X_ip, 0 (to an even column count DP), y_i, lgamma(y_i + 1)], RS = DP + 2
 // doubles, at a 128-byte boundary, zero rows up to a multiple of 64 -- every lane reads whole rows, unmasked, with
 // 16-byte loads.  The design stays in global memory (L2 / Infinity Cache): the G lanes of every particle group of a
@@ -415,12 +416,6 @@ struct PrmwcdDistModel {
 //                    the same way and lane c accumulates column c of the chunk's rows -- the column sums come out on the
 //                    lane that owns the coordinate, with no butterfly at all.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline int64_t glm_table_offset(int64_t D, int64_t n, int64_t p) {
-    return (4 + D + n + n * p + 15) / 16 * 16;
-}
-__host__ __device__ inline int glm_row_doubles(int D) { return ((D + 1) & ~1) + 2; }
-__host__ __device__ inline int64_t glm_table_rows(int64_t n) { return (n + 63) / 64 * 64; }
-
 template <int G_, int DL_>
 struct GlmModel {
     static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
@@ -800,7 +795,7 @@ struct GlmDispModel {
 //   eta_i = [b_0 +] X_i b + e^lt z_{g_i},   y_i ~ family(eta_i [, e^ld])   (the four SMCN_MODEL_GLM families, same terms)
 //   b_c ~ N(0, s_c^2), z_j ~ N(0, 1), tau = e^lt ~ half-normal(s_tau) with its Jacobian, ld ~ N(m_d, s_d^2) (families 2, 3).
 // x = (b_1..b_Dc, z_1..z_J, lt [, ld]), D = Dc + J + 1 (+ 1) <= 64; one wavefront per particle, coordinate c on lane c.
-// The table smcn_ctx_create repacks behind the caller's block: a row per observation, [1 (intercept), X_i1 .. X_ip,
+// The table reg_repack lays behind the caller's block: a row per observation, [1 (intercept), X_i1 .. X_ip,
 // 0 (to an even count DP), y_i, lgamma(y_i + 1), g_i, 0], RS = DP + 4 doubles, at a 128-byte boundary, zero rows up to a
 // multiple of 64.  Lane l takes row k0 + l of each 64-row chunk, as GlmModel<64, 1>:
 //   eta: the fixed part with the coefficients read out as scalars, the group part with ONE cross-lane read (ds_bpermute)
@@ -811,12 +806,6 @@ struct GlmDispModel {
 // The per-observation terms are GlmModel's / GlmDispModel's own obs() (and tau_const()), called on members of which only
 // the family flag is set.  Non-finite: the GLM rules, and -inf (lpri and llik) when e^(2 lt) overflows.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline int64_t hglm_head(int64_t Dc, bool disp) { return 5 + Dc + 1 + (disp ? 2 : 0); }
-__host__ __device__ inline int64_t hglm_table_offset(int64_t head, int64_t n, int64_t p) {
-    return (head + 2 * n + n * p + 15) / 16 * 16;
-}
-__host__ __device__ inline int hglm_row_doubles(int Dc) { return ((Dc + 1) & ~1) + 4; }
-
 template <int G_, int DL_>
 struct GlmHierModel {
     static_assert(G_ == 64 && DL_ == 1, "GlmHierModel: one wavefront per particle, one coordinate per lane");
@@ -937,8 +926,6 @@ struct GlmHierModel {
 //                   read per row, where reading the K - 1 residuals out as scalars and selecting costs K - 1 (DESIGN.md
 //                   4.4).  A wavefront's area is 64 x 15 doubles (7.5 KB); SHARED holds the four of a 256-lane block.
 // ---------------------------------------------------------------------------
-constexpr int kCatMaxClasses = 16;
-
 template <int G_, int DL_>
 struct GlmCatModel {
     static_assert((G_ == 8 || G_ == 64) && DL_ == 1, "GlmCatModel: 8 or 64 lanes per particle, one coordinate per lane");
@@ -1141,9 +1128,6 @@ struct GlmCatModel {
 //                   GlmCatModel's LDS staging would need a K-slot row per observation (up to 65 doubles) to let a lane
 //                   read its own slot, where the compare costs a few VALU operations and no LDS.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline int64_t ord_counts_offset(int64_t D, int64_t n, int64_t p) {
-    return glm_table_offset(D, n, p) + glm_table_rows(n) * glm_row_doubles((int)p);
-}
 // sum of v over lanes lg .. G - 1 of the group (Kogge-Stone)
 template <int G>
 __device__ __forceinline__ double group_suffix_sum(double v, int lg) {
