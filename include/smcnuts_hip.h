@@ -495,6 +495,42 @@ int smcn_pointwise_partials(smcn_ctx* ctx, const double* x_or_null /* [M][D] */,
                             int64_t M, double* out /* [1 + n][Q] */);
 int smcn_pointwise_last_ms(const smcn_ctx* ctx, double* ms);
 
+/* ---- Pareto-smoothed importance-sampling LOO (SMCN_MODEL_GLM, all four families, D <= 64, any n) ----
+ * PSIS-LOO of the weighted particles with the shape k of the fitted generalised Pareto tail as its diagnostic (definition:
+ * DESIGN.md 4.4).  With lw' = lw - mw, ll = log p(y_i | x_p) and lr = lw' - ll over the contributing particles (finite
+ * lw), S of them over all shards, mw the largest finite log-weight over all shards: M = min(S / 5, ceil(3 sqrt(S))) and
+ * T_cap = M + 1.  Contexts of every other model fail with smcn_pointwise_*'s message.  Three stages, each a function of its
+ * inputs and (mw, S) alone, and the single-rank wrapper; x == NULL takes the resident particles with their resident
+ * log-weights (M = N, logw = NULL) as smcn_pointwise_partials does, logw == NULL with x means equal weights.
+ *
+ * smcn_psis_candidates: cand[2][n][T_cap] = per observation this rank's T_cap largest lr (first block) with their ll
+ * (second block), descending in lr, equal lr in particle order, padded with -inf where the rank holds fewer.  The
+ * selection is exact (radix selection by count on the bits of lr, then a sort on (lr, particle index)): the result depends
+ * on the values alone.  T_cap <= 4096, i.e. S <= 1 863 225; larger S is refused with a message.
+ * smcn_psis_body: body[n][4] = (mb, Sb, Sb2, Sw) over this rank's contributing particles with a finite term and
+ * lr <= cutoff[i]: max lr, sum exp(lr - mb), sum exp(2 (lr - mb)), sum exp(lw').  Slices are merged in slice order; blocks
+ * of disjoint particle sets merge as the (mb, Sb, Sb2) of smcn_pointwise_partials do, Sw adds.
+ * smcn_psis_fit: from the merged candidates (T_cap per observation, any order) and merged body partials of n_obs
+ * observations, out[n_obs][6] = pareto_k, elpd_psis, psis_ess, tail_len, cutoff, sigma.  mx is the largest candidate, c the
+ * smallest minus mx, the tail the candidates with lr - mx > c (sorted on the device), cutoff the largest candidate that is
+ * not in the tail (the value smcn_psis_body wants).  Fewer than 5 tail entries: pareto_k = +inf, sigma = NaN, nothing is
+ * smoothed.  A candidate of +inf (a contributing particle with ll = -inf): pareto_k = +inf, elpd_psis = -inf, psis_ess = 0,
+ * tail_len = 0, cutoff = +inf, sigma = NaN.  elpd_psis is log sum r~ p / sum r~ of the smoothed ratios (elpd_loo_i of
+ * smcn_pointwise_partials with the tail replaced).  Needs no particles and no model: any n_obs, T_cap <= 4097.
+ * smcn_psis_loo: the three stages back to back on one rank without a host round trip (mw and S are the call's own, formed
+ * and read on the device); out[n][6], head_or_null[4] = smcn_pointwise_partials' header.  Bit for bit the staged calls.
+ * smcn_psis_last_ms: ms[4] = device time of the last candidates, body, fit stage and of the last whole smcn_psis_loo (HIP
+ * events on the context's stream), for measurements. */
+int smcn_psis_candidates(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */,
+                         int64_t M, double mw, int64_t S, double* cand /* [2][n][T_cap] */);
+int smcn_psis_body(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */, int64_t M,
+                   double mw, int64_t S, const double* cutoff /* [n] */, double* body /* [n][4] */);
+int smcn_psis_fit(smcn_ctx* ctx, const double* cand /* [2][n_obs][T_cap] */, const double* body /* [n_obs][4] */,
+                  int64_t n_obs, double mw, int64_t S, double* out /* [n_obs][6] */);
+int smcn_psis_loo(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */, int64_t M,
+                  double* out /* [n][6] */, double* head_or_null /* [4] */);
+int smcn_psis_last_ms(const smcn_ctx* ctx, double* ms /* [4] */);
+
 /* ---- held-out prediction at new rows (SMCN_MODEL_GLM, SMCN_MODEL_HGLM, SMCN_MODEL_CATEGORICAL, SMCN_MODEL_ORDINAL) ----
  * Posterior predictive summaries at rows the model was not fitted to, and log p(y_new_i | x_p) when y_new is given.
  * Contexts of every other model (arma, PRMwCD, Gaussian, host-evaluated) fail with a message that names these four.

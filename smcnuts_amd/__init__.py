@@ -12,5 +12,6 @@ from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GL
                             HostTarget, IsoGaussian, LinearRegression, LogisticRegression, NegativeBinomialRegression,
                             OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel)
 from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F401
+from .psis import PsisLoo, compare_loo, merge_candidates, tail_len  # noqa: F401
 from .predict import Prediction, PredictiveDraws, combine_predict_partials, compare_heldout  # noqa: F401
 from .summary import PosteriorSummary  # noqa: F401

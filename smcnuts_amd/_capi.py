@@ -135,6 +135,11 @@ SIGNATURES = {
     "smcn_pointwise_loglik": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
     "smcn_pointwise_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
     "smcn_pointwise_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_psis_candidates": ([_ctx, _dp, _dp, C.c_int64, C.c_double, C.c_int64, _dp], C.c_int),
+    "smcn_psis_body": ([_ctx, _dp, _dp, C.c_int64, C.c_double, C.c_int64, _dp, _dp], C.c_int),
+    "smcn_psis_fit": ([_ctx, _dp, _dp, C.c_int64, C.c_double, C.c_int64, _dp], C.c_int),
+    "smcn_psis_loo": ([_ctx, _dp, _dp, C.c_int64, _dp, _dp], C.c_int),
+    "smcn_psis_last_ms": ([_ctx, _dp], C.c_int),
     "smcn_predict_set_data": ([_ctx, _dp, C.c_int64, C.c_int], C.c_int),
     "smcn_predict_dims": ([_ctx, _lp, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
     "smcn_predict_loglik": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
@@ -403,6 +408,63 @@ class Context:
         if rc != 0:
             raise SmcnError("smcn_pointwise_last_ms failed")
         return ms.value
+
+    # ---- Pareto-smoothed LOO (SMCN_MODEL_GLM; include/smcnuts_hip.h, smcn_psis_*) ------
+    def _psis_points(self, x, logw):
+        if x is None:
+            return None, None, self.N
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+        if lw is not None and lw.shape != (x.shape[0],):
+            raise ValueError("logw must hold one log-weight per row of x")
+        return x, lw, x.shape[0]
+
+    def psis_candidates(self, mw, S, x=None, logw=None):
+        """(lr, ll), each [n][T_cap]: this rank's T_cap largest ratios per observation, descending."""
+        from .psis import tail_len
+        x, lw, M = self._psis_points(x, logw)
+        n, _ = self.pointwise_dims()
+        out = np.empty((2, n, tail_len(S) + 1))
+        self.call("smcn_psis_candidates", dptr(x), dptr(lw), M, float(mw), int(S), dptr(out))
+        return out[0], out[1]
+
+    def psis_body(self, mw, S, cutoff, x=None, logw=None):
+        """[n][4] body partials (mb, Sb, Sb2, Sw) of the particles at or below the per-observation cutoffs."""
+        x, lw, M = self._psis_points(x, logw)
+        n, _ = self.pointwise_dims()
+        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64)
+        if cutoff.shape != (n,):
+            raise ValueError("cutoff must hold one value per observation")
+        out = np.empty((n, 4))
+        self.call("smcn_psis_body", dptr(x), dptr(lw), M, float(mw), int(S), dptr(cutoff), dptr(out))
+        return out
+
+    def psis_fit(self, lr, ll, body, mw, S):
+        """[n][6] = pareto_k, elpd_psis, psis_ess, tail_len, cutoff, sigma from merged candidates and body partials."""
+        from .psis import tail_len
+        cand = np.ascontiguousarray(np.stack([lr, ll]), dtype=np.float64)
+        body = np.ascontiguousarray(body, dtype=np.float64)
+        n = cand.shape[1]
+        if cand.ndim != 3 or cand.shape[2] != tail_len(S) + 1 or body.shape != (n, 4):
+            raise ValueError("psis_fit: candidates are [n][tail_len(S) + 1] and body partials [n][4]")
+        out = np.empty((n, 6))
+        self.call("smcn_psis_fit", dptr(cand), dptr(body), n, float(mw), int(S), dptr(out))
+        return out
+
+    def psis_loo(self, x=None, logw=None):
+        """([n][6], header [mw, sw, sw2, S]) of one rank's particles: the three stages without a host round trip."""
+        x, lw, M = self._psis_points(x, logw)
+        n, _ = self.pointwise_dims()
+        out, head = np.empty((n, 6)), np.empty(4)
+        self.call("smcn_psis_loo", dptr(x), dptr(lw), M, dptr(out), dptr(head))
+        return out, head
+
+    def psis_last_ms(self):
+        """Device time [candidates, body, fit, whole psis_loo] of the last calls (HIP events on the context's stream)."""
+        ms = np.zeros(4)
+        if self._lib.smcn_psis_last_ms(self._h, dptr(ms)) != 0:
+            raise SmcnError("smcn_psis_last_ms failed")
+        return ms
 
     # ---- held-out prediction (GLM, hierarchical, categorical, ordinal) ----------------
     def predict_set_data(self, block, has_y):

@@ -10,8 +10,8 @@ observation i:
   loo_ess_i     = (sum_p r_p)^2 / sum_p r_p^2, r_p = W_p exp(-ll[p, i])
   fitted_i      = sum_p W_p E[y_i | x_p]
 Plain IS-LOO has heavy-tailed ratios: `loo_ess_i` is the effective number of particles behind `elpd_loo_i`, and a value
-of a few says that observation's estimate is not to be trusted (Pareto smoothing is not part of this library;
-`GLMTarget.pointwise_loglik` hands out the matrix for problems small enough to hold it).
+of a few says that observation's estimate is not to be trusted: `GLMTarget.loo` / `SMCSampler.loo` (psis.py) smooth the
+tail of the ratios on the device and report the Pareto shape k beside the smoothed elpd_loo_i.
 
 Rules: a particle with a non-finite log-weight contributes to nothing.  An observation for which some contributing
 particle has ll = -inf keeps lppd_i as defined (that particle adds 0), has mean_loglik_i = elpd_loo_i = -inf,

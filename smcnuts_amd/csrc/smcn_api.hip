@@ -32,6 +32,7 @@
 #include "smcn_predict.hpp"
 #include "smcn_predict_draws.hpp"
 #include "smcn_quantile.hpp"
+#include "smcn_psis.hpp"
 
 using namespace smcn;
 
@@ -174,6 +175,13 @@ struct smcn_ctx {
     int64_t pw_len = 0;
     hipEvent_t pw_ev0 = nullptr, pw_ev1 = nullptr;
     double pw_ms = 0.0;
+
+    // Pareto-smoothed LOO (smcn_psis_*): header, log-weights, the staged slab of ll, candidates, cutoffs, body partials and
+    // the result of a call; device time of the stages of the last calls (candidates, body, fit, whole smcn_psis_loo)
+    double* ps_buf = nullptr;
+    int64_t ps_len = 0;
+    hipEvent_t ps_ev[4] = {};
+    double ps_ms[4] = {};
 
     // held-out prediction (smcn_predict_*): the new rows' image [block | padding | table] as smcn_ctx_create lays out the
     // training data, its layout (pr.n new rows, 0: none set) and whether they came with y
@@ -513,12 +521,14 @@ static void free_all(smcn_ctx* c) {
                     c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
                     c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
                     c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->pr_md, c->dr_buf, c->sm_buf, c->sm_hist};
+                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->ps_buf, c->pr_md, c->dr_buf, c->sm_buf, c->sm_hist};
     if (c->rows_h) (void)hipHostFree(c->rows_h);
     if (c->hist_h) (void)hipHostFree(c->hist_h);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
     if (c->pw_ev0) (void)hipEventDestroy(c->pw_ev0);
     if (c->pw_ev1) (void)hipEventDestroy(c->pw_ev1);
+    for (hipEvent_t e : c->ps_ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->sm_ev)
         if (e) (void)hipEventDestroy(e);
     // ONE wait for everything this context has in flight (its own stream, the history stream); the buffers below were
@@ -3232,6 +3242,191 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
 int smcn_pointwise_last_ms(const smcn_ctx* c, double* ms) {
     if (!c || !ms) return -1;
     *ms = c->pw_ms;
+    return 0;
+}
+
+}  // extern "C"
+// ---- Pareto-smoothed importance-sampling LOO (smcn_psis.hpp) ---------------------------------------------------------------
+namespace {
+// ps_buf of a call over particles: [header 16 | lw | slab of ll | candidates lr, ll [n][stride] | cutoff npad | slice
+// partials | group partials | body [n][4] | out [n][6]]
+struct PsLayout {
+    int64_t n, tiles, npad, M, Mpad, cps, slices, groups, slab_tiles, stride;
+    int64_t o_lw, o_stage, o_clr, o_cll, o_cut, o_part, o_grp, o_body, o_out, total;
+};
+constexpr int64_t kPsSlab = 1ll << 25;     // doubles of ll staged at once (256 MB), one observation tile at the least
+}  // namespace
+
+static int ps_layout(smcn_ctx* c, const char* who, int64_t M, int64_t S_bound, PsLayout* L) {
+    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string(who) + ": " + kPwScope);
+    if (M < 1 || M > 2147483647LL) FAIL(c, std::string(who) + ": bad arguments");
+    if (S_bound < 1) FAIL(c, std::string(who) + ": no contributing particle (S < 1)");
+    L->stride = psis_tail_len(S_bound) + 1;
+    if (L->stride > kPsMaxCap)
+        FAIL(c, std::string(who) + ": the tail of " + std::to_string(L->stride - 1) + " candidates per observation exceeds " +
+                    std::to_string(kPsMaxCap - 1) + " (more than 1863225 contributing particles are not implemented)");
+    L->n = c->reg.n;
+    L->tiles = (L->n + 63) / 64;
+    L->npad = L->tiles * 64;
+    L->M = M;
+    L->Mpad = (M + 63) / 64 * 64;
+    L->slices = pointwise_slices(M, L->n, &L->cps);
+    L->groups = (L->slices + kPwGroup - 1) / kPwGroup;
+    int64_t st = kPsSlab / (64 * L->Mpad);
+    st = st < 1 ? 1 : (st > L->tiles ? L->tiles : st);
+    while (st > 1 && st * L->slices > 2147483647LL) --st;
+    L->slab_tiles = st;
+    if (L->tiles * L->slices > 2147483647LL) FAIL(c, std::string(who) + ": too many observations");
+    L->o_lw = 16;
+    L->o_stage = L->o_lw + L->Mpad;
+    L->o_clr = L->o_stage + st * 64 * L->Mpad;
+    L->o_cll = L->o_clr + L->n * L->stride;
+    L->o_cut = L->o_cll + L->n * L->stride;
+    L->o_part = L->o_cut + L->npad;
+    L->o_grp = L->o_part + L->slices * kPsBodyCols * L->npad;
+    L->o_body = L->o_grp + L->groups * kPsBodyCols * L->npad;
+    L->o_out = L->o_body + L->n * kPsBodyCols;
+    L->total = L->o_out + L->n * kPsOutCols;
+    return grow_scratch(c, c->ps_buf, c->ps_len, L->total);
+}
+static int ps_events(smcn_ctx* c) {
+    for (hipEvent_t& e : c->ps_ev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    return 0;
+}
+// header of a staged call from the caller's (mw, S)
+static int ps_put_head(smcn_ctx* c, double mw, int64_t S) {
+    const double h[16] = {mw, 0.0, 0.0, (double)S};
+    HIPC(c, hipMemcpyAsync(c->ps_buf, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, stream_wait(c->stream));      // (h is a local)
+    return 0;
+}
+static void ps_run_candidates(smcn_ctx* c, const PsLayout& L, const PwArgs& a, const double* lw) {
+    double* const B = c->ps_buf;
+    for (int64_t t0 = 0; t0 < L.tiles; t0 += L.slab_tiles) {
+        const int64_t nt = L.tiles - t0 < L.slab_tiles ? L.tiles - t0 : L.slab_tiles;
+        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
+            psis_stage_kernel<decltype(dp)::value, decltype(disp)::value>
+                <<<(int)(nt * L.slices), 64, 0, c->stream>>>(a, t0, nt, lw, B, L.Mpad, B + L.o_stage);
+        });
+        psis_select_kernel<<<(int)(nt * 64), kPsBlock, 0, c->stream>>>(B + L.o_stage, L.Mpad, lw, B, L.M, t0 * 64, L.n,
+                                                                       (int)L.stride, B + L.o_clr, B + L.o_cll, B + L.o_cut);
+    }
+}
+static void ps_run_body(smcn_ctx* c, const PsLayout& L, const PwArgs& a, const double* lw) {
+    double* const B = c->ps_buf;
+    row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
+        psis_body_kernel<decltype(dp)::value, decltype(disp)::value>
+            <<<(int)(L.tiles * L.slices), 64, 0, c->stream>>>(a, L.tiles, lw, B, B + L.o_cut, B + L.o_part);
+    });
+    psis_body_combine_kernel<false><<<dim3((unsigned)grid_for(L.n, 64), (unsigned)L.groups), 64, 0, c->stream>>>(
+        B + L.o_part, L.slices, L.n, L.npad, B + L.o_grp);
+    psis_body_combine_kernel<true><<<grid_for(L.n, 64), 64, 0, c->stream>>>(B + L.o_grp, L.groups, L.n, L.npad, B + L.o_body);
+}
+static int ps_elapsed(smcn_ctx* c, int slot, int e0, int e1) {
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->ps_ev[e0], c->ps_ev[e1]));
+    c->ps_ms[slot] = (double)ms;
+    return 0;
+}
+
+extern "C" {
+
+int smcn_psis_candidates(smcn_ctx* c, const double* x, const double* logw, int64_t M, double mw, int64_t S, double* cand) {
+    CHECK_CTX(c);
+    if (!cand) FAIL(c, "smcn_psis_candidates: bad arguments");
+    if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_candidates: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
+    PsLayout L;
+    int rc = ps_layout(c, "smcn_psis_candidates", M, S, &L);
+    if (rc || (rc = ps_events(c)) || (rc = ps_put_head(c, mw, S))) return rc;
+    Particles P;
+    if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
+    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
+    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    ps_run_candidates(c, L, a, P.lw);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    HIPC(c, hipMemcpyAsync(cand, c->ps_buf + L.o_clr, sizeof(double) * 2 * L.n * L.stride, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return ps_elapsed(c, 0, 0, 1);
+}
+
+int smcn_psis_body(smcn_ctx* c, const double* x, const double* logw, int64_t M, double mw, int64_t S, const double* cutoff,
+                   double* body) {
+    CHECK_CTX(c);
+    if (!cutoff || !body) FAIL(c, "smcn_psis_body: bad arguments");
+    if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_body: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
+    PsLayout L;
+    int rc = ps_layout(c, "smcn_psis_body", M, S, &L);
+    if (rc || (rc = ps_events(c)) || (rc = ps_put_head(c, mw, S))) return rc;
+    Particles P;
+    if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
+    HIPC(c, hipMemcpyAsync(c->ps_buf + L.o_cut, cutoff, sizeof(double) * L.n, hipMemcpyHostToDevice, c->stream));
+    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
+    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    ps_run_body(c, L, a, P.lw);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    HIPC(c, hipMemcpyAsync(body, c->ps_buf + L.o_body, sizeof(double) * L.n * kPsBodyCols, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return ps_elapsed(c, 1, 0, 1);
+}
+
+int smcn_psis_fit(smcn_ctx* c, const double* cand, const double* body, int64_t n_obs, double mw, int64_t S, double* out) {
+    CHECK_CTX(c);
+    if (!cand || !body || !out || n_obs < 1 || n_obs > 2147483647LL) FAIL(c, "smcn_psis_fit: bad arguments");
+    if (S < 1) FAIL(c, "smcn_psis_fit: no contributing particle (S < 1)");
+    const int64_t stride = psis_tail_len(S) + 1;
+    if (stride > kPsMaxTail + 1)
+        FAIL(c, "smcn_psis_fit: the tail of " + std::to_string(stride - 1) + " candidates per observation exceeds " +
+                    std::to_string(kPsMaxTail));
+    // ps_buf: [header 16 | candidates lr, ll [n][stride] | body [n][4] | out [n][6]]
+    const int64_t o_c = 16, o_b = o_c + 2 * n_obs * stride, o_o = o_b + n_obs * kPsBodyCols;
+    int rc = grow_scratch(c, c->ps_buf, c->ps_len, o_o + n_obs * kPsOutCols);
+    if (rc || (rc = ps_events(c)) || (rc = ps_put_head(c, mw, S))) return rc;
+    double* const B = c->ps_buf;
+    HIPC(c, hipMemcpyAsync(B + o_c, cand, sizeof(double) * 2 * n_obs * stride, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(B + o_b, body, sizeof(double) * n_obs * kPsBodyCols, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    psis_fit_kernel<<<(int)n_obs, kPsBlock, 0, c->stream>>>(B + o_c, B + o_c + n_obs * stride, B + o_b, B, (int)stride, B + o_o);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    HIPC(c, hipMemcpyAsync(out, B + o_o, sizeof(double) * n_obs * kPsOutCols, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return ps_elapsed(c, 2, 0, 1);
+}
+
+int smcn_psis_loo(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out, double* head_out) {
+    CHECK_CTX(c);
+    if (!out) FAIL(c, "smcn_psis_loo: bad arguments");
+    if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_loo: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
+    // S <= M is known on the device only: the candidate rows are laid out for S = M, the kernels read S from the header
+    PsLayout L;
+    int rc = ps_layout(c, "smcn_psis_loo", M, M, &L);
+    if (rc || (rc = ps_events(c))) return rc;
+    Particles P;
+    if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
+    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
+    double* const B = c->ps_buf;
+    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(P.lw, M, B);
+    ps_run_candidates(c, L, a, P.lw);
+    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    ps_run_body(c, L, a, P.lw);
+    HIPC(c, hipEventRecord(c->ps_ev[2], c->stream));
+    psis_fit_kernel<<<(int)L.n, kPsBlock, 0, c->stream>>>(B + L.o_clr, B + L.o_cll, B + L.o_body, B, (int)L.stride, B + L.o_out);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->ps_ev[3], c->stream));
+    HIPC(c, hipMemcpyAsync(out, B + L.o_out, sizeof(double) * L.n * kPsOutCols, hipMemcpyDeviceToHost, c->stream));
+    if (head_out) HIPC(c, hipMemcpyAsync(head_out, B, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    if ((rc = ps_elapsed(c, 0, 0, 1)) || (rc = ps_elapsed(c, 1, 1, 2)) || (rc = ps_elapsed(c, 2, 2, 3))) return rc;
+    return ps_elapsed(c, 3, 0, 3);
+}
+
+int smcn_psis_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    for (int k = 0; k < 4; ++k) ms[k] = c->ps_ms[k];
     return 0;
 }
 

@@ -83,6 +83,9 @@ class DeviceTarget:
     def pointwise(self, x, logw=None):
         self._no_pointwise()
 
+    def loo(self, x, logw=None):
+        self._no_pointwise()
+
     def summary(self, x, logw=None, probs=_summary.DEFAULT_PROBS, at=None):
         """summary.PosteriorSummary of the points x [M][D] (unconstrained) with log-weights logw (None: equal): weighted
         quantiles at `probs` (at most 16, each in (0, 1]) and, with `at` (a scalar, [T] or [Dc][T], T <= 16), the mass at
@@ -158,6 +161,9 @@ class HostTarget:
         DeviceTarget._no_pointwise(self)
 
     def pointwise(self, x, logw=None):
+        DeviceTarget._no_pointwise(self)
+
+    def loo(self, x, logw=None):
         DeviceTarget._no_pointwise(self)
 
     def summary(self, x, logw=None, probs=_summary.DEFAULT_PROBS, at=None):
@@ -371,6 +377,14 @@ class GLMTarget(PredictMixin, DeviceTarget):
         for equal weights) -> criteria.Pointwise.  The matrix ll is never formed."""
         from ..criteria import combine_pointwise_partials
         return combine_pointwise_partials([self.pointwise_partials(x, logw)])
+
+    def loo(self, x, logw=None):
+        """Pareto-smoothed importance-sampling LOO of the weighted points (x [M, D], logw unnormalised or None for equal
+        weights) -> psis.PsisLoo: elpd_loo_i from the smoothed ratios, pareto_k_i as its diagnostic, and `plain`, the
+        Pointwise of the same call.  Selection, fit and smoothing run on the device; the matrix ll is never downloaded."""
+        from ..psis import loo_from_context
+        x2 = self._points(x)
+        return loo_from_context(self._context(x2.shape[0]), None, x2, logw)
 
 
 class HierarchicalGLM(PredictMixin, DeviceTarget):

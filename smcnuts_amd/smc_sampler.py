@@ -527,6 +527,27 @@ class SMCSampler:
             return combine_pointwise_partials([p.reshape(part.shape) for p in allp])
         return combine_pointwise_partials([part])
 
+    def loo(self):
+        """Pareto-smoothed importance-sampling LOO (psis.PsisLoo: elpd_loo_i, pareto_k_i, psis_ess_i and `plain`, what
+        pointwise() returns) of the final generation and its weights, after sample() / finalise(): selected, fitted and
+        smoothed on the device from the resident particles.  Several shards: three host all-gathers (the partials' headers
+        for the global mw and S, the ranks' candidates, the body partials), the fit on every rank; every rank returns the
+        same object."""
+        from .psis import loo_from_context
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError("loo(): the asymptotic L-kernel's estimates pool generations; criteria over the "
+                                      "pooled generations are not implemented")
+        if not hasattr(self.target, "pointwise_partials"):
+            self.target.loo(None)               # raises NotImplementedError naming the supported targets
+        if not self._finalised:
+            raise RuntimeError("loo(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"loo(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
+                               "target the posterior")
+        ctx = self.samples.ctx
+        ctx.call("smcn_synchronize")
+        return loo_from_context(ctx, self.comm)
+
     def summary(self, probs=(0.025, 0.25, 0.5, 0.75, 0.975), at=None):
         """Posterior summary (summary.PosteriorSummary: mean, sd, weighted quantiles at `probs`, and with `at` the mass at
         or below each threshold, per constrained parameter) of the final generation and its weights, after sample() /
