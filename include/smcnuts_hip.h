@@ -56,6 +56,16 @@ typedef struct smcn_ctx smcn_ctx;
                               logit^-1(eta_i - c_{k+1}) (c_0 = -inf, c_K = +inf), b_j ~ N(0, s_j^2), c_k ~ N(0, t_k^2) with
                               the log-Jacobian sum_{k>=2} u_k; x = (b_1..b_p, u_1..u_{K-1}), D = p + K - 1 <= 64;
                               constrain reports (b, c_1..c_{K-1}) */
+#define SMCN_MODEL_MLGLM 8   /* multilevel GLM, non-centred, R independent varying terms (slopes, crossed factors): data =
+                              [family (0..3 as SMCN_MODEL_GLM), n, p, intercept, R, J_1, J_2, J_3, J_4 (0 beyond R),
+                              s_1..s_Dc, s_tau_1..s_tau_R, (m_d, s_d: families 2, 3), y_1..y_n, then for each term r = 1..R
+                              g_r1..g_rn (in 0..J_r-1) and z_r1..z_rn (finite; 1 = varying intercept, a covariate = varying
+                              slope), X (n x p, row-major)], 1 <= R <= 4, J_r >= 1, Dc = p + intercept >= 0;
+                              eta_i = [b_0 +] X_i b + sum_r z_ri e^lt_r u_{r,g_ri}, b_c ~ N(0, s_c^2), u_rj ~ N(0, 1),
+                              e^lt_r ~ half-normal(s_tau_r), ld ~ N(m_d, s_d^2) (dispersion e^ld);
+                              x = (b_1..b_Dc, u_1,1..u_1,J1, .., u_R,1..u_R,JR, lt_1..lt_R [, ld]),
+                              D = Dc + sum_r J_r + R (+ 1) <= 64;
+                              constrain reports (b, e^lt_r u_rj .., e^lt_1..e^lt_R [, e^ld]) */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

@@ -98,7 +98,7 @@ struct smcn_ctx {
     int64_t stage_len = 0;
     double* stage2 = nullptr;
     int64_t stage2_len = 0;
-    double* cstage = nullptr;   // SMCN_MODEL_HGLM / ORDINAL: the constrained population the moment kernels read ([ngen][D][N])
+    double* cstage = nullptr;   // SMCN_MODEL_HGLM / ORDINAL / MLGLM: the constrained population the moment kernels read ([ngen][D][N])
     int64_t cstage_len = 0;
     int32_t *nleap = nullptr, *depth = nullptr, *ndraws = nullptr, *flags = nullptr;
     int64_t* idx = nullptr;
@@ -470,6 +470,7 @@ static int with_model(smcn_ctx* c, F&& f) {
     }
     // (smcn_ctx_create has checked the data and refused D > 64)
     if (c->model == SMCN_MODEL_HGLM) return f(GlmHierModel<64, 1>{});
+    if (c->model == SMCN_MODEL_MLGLM) return f(GlmMultiModel<64, 1>{});
     if (c->model == SMCN_MODEL_CATEGORICAL) {
         // (checked at creation: 2 <= K <= 16, D = (K - 1) Dc <= 64)
         if (c->D <= 8) return f(GlmCatModel<8, 1>{});
@@ -585,7 +586,8 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
         case SMCN_MODEL_GLM:
         case SMCN_MODEL_HGLM:
         case SMCN_MODEL_CATEGORICAL:
-        case SMCN_MODEL_ORDINAL: {
+        case SMCN_MODEL_ORDINAL:
+        case SMCN_MODEL_MLGLM: {
             const std::string why = reg_check(model_id, model_data, model_data_len, &c->reg);
             if (!why.empty()) {
                 g_create_error = "smcn_ctx_create: " + why;
@@ -604,9 +606,10 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
     // constrain_coord applies to arma's log sigma (the other models keep their own id)
     c->cmodel = (model_id == SMCN_MODEL_GLM && c->reg.disp()) ? SMCN_MODEL_ARMA : model_id;
-    // hierarchical GLM, ordinal: the constrained space is not coordinate-wise; the moment kernels read a constrained copy
+    // hierarchical and multilevel GLM, ordinal: the constrained space is not coordinate-wise; the moment kernels read a constrained copy
     // of the population (model_constrained) with the identity
-    if (model_id == SMCN_MODEL_HGLM || model_id == SMCN_MODEL_ORDINAL) c->cmodel = SMCN_MODEL_HOST;
+    if (model_id == SMCN_MODEL_HGLM || model_id == SMCN_MODEL_ORDINAL || model_id == SMCN_MODEL_MLGLM)
+        c->cmodel = SMCN_MODEL_HOST;
     auto fail = [&](const char* what, hipError_t er) {
         g_create_error = std::string("smcn_ctx_create: ") + what + ": " + hipGetErrorString(er);
         free_all(c);
@@ -791,17 +794,25 @@ static int ensure_stage2(smcn_ctx* c, int64_t n) {
     return 0;
 }
 // models whose constrained space is not coordinate-wise: the moment kernels read a constrained copy of the population
-static bool has_constrain_pass(const smcn_ctx* c) { return c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_ORDINAL; }
+static bool has_constrain_pass(const smcn_ctx* c) {
+    return c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_ORDINAL || c->model == SMCN_MODEL_MLGLM;
+}
 // their constrain pass over M particles, particle t's coordinate c at x[(t / Np) * Np * D + (t % Np) * si + c * sc]
 static void launch_constrain_pass(smcn_ctx* c, const double* x, double* out, int64_t M, int64_t Np, int64_t si,
                                   int64_t sc) {
     if (c->model == SMCN_MODEL_ORDINAL)
         ord_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D, (int)c->reg.p, si, sc);
-    else
+    else if (c->model == SMCN_MODEL_MLGLM) {
+        MlOffsets off;
+        off.v[0] = c->reg.Dc;
+        for (int r = 0; r < 4; ++r) off.v[r + 1] = off.v[r] + (int)c->reg.Jr[r];
+        mlglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D, c->reg.Dc, c->reg.R, off, si,
+                                                                        sc);
+    } else
         hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D,
                                                                        c->reg.Dc, (int)c->reg.J, si, sc);
 }
-// SMCN_MODEL_HGLM / SMCN_MODEL_ORDINAL: the constrained population of ngen consecutive generations ([ngen][D][N] from x)
+// SMCN_MODEL_HGLM / _ORDINAL / _MLGLM: the constrained population of ngen consecutive generations ([ngen][D][N] from x)
 // into c->cstage, on the context's stream; *out is what the moment kernels then read with the identity (c->cmodel)
 static int model_constrained(smcn_ctx* c, const double* x, int ngen, const double** out) {
     const int64_t M = (int64_t)ngen * c->N, n = M * c->D;

@@ -906,6 +906,183 @@ struct GlmHierModel {
 };
 
 // ---------------------------------------------------------------------------
+// Multilevel GLM, non-centred (SMCN_MODEL_MLGLM): Dc = p + intercept fixed coefficients b and R <= 4 independent varying
+// terms; term r has J_r levels, a level g_ir and a multiplier z_ir per observation (1: varying intercept, a covariate:
+// varying slope; two terms may share a factor),
+//   eta_i = [b_0 +] X_i b + sum_r z_ir e^lt_r u_{r,g_ir},   y_i ~ family(eta_i [, e^ld])   (the SMCN_MODEL_GLM families)
+//   b_c ~ N(0, s_c^2), u_rj ~ N(0, 1), e^lt_r ~ half-normal(s_tau_r) with its Jacobian, ld ~ N(m_d, s_d^2) (families 2, 3).
+// x = (b_1..b_Dc, u_1,1..u_1,J1, .., u_R,1..u_R,JR, lt_1..lt_R [, ld]), D = Dc + sum J_r + R (+ 1) <= 64; one wavefront
+// per particle, coordinate c on lane c.  With R = 1 and z = 1 this is GlmHierModel's density, term for term.
+// The table: a row per observation, [1 (intercept), X_i1 .. X_ip, 0 (to an even count DP), y_i, lgamma(y_i + 1), g_1i, z_1i,
+// .., g_Ri, z_Ri], RS = DP + 2 + 2R doubles, at a 128-byte boundary, zero rows up to a multiple of 64.  The shape is
+// GlmHierModel's -- lane l takes row k0 + l of each 64-row chunk:
+//   eta: the fixed part with the coefficients as scalars, then per term one cross-lane read (ds_bpermute) of u from its
+//        owner, lane off_r + g_ir, times e^lt_r, times z_ir;
+//   the 64-step read-out: in the first pass lane c < Dc accumulates d_i X_ic while the owners of term 1's u compare the
+//        broadcast key off_1 + g_1i with their own lane index and accumulate d_i z_1i; terms 2..R take a pass each over
+//        the broadcast (key, d_i z_ri) -- no lane has to find out which term it belongs to first.  e^lt_r multiplies the
+//        sum at the end;
+//   d / d lt_r = sum_i d_i z_ir e^lt_r u_{r,g_ir} is a per-lane term: with llik, lpri and the dispersion sum up to seven
+//        wave-wide sums, one wave_sum4 for R = 1 (GlmHierModel's) and a second one for terms 2..R.
+// The terms' registers are arrays with compile-time indices under guards on the wave-uniform R (a private array indexed
+// at run time would be placed in scratch).  Non-finite: -inf (lpri and llik) when any e^(2 lt_r) overflows, then the GLM
+// rules.
+// ---------------------------------------------------------------------------
+template <int G_, int DL_>
+struct GlmMultiModel {
+    static_assert(G_ == 64 && DL_ == 1, "GlmMultiModel: one wavefront per particle, one coordinate per lane");
+    static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
+    static constexpr bool DIST = true;
+    static constexpr int RM = kMlMaxTerms;
+    using d2 = double __attribute__((ext_vector_type(2)));
+    GlmModel<64, 1> glm;          // families 0 / 1: obs() (only `poisson` is set)
+    GlmDispModel<64, 1> disp;     // families 2 / 3: tau_const() and obs() (only `nb` is set)
+    int lg, D, Dc, R, LT0, DP, RS, n;
+    int off[RM];                  // first lane of term r's u (wave-uniform)
+    int role;                     // this lane's coordinate: 0 coefficient, 1 a level's u, 2 an lt, 3 ld, 4 none
+    int tr;                       // (roles 1, 2) the lane's term
+    bool hasd;
+    const double* T;              // the repacked table
+    double mc, inv_s2, lc;        // prior of the lane's coordinate: mean, 1 / s^2, constant
+
+    __device__ int dim() const { return D; }
+    __device__ void init(const double* md, int lg_, double*) {
+        lg = lg_;
+        const double fam = md[0];
+        hasd = fam >= 2.0;
+        glm.poisson = fam == 1.0;
+        disp.nb = fam == 3.0;
+        n = (int)md[1];
+        const int p = (int)md[2];
+        Dc = p + (int)md[3];
+        R = (int)md[4];
+        int o = Dc;
+        tr = 0;
+#pragma unroll
+        for (int r = 0; r < RM; ++r) {
+            off[r] = o;
+            o += r < R ? (int)md[5 + r] : 0;
+            tr = (r < R && lg >= off[r]) ? r : tr;             // (u lanes: the last term that starts at or before lg)
+        }
+        LT0 = o;
+        D = LT0 + R + (hasd ? 1 : 0);
+        DP = (Dc + 1) & ~1;
+        RS = mlglm_row_doubles(Dc, R);
+        T = md + mlglm_table_offset(mlglm_head(Dc, R, hasd), R, n, p);
+        role = lg < Dc ? 0 : (lg < LT0 ? 1 : (lg < LT0 + R ? 2 : (lg < D ? 3 : 4)));
+        tr = role == 2 ? lg - LT0 : tr;
+        double s = 1.0;
+        mc = 0.0;
+        if (role == 0) s = md[9 + lg];
+        else if (role == 2) s = md[9 + Dc + tr];
+        else if (role == 3) { mc = md[9 + Dc + R]; s = md[10 + Dc + R]; }
+        inv_s2 = role < 4 ? 1.0 / (s * s) : 0.0;
+        // half-normal on e^lt_r with the Jacobian of lt_r: log 2 - log s_tau_r - log(2 pi) / 2 (+ lt - e^2lt / 2 s_tau_r^2)
+        lc = role == 2 ? (0.69314718055994530942 - log(s)) - 0.5 * kLog2Pi : (role < 4 ? -log(s) - 0.5 * kLog2Pi : 0.0);
+    }
+    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
+        // ---- everything that depends on the lt_r or ld alone, once
+        double tau[RM], e2o = 0.0, tauo = 0.0;                 // (e2o, tauo: the lane's own term's)
+        bool bad = false;
+#pragma unroll
+        for (int r = 0; r < RM; ++r) {
+            tau[r] = 0.0;
+            if (r < R) {
+                tau[r] = exp_fast(group_read<64>(x[0], LT0 + r));
+                const double e2 = tau[r] * tau[r];
+                bad = bad || !(e2 < kInf);                     // e^(2 lt_r) overflows
+                e2o = tr == r ? e2 : e2o;
+                tauo = tr == r ? tau[r] : tauo;
+            }
+        }
+        const auto k = disp.tau_const(hasd ? group_read<64>(x[0], LT0 + R) : 0.0);
+        // ---- prior of the lane's coordinate
+        double lp, g0;
+        if (role == 2) {
+            lp = (lc + x[0]) - 0.5 * e2o * inv_s2;
+            g0 = fma(-e2o, inv_s2, 1.0);
+        } else {
+            const double v = x[0] - mc;
+            g0 = -v * inv_s2;
+            lp = fma(-0.5 * v, v * inv_s2, lc);
+        }
+        // ---- observations, 64 a chunk
+        double acc[4] = {0.0, 0.0, 0.0, 0.0}, ll = 0.0, gt = 0.0, ga[RM] = {0.0, 0.0, 0.0, 0.0};
+        const int col = lg < DP ? lg : 0;
+        const bool grp = role == 1;
+        const double xb = lg < Dc ? x[0] : 0.0;            // (0 on the pad column)
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const d2* const row = (const d2*)(T + (int64_t)(k0 + lg) * RS);
+            double e0 = 0.0, e1 = 0.0;
+            for (int j = 0; j < DP; j += 2) {              // (j wave-uniform: the coefficients are scalar operands)
+                const d2 v = row[j >> 1];
+                e0 = fma(group_read<64>(xb, j), v.x, e0);
+                e1 = fma(group_read<64>(xb, j + 1), v.y, e1);
+            }
+            const d2 yl = row[DP >> 1];
+            int key[RM];                                   // the lane that owns u_{r, g_ir}
+            double z[RM], a[RM], as = 0.0;
+#pragma unroll
+            for (int r = 0; r < RM; ++r) {
+                key[r] = 0, z[r] = 0.0, a[r] = 0.0;
+                if (r < R) {
+                    const d2 gz = row[(DP >> 1) + 1 + r];
+                    key[r] = off[r] + (int)gz.x;
+                    z[r] = gz.y;
+                    a[r] = (tau[r] * __shfl(x[0], key[r], 64)) * z[r];
+                    as = r == 0 ? a[0] : as + a[r];
+                }
+            }
+            const double e = (e0 + e1) + as;
+            double term, d, g = 0.0;
+            if (hasd) disp.obs(k, e, yl.x, yl.y, term, d, g);
+            else glm.obs(e, yl.x, yl.y, term, d);
+            const bool live = k0 + lg < n;
+            ll += live ? term : 0.0;
+            gt += live ? g : 0.0;
+            d = live ? d : 0.0;
+#pragma unroll
+            for (int r = 0; r < RM; ++r)
+                if (r < R) ga[r] = fma(d, a[r], ga[r]);
+            // the chunk's 64 residuals read out as scalars: column `lg` of their rows, or term 1's z where its key is
+            // this lane
+            const double* const colp = T + (int64_t)k0 * RS + col;
+#pragma unroll 16
+            for (int i = 0; i < 64; ++i) {
+                const double w = grp ? (__builtin_amdgcn_readlane(key[0], i) == lg ? lane_value(z[0], i) : 0.0)
+                                     : colp[(int64_t)i * RS];
+                acc[i & 3] = fma(lane_value(d, i), w, acc[i & 3]);
+            }
+            // terms 2..R: d_i z_ri to the lane its key names (a lane of another term or role matches no key)
+#pragma unroll
+            for (int r = 1; r < RM; ++r) {
+                if (r < R) {
+                    const double dz = d * z[r];
+#pragma unroll 16
+                    for (int i = 0; i < 64; ++i)
+                        acc[i & 3] += __builtin_amdgcn_readlane(key[r], i) == lg ? lane_value(dz, i) : 0.0;
+                }
+            }
+        }
+        double L, P, GT, GA[RM];
+        wave_sum4(ll, lp, gt, ga[0], L, P, GT, GA[0]);
+        GA[1] = GA[2] = GA[3] = 0.0;
+        if (R > 1) {
+            double u0;
+            wave_sum4(ga[1], ga[2], ga[3], 0.0, GA[1], GA[2], GA[3], u0);
+        }
+        double GAo = GA[0];
+#pragma unroll
+        for (int r = 1; r < RM; ++r) GAo = tr == r ? GA[r] : GAo;
+        const double cs = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        gl[0] = role == 0 ? cs : (role == 1 ? tauo * cs : (role == 2 ? GAo : (role == 3 ? GT : 0.0)));
+        gp[0] = g0;
+        llik = (bad || k.bad) ? -kInf : L;
+        lpri = bad ? -kInf : P;
+    }
+};
+
+// ---------------------------------------------------------------------------
 // Categorical (multinomial logistic) regression, class 0 the reference (SMCN_MODEL_CATEGORICAL): K classes, Dc = p +
 // intercept columns,
 //   eta_i0 = 0, eta_ik = [b_k0 +] X_i b_k (k = 1..K-1),   log p(y_i) = eta_{i,y_i} - logsumexp(0, eta_i1, .., eta_i,K-1)

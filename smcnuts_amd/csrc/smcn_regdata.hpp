@@ -1,6 +1,6 @@
-// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL) on the host: where the header,
-// the priors, y, g and X sit in the caller's block, which table the functors read behind it, the check of a caller's
-// block and its repacking.  Plain C++17 with no HIP types: it compiles without a device compiler, so the code that
+// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL, _MLGLM) on the host: where the
+// header, the priors, y, g (and z) and X sit in the caller's block, which table the functors read behind it, the check
+// of a caller's block and its repacking.  Plain C++17 with no HIP types: it compiles without a device compiler, so the code that
 // indexes by caller-supplied lengths runs under the host sanitizers (tests/test_regdata_host.py).  The layout helpers
 // are shared with the device functors (smcn_models.hpp), which find the table by the same arithmetic.
 #pragma once
@@ -33,40 +33,51 @@ SMCN_HD inline int64_t hglm_table_offset(int64_t head, int64_t n, int64_t p) {
     return (head + 2 * n + n * p + 15) / 16 * 16;
 }
 SMCN_HD inline int hglm_row_doubles(int Dc) { return ((Dc + 1) & ~1) + 4; }
+// multilevel GLM: up to kMlMaxTerms varying terms; the table starts at the first 128-byte boundary behind the block, a
+// row holds a (g, z) pair per term behind y and lgamma(y + 1)
+constexpr int kMlMaxTerms = 4;
+SMCN_HD inline int64_t mlglm_head(int64_t Dc, int R, bool disp) { return 9 + Dc + R + (disp ? 2 : 0); }
+SMCN_HD inline int64_t mlglm_table_offset(int64_t head, int R, int64_t n, int64_t p) {
+    return (head + (1 + 2 * (int64_t)R) * n + n * p + 15) / 16 * 16;
+}
+SMCN_HD inline int mlglm_row_doubles(int Dc, int R) { return ((Dc + 1) & ~1) + 2 + 2 * R; }
 constexpr int kCatMaxClasses = 16;
 // ordinal: the K class counts behind the table
 SMCN_HD inline int64_t ord_counts_offset(int64_t D, int64_t n, int64_t p) {
     return glm_table_offset(D, n, p) + glm_table_rows(n) * glm_row_doubles((int)p);
 }
 
-// One checked block: the caller's [header nh | priors npri | y n | g n (hierarchical) | X n x p], and its repacked image
+// One checked block: the caller's [header nh | priors npri | y n | g n (hierarchical) or g_r n, z_r n per term
+// (multilevel) | X n x p], and its repacked image
 // [block | padding | table rows x RS | class counts K (ordinal)].
 struct RegLayout {
     int model = 0;
     int fam = 0, K = 0;         // the header's first slot: the family (GLM, hierarchical) or the classes (categorical, ordinal)
-    int64_t n = 0, p = 0, J = 0;
+    int64_t n = 0, p = 0, J = 0;   // (multilevel: J is the sum of the terms' level counts)
+    int R = 0;                  // multilevel: varying terms, and the levels of each (0 beyond R)
+    int64_t Jr[kMlMaxTerms] = {0, 0, 0, 0};
     int ic = 0;                 // intercept flag
     int Dc = 0, D = 0;          // columns of a table row (p for the ordinal model), coordinates
     int64_t nh = 0, npri = 0;   // header doubles, prior doubles
-    int64_t y0 = 0, g0 = 0, X0 = 0, len = 0;      // offsets in the block (g0 = 0: no groups), the block's length
+    int64_t y0 = 0, g0 = 0, X0 = 0, len = 0;      // offsets in the block (g0 = 0: no groups; multilevel: g_1), the block's length
     int64_t t0 = 0, rows = 0;   // the table: offset, padded row count,
-    int RS = 0, ys = 0;         // row width, y slot (lgamma(y + 1) and g follow it)
+    int RS = 0, ys = 0;         // row width, y slot (lgamma(y + 1) and g, or the (g_r, z_r) pairs, follow it)
     int64_t c0 = 0;             // ordinal: offset of the class counts (0 otherwise)
     int64_t rlen = 0;           // length of the repacked image
     bool disp() const { return fam >= 2; }
 };
 
 namespace regdata {
-// What differs between the four models' checks apart from arithmetic: texts and bounds.
+// What differs between the five models' checks apart from arithmetic: texts and bounds.
 struct Spec {
     int nh;
-    bool has_ic, has_J, need_cols;      // header slots 3 and 4; "no coefficients" refusal
+    bool has_ic, has_J, has_R, need_cols;   // header slots 3 and 4 (J, or R with J_1..J_4 behind it); "no coefficients" refusal
     double kmax, pmax;
     const char *who, *layout, *slot0, *too_big, *sds;
 };
 inline const Spec* spec(int model) {
     static const Spec glm = {
-        4, true, false, true, 0.0, 1048576.0, "GLM target: ",
+        4, true, false, false, true, 0.0, 1048576.0, "GLM target: ",
         "GLM target: data = [family, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)]",
         "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log), or 2 (normal) or 3 (neg_binomial_2_log) "
         "with a dispersion prior",
@@ -74,7 +85,7 @@ inline const Spec* spec(int model) {
         "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)",
         "GLM target: prior sds must be finite and > 0"};
     static const Spec hglm = {
-        5, true, true, false, 0.0, 1048576.0, "hierarchical GLM target: ",
+        5, true, true, false, false, 0.0, 1048576.0, "hierarchical GLM target: ",
         "hierarchical GLM target: data = [family, n, p, intercept, J, s_1..s_Dc, s_tau, (m_d, s_d: families "
         "2, 3), y_1..y_n, g_1..g_n, X (n x p, row-major)]",
         "hierarchical GLM target: family must be 0 (bernoulli_logit), 1 (poisson_log), 2 (normal) or 3 "
@@ -84,7 +95,7 @@ inline const Spec* spec(int model) {
         "HostTarget)",
         "hierarchical GLM target: prior sds must be finite and > 0"};
     static const Spec cat = {
-        4, true, false, true, (double)kCatMaxClasses, 1048576.0, "categorical target: ",
+        4, true, false, false, true, (double)kCatMaxClasses, 1048576.0, "categorical target: ",
         "categorical target: data = [K, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], "
         "D = (K - 1) (p + intercept)",
         "categorical target: K must be an integer in [2, 16] (the device functor holds up to 16 classes; more "
@@ -95,7 +106,7 @@ inline const Spec* spec(int model) {
         "through HostTarget)",
         "categorical target: prior sds must be finite and > 0"};
     static const Spec ord = {
-        3, false, false, false, HUGE_VAL, HUGE_VAL, "ordinal target: ",
+        3, false, false, false, false, HUGE_VAL, HUGE_VAL, "ordinal target: ",
         "ordinal target: data = [K, n, p, s_1..s_p, t_1..t_{K-1}, y_1..y_n, X (n x p, row-major)], "
         "D = p + K - 1",
         "ordinal target: K must be an integer >= 2",
@@ -103,11 +114,23 @@ inline const Spec* spec(int model) {
         "host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
         "HostTarget)",
         "ordinal target: prior sds (s for the coefficients, t for the cutpoints) must be finite and > 0"};
+    static const Spec ml = {
+        9, true, false, true, false, 0.0, 1048576.0, "multilevel GLM target: ",
+        "multilevel GLM target: data = [family, n, p, intercept, R, J_1, J_2, J_3, J_4 (0 beyond R), s_1..s_Dc, "
+        "s_tau_1..s_tau_R, (m_d, s_d: families 2, 3), y_1..y_n, then g_r (n) and z_r (n) for each of the R terms, "
+        "X (n x p, row-major)]",
+        "multilevel GLM target: family must be 0 (bernoulli_logit), 1 (poisson_log), 2 (normal) or 3 "
+        "(neg_binomial_2_log)",
+        "multilevel GLM target: the device functor covers D = Dc + J_1 + .. + J_R + R (+ 1) <= 64 coordinates; larger "
+        "models run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad "
+        "through HostTarget)",
+        "multilevel GLM target: prior sds must be finite and > 0"};
     switch (model) {
         case SMCN_MODEL_GLM: return &glm;
         case SMCN_MODEL_HGLM: return &hglm;
         case SMCN_MODEL_CATEGORICAL: return &cat;
         case SMCN_MODEL_ORDINAL: return &ord;
+        case SMCN_MODEL_MLGLM: return &ml;
     }
     return nullptr;
 }
@@ -121,7 +144,8 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     if (!sp) return "not a regression model";
     const auto say = [&](const char* what) { return std::string(sp->who) + what; };
     const bool glm = model == SMCN_MODEL_GLM, hg = model == SMCN_MODEL_HGLM, cat = model == SMCN_MODEL_CATEGORICAL;
-    const bool fams = glm || hg;                 // slot 0 is a family, not a class count
+    const bool ml = model == SMCN_MODEL_MLGLM;
+    const bool fams = glm || hg || ml;                 // slot 0 is a family, not a class count
     if (len < sp->nh) return sp->layout;
     const double s0 = md[0], nd = md[1], pd = md[2], icd = sp->has_ic ? md[3] : 0.0, Jd = sp->has_J ? md[4] : 0.0;
     if (fams ? !(s0 == 0.0 || s0 == 1.0 || s0 == 2.0 || s0 == 3.0) : !whole(s0, 2.0, sp->kmax)) return sp->slot0;
@@ -130,15 +154,31 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     if (!whole(nd, 1.0, 2147483647.0)) return say("n must be an integer >= 1");
     if (!whole(pd, 0.0, sp->pmax)) return say("p must be an integer >= 0");
     if (sp->has_J && !whole(Jd, 1.0, 1048576.0)) return say("J must be an integer >= 1 (the number of groups)");
+    // multilevel: R terms, their level counts in the four slots behind R
+    const double Rd = sp->has_R ? md[4] : 0.0;
+    if (sp->has_R && !whole(Rd, 1.0, (double)kMlMaxTerms))
+        return say("R must be an integer in [1, 4] (the number of varying terms)");
+    double Jsum = 0.0;
+    for (int r = 0; sp->has_R && r < kMlMaxTerms; ++r) {
+        const double v = md[5 + r];
+        if (r < (int)Rd ? !whole(v, 1.0, 1048576.0) : !(v == 0.0))
+            return say("J_r must be an integer >= 1 (the levels of term r) for r <= R and 0 beyond R");
+        Jsum += v;
+    }
     const double Dcd = pd + icd;
     if (sp->need_cols && Dcd < 1.0) return say("no coefficients (p = 0 without an intercept)");
     // (in doubles: the ordinal model bounds neither p nor K before this)
-    const double Dd = glm ? Dcd + (disp ? 1 : 0) : hg ? Dcd + Jd + 1 + (disp ? 1 : 0) : cat ? (s0 - 1.0) * Dcd : pd + s0 - 1.0;
+    const double Dd = glm  ? Dcd + (disp ? 1 : 0)
+                      : hg ? Dcd + Jd + 1 + (disp ? 1 : 0)
+                      : ml ? Dcd + Jsum + Rd + (disp ? 1 : 0)
+                      : cat ? (s0 - 1.0) * Dcd
+                            : pd + s0 - 1.0;
     if (Dd > 64.0) return sp->too_big;
     // the priors: sds, then the named ones -- a mean (finite) or an sd (finite and > 0)
-    struct { const char* name; bool mean; } named[3];
+    struct { const char* name; bool mean; } named[kMlMaxTerms + 2];
     int nn = 0;
     if (hg) named[nn++] = {"s_tau", false};
+    for (int r = 0; r < (int)Rd; ++r) named[nn++] = {"s_tau", false};
     if (disp) {
         named[nn++] = {glm ? "m_tau" : "m_d", true};
         named[nn++] = {glm ? "s_tau" : "s_d", false};
@@ -148,12 +188,16 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     (fams ? l.fam : l.K) = (int)s0;
     l.n = (int64_t)nd, l.p = (int64_t)pd, l.ic = (int)icd, l.J = (int64_t)Jd;
     l.Dc = (int)Dcd, l.D = (int)Dd;
+    if (ml) {
+        l.R = (int)Rd, l.J = (int64_t)Jsum;
+        for (int r = 0; r < l.R; ++r) l.Jr[r] = (int64_t)md[5 + r];
+    }
     const int64_t n = l.n, p = l.p, nsd = fams ? l.Dc : l.D;
     l.nh = sp->nh;
     l.npri = nsd + nn;
     l.y0 = hg ? hglm_head(l.Dc, disp) : l.nh + l.npri;
-    l.g0 = hg ? l.y0 + n : 0;
-    l.X0 = l.y0 + (hg ? 2 : 1) * n;
+    l.g0 = hg || ml ? l.y0 + n : 0;
+    l.X0 = l.y0 + (hg ? 2 : 1 + 2 * l.R) * n;
     l.len = l.X0 + n * p;
     if (len != l.len) {
         // a block laid out for families 0 / 1 but naming a dispersion family
@@ -190,11 +234,22 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
         const double g = md[l.g0 + i];
         if (!(g >= 0.0 && g < Jd && g == std::floor(g))) return say("every group index g must be an integer in [0, J)");
     }
+    for (int r = 0; r < l.R; ++r) {                      // (multilevel) term r: g_r (n), z_r (n)
+        const double* const gr = md + l.g0 + 2 * r * n;
+        for (int64_t i = 0; i < n; ++i)
+            if (!(gr[i] >= 0.0 && gr[i] < (double)l.Jr[r] && gr[i] == std::floor(gr[i])))
+                return say("every group index g_r must be an integer in [0, J_r)");
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(gr[n + i])) return say("z must be finite");
+    }
     for (int64_t t = 0; t < n * p; ++t)
         if (!std::isfinite(md[l.X0 + t])) return say("X must be finite");
     // the table, found as the functors find it (smcn_models.hpp)
-    l.t0 = glm ? glm_table_offset(l.npri, n, p) : hg ? hglm_table_offset(l.y0, n, p) : glm_table_offset(l.D, n, p);
-    l.RS = hg ? hglm_row_doubles(l.Dc) : glm_row_doubles(l.Dc);
+    l.t0 = glm  ? glm_table_offset(l.npri, n, p)
+           : hg ? hglm_table_offset(l.y0, n, p)
+           : ml ? mlglm_table_offset(l.y0, l.R, n, p)
+                : glm_table_offset(l.D, n, p);
+    l.RS = hg ? hglm_row_doubles(l.Dc) : ml ? mlglm_row_doubles(l.Dc, l.R) : glm_row_doubles(l.Dc);
     l.rows = glm_table_rows(n);
     l.ys = (l.Dc + 1) & ~1;
     l.rlen = l.t0 + l.rows * l.RS;
@@ -208,9 +263,9 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
 
 // The image the functors read, from a checked block: `mup` becomes [block | padding | table (| class counts)].  A row is
 // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1) (families; 0 for the normal, whose y may
-// be negative), g_i (hierarchical), 0 ..]; the ordinal model's K class counts n_0..n_{K-1} follow the table.
+// be negative), g_i (hierarchical) or g_1i, z_1i, .., g_Ri, z_Ri (multilevel), 0 ..]; the ordinal model's K class counts n_0..n_{K-1} follow the table.
 inline void reg_repack(const RegLayout& L, const double* md, std::vector<double>& mup) {
-    const bool fams = L.model == SMCN_MODEL_GLM || L.model == SMCN_MODEL_HGLM;
+    const bool fams = L.model == SMCN_MODEL_GLM || L.model == SMCN_MODEL_HGLM || L.model == SMCN_MODEL_MLGLM;
     mup.assign(L.rlen, 0.0);
     std::copy(md, md + L.len, mup.begin());
     for (int64_t i = 0; i < L.n; ++i) {
@@ -220,7 +275,11 @@ inline void reg_repack(const RegLayout& L, const double* md, std::vector<double>
         const double y = md[L.y0 + i];
         row[L.ys] = y;
         if (fams) row[L.ys + 1] = L.fam == 2 ? 0.0 : std::lgamma(y + 1.0);
-        if (L.g0) row[L.ys + 2] = md[L.g0 + i];
+        if (L.g0 && !L.R) row[L.ys + 2] = md[L.g0 + i];
+        for (int r = 0; r < L.R; ++r) {
+            row[L.ys + 2 + 2 * r] = md[L.g0 + 2 * r * L.n + i];
+            row[L.ys + 3 + 2 * r] = md[L.g0 + (2 * r + 1) * L.n + i];
+        }
         if (L.c0) mup[L.c0 + (int64_t)y] += 1.0;
     }
 }

@@ -128,6 +128,24 @@ __global__ void hglm_constrain_kernel(const double* x, double* out, int64_t M, i
         out[base + (int64_t)c * sc] = c < Dc ? v : (c < Dc + J ? tau * v : exp(v));
     }
 }
+// constrain() of the multilevel GLM (SMCN_MODEL_MLGLM): (b, u_1. .., u_R. , lt_1..lt_R [, ld]) -> (b, e^lt_r u_rj ..,
+// e^lt_1..e^lt_R [, e^ld]); term r's u start at coordinate off.v[r] (off.v[R] = the first lt).  Addressing as
+// hglm_constrain_kernel's.
+struct MlOffsets { int v[5]; };
+__global__ void mlglm_constrain_kernel(const double* x, double* out, int64_t M, int64_t Np, int D, int Dc, int R,
+                                       MlOffsets off, int64_t si, int64_t sc) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    const int64_t base = (t / Np) * Np * D + (t % Np) * si;
+    const int lt0 = off.v[R];
+    int r = 0;
+    double tau = exp(x[base + (int64_t)lt0 * sc]);
+    for (int c = 0; c < D; ++c) {
+        const double v = x[base + (int64_t)c * sc];
+        if (c >= Dc && c < lt0 && c >= off.v[r + 1]) tau = exp(x[base + (int64_t)(lt0 + ++r) * sc]);
+        out[base + (int64_t)c * sc] = c < Dc ? v : (c < lt0 ? tau * v : exp(v));
+    }
+}
 // constrain() of the ordinal regression (SMCN_MODEL_ORDINAL): (b, u_1..u_{K-1}) -> (b, c_1..c_{K-1}), c_1 = u_1,
 // c_k = c_{k-1} + e^u_k -- the running sum GlmOrdModel forms, in the same order.  Addressing as hglm_constrain_kernel's.
 __global__ void ord_constrain_kernel(const double* x, double* out, int64_t M, int64_t Np, int D, int p, int64_t si,

@@ -493,6 +493,152 @@ class HierarchicalGLM(PredictMixin, DeviceTarget):
         super().__init__(data, D, names)
 
 
+ML_MAX_TERMS = 4
+
+
+class MultilevelGLM(DeviceTarget):
+    """Multilevel GLM on the device, non-centred: R = 1..4 independent varying terms, term r with J_r levels, a level
+    g_ir and a multiplier z_ir per observation (z = 1: a varying intercept; z = a covariate: a varying slope; two terms
+    may use the same factor -- `(1 + days || subject)` -- or crossed ones -- `(1 | subject) + (1 | item)`),
+      eta_i = [b_0 +] X_i b + sum_r z_ir tau_r u_{r,g_ir},   y_i ~ family(eta_i [, e^ld])   (GLMTarget's four families)
+      b_c ~ N(0, prior_sd_c^2),  u_rj ~ N(0, 1),  tau_r ~ half-normal(group_sd_prior_r) (sampled as lt_r = log tau_r, with
+      its Jacobian),  e^ld ~ lognormal(m, s) for dispersion_prior = (m, s) (families normal / neg_binomial_2_log).
+    x = (b_1..b_Dc, u_1,1..u_1,J1, .., u_R,1..u_R,JR, lt_1..lt_R [, ld]), D = Dc + sum J_r + R (+ 1) <= 64 (larger
+    models: HostTarget); Dc = p + intercept may be 0.  `terms` is a sequence of (groups,), (groups, z) or
+    (groups, z, n_groups): groups in 0..J_r-1 with J_r = max + 1 unless n_groups is given, z=None for ones.  `constrain`
+    reports (b, alpha.r.j = tau_r u_rj .., tau.1..tau.R [, sigma | phi]).  With one term and z = None this is
+    HierarchicalGLM's density.  Held-out prediction and the pointwise criteria do not cover this target.
+
+    Data block (include/smcnuts_hip.h, SMCN_MODEL_MLGLM):
+    [family, n, p, intercept, R, J_1..J_4 (0 beyond R), s_1..s_Dc, s_tau_1..s_tau_R, (m, s: families 2, 3), y_1..y_n,
+     g_1 (n), z_1 (n), .., g_R (n), z_R (n), X (n x p, row-major)]."""
+    model_id = _capi.MODEL_MLGLM
+
+    def __init__(self, X, y, terms, family="bernoulli_logit", prior_sd=2.5, group_sd_prior=1.0, intercept=True,
+                 dispersion_prior=_NO_PRIOR):
+        if family not in GLM_FAMILIES:
+            raise ValueError(f"MultilevelGLM: family must be one of {GLM_FAMILIES}, not {family!r}")
+        disp = family in GLM_DISPERSION
+        if not disp and dispersion_prior is not _NO_PRIOR:
+            raise ValueError(f"MultilevelGLM: {family} has no dispersion parameter; dispersion_prior is for "
+                             f"{tuple(GLM_DISPERSION)}")
+        if disp:
+            m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
+            try:
+                m_d, s_d = (float(v) for v in m_s)
+            except (TypeError, ValueError):
+                raise ValueError("MultilevelGLM: dispersion_prior must be a pair (m, s)") from None
+            if not math.isfinite(m_d):
+                raise ValueError("MultilevelGLM: dispersion_prior's m must be finite")
+            if not (math.isfinite(s_d) and s_d > 0.0):
+                raise ValueError("MultilevelGLM: dispersion_prior's s must be finite and > 0")
+        try:
+            terms = [tuple(t) for t in terms]
+        except TypeError:
+            raise ValueError("MultilevelGLM: terms must be a sequence of (groups,), (groups, z) or (groups, z, n_groups)") \
+                from None
+        R = len(terms)
+        if not 1 <= R <= ML_MAX_TERMS:
+            raise ValueError(f"MultilevelGLM: terms must hold 1 to {ML_MAX_TERMS} varying terms, not {R}")
+        if any(not 1 <= len(t) <= 3 for t in terms):
+            raise ValueError("MultilevelGLM: every term must be (groups,), (groups, z) or (groups, z, n_groups)")
+        try:
+            s_tau = np.asarray(group_sd_prior, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("MultilevelGLM: group_sd_prior must be a number or one per term") from None
+        if s_tau.ndim == 0:
+            s_tau = np.full(R, float(s_tau))
+        if s_tau.shape != (R,):
+            raise ValueError(f"MultilevelGLM: group_sd_prior must be a scalar or one value per term ({R})")
+        if not np.all(np.isfinite(s_tau) & (s_tau > 0.0)):
+            raise ValueError("MultilevelGLM: group_sd_prior must be finite and > 0")
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2:
+            raise ValueError("MultilevelGLM: X must be an (n, p) matrix")
+        n, p = X.shape
+        if n < 1:
+            raise ValueError("MultilevelGLM: at least one observation")
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim != 1 or y.shape[0] != n:
+            raise ValueError(f"MultilevelGLM: y must be a vector of the n = {n} observations X has rows for")
+        gs, zs, Js = [], [], []
+        for r, t in enumerate(terms):
+            g = np.asarray(t[0])
+            if g.ndim != 1 or g.shape[0] != n:
+                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be a vector of the n = {n} observations X has "
+                                 "rows for")
+            if g.dtype == bool or not (np.issubdtype(g.dtype, np.integer) or np.issubdtype(g.dtype, np.floating)):
+                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be integers")
+            gf = g.astype(np.float64)
+            if not np.all(np.isfinite(gf) & (gf == np.floor(gf))):
+                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be integers")
+            if np.any(gf < 0):
+                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be >= 0")
+            if len(t) < 2 or t[1] is None:
+                z = np.ones(n)
+            else:
+                try:
+                    z = np.asarray(t[1], dtype=np.float64)
+                except (TypeError, ValueError):
+                    raise ValueError(f"MultilevelGLM: term {r + 1}: z must be numbers") from None
+                if z.ndim != 1 or z.shape[0] != n:
+                    raise ValueError(f"MultilevelGLM: term {r + 1}: z must be a vector of the n = {n} observations X has "
+                                     "rows for")
+                if not np.all(np.isfinite(z)):
+                    raise ValueError(f"MultilevelGLM: term {r + 1}: z must be finite")
+            J = int(gf.max()) + 1 if len(t) < 3 or t[2] is None else t[2]
+            if isinstance(J, bool) or not isinstance(J, (int, np.integer)) or J < 1:
+                raise ValueError(f"MultilevelGLM: term {r + 1}: n_groups must be an integer >= 1")
+            J = int(J)
+            if gf.max() >= J:
+                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be in 0..n_groups - 1 = {J - 1}")
+            gs.append(gf), zs.append(z.copy()), Js.append(J)
+        ic = 1 if intercept else 0
+        Dc = p + ic
+        D = Dc + sum(Js) + R + (1 if disp else 0)
+        if D > GLM_MAX_DIM:
+            raise ValueError(f"MultilevelGLM: D = {D} coordinates ({Dc} coefficients, {' + '.join(map(str, Js))} levels, "
+                             f"{R} tau{', ' + GLM_DISPERSION[family] if disp else ''}); the device functor covers "
+                             f"D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget "
+                             "instead.")
+        if not np.all(np.isfinite(X)):
+            raise ValueError("MultilevelGLM: X must be finite")
+        if family == "bernoulli_logit":
+            if not np.all((y == 0.0) | (y == 1.0)):
+                raise ValueError("MultilevelGLM: bernoulli_logit needs y in {0, 1}")
+        elif family == "poisson_log":
+            if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
+                raise ValueError("MultilevelGLM: poisson_log needs y in {0, 1, 2, ...}")
+        elif family == "normal":
+            if not np.all(np.isfinite(y)):
+                raise ValueError("MultilevelGLM: normal needs finite y")
+        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
+            raise ValueError("MultilevelGLM: neg_binomial_2_log needs y in {0, 1, 2, ..., 2^53}")
+        s = np.asarray(prior_sd, dtype=np.float64)
+        if s.ndim == 0:
+            s = np.full(Dc, float(s))
+        if s.shape != (Dc,):
+            raise ValueError(f"MultilevelGLM: prior_sd must be a scalar or one value per coefficient ({Dc})")
+        if not np.all(np.isfinite(s) & (s > 0.0)):
+            raise ValueError("MultilevelGLM: prior_sd must be finite and > 0")
+        self.family, self.intercept, self.n_groups = family, bool(intercept), tuple(Js)
+        self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
+        self.term_groups, self.term_z = [g.astype(np.int64) for g in gs], zs
+        self.group_sd_prior = s_tau.copy()
+        self.dispersion_prior = (m_d, s_d) if disp else None
+        head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic), float(R)] \
+            + [float(J) for J in Js] + [0.0] * (ML_MAX_TERMS - R)
+        gz = [v for r in range(R) for v in (gs[r], zs[r])]
+        data = np.concatenate([head, s, s_tau, [m_d, s_d] if disp else [], y] + gz + [X.reshape(-1)])
+        names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)] \
+            + [f"alpha.{r + 1}.{j + 1}" for r in range(R) for j in range(Js[r])] + [f"tau.{r + 1}" for r in range(R)]
+        if disp:
+            names.append(GLM_DISPERSION[family])
+        super().__init__(data, D, names)
+
+
 CAT_MAX_CLASSES = 16
 
 

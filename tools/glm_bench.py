@@ -1,8 +1,8 @@
 """GLM targets (GLMTarget, SMCN_MODEL_GLM; HierarchicalGLM, SMCN_MODEL_HGLM; CategoricalRegression;
-OrdinalRegression) throughput on one MI355X: one JSON line per case.
+OrdinalRegression; MultilevelGLM, SMCN_MODEL_MLGLM) throughput on one MI355X: one JSON line per case.
 
     python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096] [--families normal,neg_binomial_2_log]
-                              [--models glm,hier,cat,ord]
+                              [--models glm,hier,cat,ord,multi]
 
 GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
 (1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)}, poisson_log at (1 000, 25), and normal and neg_binomial_2_log
@@ -20,6 +20,10 @@ Categorical cases (CategoricalRegression, D = (K - 1) Dc): (K, n, Dc) in {(3, 10
 the (5, 1 000, 6) one also against HostTarget with tests/_cat.py's numpy density; flop count 4 n D per leapfrog.
 Ordinal cases (OrdinalRegression, D = p + K - 1): (K, n, p) in {(5, 100, 3), (5, 1 000, 20), (10, 1 000, 40)}, the
 (5, 1 000, 20) one also against HostTarget with tests/_ord.py's numpy density; flop count 4 n p per leapfrog.
+Multilevel cases (--models multi; MultilevelGLM, not in the default set): (a) the hierarchical logistic case (n = 1 000,
+Dc = 5, J = 20) expressed as MultilevelGLM with one term and z = 1, against HierarchicalGLM on the same data, step and
+seed in one process, the two alternated five times -- both medians, their min..max and the ratio of the medians; (b)
+normal, n = 1 000, Dc = 3, an intercept and a slope on one factor of 18 levels.  Flop count 4 n (Dc + R) per leapfrog.
 """
 import argparse
 import json
@@ -50,6 +54,7 @@ CAT_HOST_CASES = ((5, 1000, 6),)
 # ordinal: (classes K, n, p); D = p + K - 1: 7 (the 8-lane shape), 24, 49
 ORD_CASES = [(5, 100, 3), (5, 1000, 20), (10, 1000, 40)]
 ORD_HOST_CASES = ((5, 1000, 20),)
+MULTI_REPEATS = 5
 
 
 def pick_step(target, N, seed):
@@ -92,7 +97,7 @@ def main():
     ap.add_argument("--families", default=None, help="comma-separated subset of the families (default: all)")
     ap.add_argument("--models", default="glm,hier,cat,ord",
                     help="comma-separated: glm (GLMTarget cases), hier (HierarchicalGLM cases), cat (CategoricalRegression), "
-                         "ord (OrdinalRegression)")
+                         "ord (OrdinalRegression); multi (MultilevelGLM, not in the default set)")
     a = ap.parse_args()
     models = set(a.models.split(","))
     import _glm
@@ -130,6 +135,8 @@ def main():
         cat(a)
     if "ord" in models:
         ordinal(a)
+    if "multi" in models:
+        multi(a)
 
 
 def hier(a, fams):
@@ -203,6 +210,51 @@ def ordinal(a):
             print(json.dumps(dict(case=f"ord_K{K}_n{n}_p{p}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
                                   device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
                                   speedup=host["run_s"] / dev["run_s"])), flush=True)
+
+
+def multi(a):
+    import _hglm
+    import _mlglm
+    from smcnuts_amd import HierarchicalGLM, MultilevelGLM
+    # (a) HIER_CASES[0] as one varying-intercept term, alternated with HierarchicalGLM
+    family, n, Dc, J = HIER_CASES[0]
+    D = Dc + J + 1
+    X, y, g = _hglm.synthetic(family, n, Dc - 1, J, 2000 + D)
+    th = HierarchicalGLM(X, y, g, family=family, prior_sd=2.0, group_sd_prior=1.0, n_groups=J)
+    tm = MultilevelGLM(X, y, [(g, None, J)], family=family, prior_sd=2.0, group_sd_prior=1.0)
+    eps, pilot = pick_step(th, a.N, 5)
+    run(th, a.N, 2, eps, 6)
+    run(tm, a.N, 2, eps, 6)
+    rh, rm = [], []
+    for _ in range(MULTI_REPEATS):
+        rh.append(run(th, a.N, a.K, eps, 7))
+        rm.append(run(tm, a.N, a.K, eps, 7))
+
+    def stats(rs):
+        v = sorted(r["leapfrog_per_s"] for r in rs)
+        return dict(median=v[len(v) // 2], min=v[0], max=v[-1])
+    sh, sm = stats(rh), stats(rm)
+    r = dict(rm[-1])
+    r.update(case=f"multi_R1_{family}_n{n}_Dc{Dc}_J{J}_vs_hier", family=family, n=n, Dc=Dc, J=[J], R=1, D=D, N=a.N,
+             K=a.K, step_size=eps, pilot_nleap=pilot, repeats=MULTI_REPEATS, leapfrog_per_s=sm["median"],
+             multi_leapfrog_per_s=sm, hier_leapfrog_per_s=sh, ratio_multi_over_hier=sm["median"] / sh["median"],
+             hier_spread=(sh["max"] - sh["min"]) / sh["median"],
+             same_leapfrogs=all(q["leapfrogs"] == rh[0]["leapfrogs"] for q in rh + rm),
+             fp64_tflops=4.0 * n * (Dc + 1) * sm["median"] / 1e12)
+    r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
+    print(json.dumps(r), flush=True)
+    # (b) normal, an intercept and a slope on one factor of 18 levels
+    family, n, Dc, J = "normal", 1000, 3, 18
+    D = Dc + 2 * J + 2 + 1
+    X, y, terms = _mlglm.synthetic(family, n, Dc - 1, [(J, 0), (J, 0)], 2000 + D)
+    t = MultilevelGLM(X, y, terms, family=family, prior_sd=2.0, group_sd_prior=1.0, dispersion_prior=(0.0, 2.5))
+    eps, pilot = pick_step(t, a.N, 5)
+    run(t, a.N, 2, eps, 6)
+    r = run(t, a.N, a.K, eps, 7)
+    r.update(case=f"multi_R2_{family}_n{n}_Dc{Dc}_J{J}x2", family=family, n=n, Dc=Dc, J=[J, J], R=2, D=D, N=a.N, K=a.K,
+             step_size=eps, pilot_nleap=pilot, fp64_tflops=4.0 * n * (Dc + 2) * r["leapfrog_per_s"] / 1e12)
+    r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
+    print(json.dumps(r), flush=True)
 
 
 if __name__ == "__main__":
