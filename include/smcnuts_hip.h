@@ -66,6 +66,12 @@ typedef struct smcn_ctx smcn_ctx;
                               x = (b_1..b_Dc, u_1,1..u_1,J1, .., u_R,1..u_R,JR, lt_1..lt_R [, ld]),
                               D = Dc + sum_r J_r + R (+ 1) <= 64;
                               constrain reports (b, e^lt_r u_rj .., e^lt_1..e^lt_R [, e^ld]) */
+#define SMCN_MODEL_WGLM 9    /* wide GLM: SMCN_MODEL_GLM's model and data block, word for word (families 0..3, the same priors,
+                              the same constrained space (b [, e^tau])), for 65 <= D <= 256 coordinates (D = p + intercept, + 1
+                              for tau in families 2 and 3).  D <= 64 is refused (SMCN_MODEL_GLM), D > 256 runs host-evaluated.
+                              Sampling, moments, summaries and shards as for any device model; the pointwise criteria,
+                              PSIS-LOO, prediction and predictive draws keep a row in registers and stay with
+                              SMCN_MODEL_GLM; smcn_gauss_lkernel_sums refuses D > 64 as for every model */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

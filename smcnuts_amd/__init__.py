@@ -10,7 +10,7 @@ on this path and no CPU fallback.
 from .smc_sampler import SMCSampler  # noqa: F401
 from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GLMTarget, HierarchicalGLM,  # noqa: F401
                             HostTarget, IsoGaussian, LinearRegression, LogisticRegression, MultilevelGLM,
-                            NegativeBinomialRegression, OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel)
+                            NegativeBinomialRegression, OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel, WideGLMTarget)
 from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F401
 from .psis import PsisLoo, compare_loo, merge_candidates, tail_len  # noqa: F401
 from .predict import Prediction, PredictiveDraws, combine_predict_partials, compare_heldout  # noqa: F401

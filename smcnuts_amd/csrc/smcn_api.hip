@@ -471,6 +471,11 @@ static int with_model(smcn_ctx* c, F&& f) {
     // (smcn_ctx_create has checked the data and refused D > 64)
     if (c->model == SMCN_MODEL_HGLM) return f(GlmHierModel<64, 1>{});
     if (c->model == SMCN_MODEL_MLGLM) return f(GlmMultiModel<64, 1>{});
+    if (c->model == SMCN_MODEL_WGLM) {
+        // (checked at creation: 65 <= D <= 256; two or four coordinates per lane, the tree stack in HBM)
+        if (c->D <= 128) return f(GlmWideModel<64, 2>{});
+        return f(GlmWideModel<64, 4>{});
+    }
     if (c->model == SMCN_MODEL_CATEGORICAL) {
         // (checked at creation: 2 <= K <= 16, D = (K - 1) Dc <= 64)
         if (c->D <= 8) return f(GlmCatModel<8, 1>{});
@@ -587,7 +592,8 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
         case SMCN_MODEL_HGLM:
         case SMCN_MODEL_CATEGORICAL:
         case SMCN_MODEL_ORDINAL:
-        case SMCN_MODEL_MLGLM: {
+        case SMCN_MODEL_MLGLM:
+        case SMCN_MODEL_WGLM: {
             const std::string why = reg_check(model_id, model_data, model_data_len, &c->reg);
             if (!why.empty()) {
                 g_create_error = "smcn_ctx_create: " + why;
@@ -605,7 +611,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     c->Dc = c->D;
     // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
     // constrain_coord applies to arma's log sigma (the other models keep their own id)
-    c->cmodel = (model_id == SMCN_MODEL_GLM && c->reg.disp()) ? SMCN_MODEL_ARMA : model_id;
+    c->cmodel = ((model_id == SMCN_MODEL_GLM || model_id == SMCN_MODEL_WGLM) && c->reg.disp()) ? SMCN_MODEL_ARMA : model_id;
     // hierarchical and multilevel GLM, ordinal: the constrained space is not coordinate-wise; the moment kernels read a constrained copy
     // of the population (model_constrained) with the identity
     if (model_id == SMCN_MODEL_HGLM || model_id == SMCN_MODEL_ORDINAL || model_id == SMCN_MODEL_MLGLM)

@@ -1083,6 +1083,132 @@ struct GlmMultiModel {
 };
 
 // ---------------------------------------------------------------------------
+// Wide GLM (SMCN_MODEL_WGLM): SMCN_MODEL_GLM's density -- the four families, the same data block, the same table -- for
+// 65 <= D <= 256 coordinates.  One wavefront per particle, coordinate c = lane + 64 k in slot k of lane `lane`
+// (DL = 2: D <= 128, DL = 4: D <= 256); x = (b_1..b_Dc [, tau]), tau on lane Dc % 64, slot Dc / 64.  A sibling of
+// GlmModel<64, 1> / GlmDispModel<64, 1>, not a switch on them (their instruction streams stay as they are); the
+// per-observation terms are their own obs() (and tau_const()), called on members of which only the family flag is set,
+// the family a wave-uniform runtime branch as in GlmHierModel.  One evaluation walks the observations in chunks of 64, one
+// row per lane, in two passes over the chunk:
+//   eta: slot by slot, the coefficient of column 64 k + j read out of lane j as a scalar operand, the lane's own row read
+//        with 16-byte loads, two accumulators;
+//   column sums: the chunk's 64 residuals read out as scalars; lane l accumulates d_i T[(k0 + i) RS + l + 64 k] for
+//        every slot k that has columns -- DL independent chains per lane (two accumulators each), every read a coalesced
+//        512-byte line, and the sums land on the owning lane and slot with no butterfly.
+// The dispersion sum, llik and lpri go through one wave_sum4.  No atomics, no LDS: a result depends on its inputs alone.
+// Slots without columns (D <= 64 (k + 1) - 64) are skipped under wave-uniform bounds kept out of lane masks (`uniform`).
+// ---------------------------------------------------------------------------
+template <int G_, int DL_>
+struct GlmWideModel {
+    static_assert(G_ == 64 && (DL_ == 2 || DL_ == 4), "GlmWideModel: one wavefront per particle, two or four coordinates per lane");
+    // (four coordinates per lane: the NUTS kernel holds 15 vectors of them -- 120 registers -- beside the evaluation; with
+    //  two wavefronts per SIMD (256 registers) it spilled 340 B per lane, with one it needs no scratch.  DESIGN.md 4.4)
+    static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = DL_ == 2 ? 2 : 1, LDS_LEVELS = 2;
+    static constexpr bool DIST = true;
+    using d2 = double __attribute__((ext_vector_type(2)));
+    GlmModel<64, 1> glm;          // families 0 / 1: obs() (only `poisson` is set)
+    GlmDispModel<64, 1> disp;     // families 2 / 3: tau_const() and obs() (only `nb` is set)
+    int lg, D, Dc, DP, RS, n;
+    bool hasd;
+    const double* T;              // the repacked table
+    double mc[DL], inv_s2[DL], lc[DL];   // prior mean, 1 / s^2 and -log s - log(2 pi) / 2 of the lane's coordinates
+
+    // a wave-uniform bound the compiler may not hoist into a lane mask per unrolled slot (smcn_predict.hpp: pr_opaque)
+    static __device__ __forceinline__ int uniform(int v) {
+        asm volatile("" : "+s"(v));
+        return v;
+    }
+    __device__ int dim() const { return D; }
+    __device__ void init(const double* md, int lg_, double*) {
+        lg = lg_;
+        const double fam = md[0];
+        hasd = fam >= 2.0;
+        glm.poisson = fam == 1.0;
+        disp.nb = fam == 3.0;
+        n = (int)md[1];
+        const int p = (int)md[2];
+        Dc = p + (int)md[3];
+        D = Dc + (hasd ? 1 : 0);
+        DP = (Dc + 1) & ~1;
+        RS = glm_row_doubles(Dc);
+        T = md + glm_table_offset(Dc + (hasd ? 2 : 0), n, p);
+#pragma unroll
+        for (int i = 0; i < DL; ++i) {
+            const int c = lg + G * i;
+            const bool isd = hasd && c == Dc;
+            const double s = c < Dc ? md[4 + c] : (isd ? md[5 + Dc] : 1.0);
+            mc[i] = isd ? md[4 + Dc] : 0.0;
+            inv_s2[i] = c < D ? 1.0 / (s * s) : 0.0;
+            lc[i] = c < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
+        }
+    }
+    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
+        double ll = 0.0, lp = 0.0, gt = 0.0;
+        double xb[DL];                                     // the coefficients (0 for tau, the pad column and beyond)
+        int col[DL];                                       // the lane's column of slot k (0 where the slot's column is past DP)
+#pragma unroll
+        for (int k = 0; k < DL; ++k) {
+            const double v = x[k] - mc[k];
+            gp[k] = -v * inv_s2[k];
+            lp += fma(-0.5 * v, v * inv_s2[k], lc[k]);
+            xb[k] = lg + G * k < Dc ? x[k] : 0.0;
+            col[k] = lg + G * k < DP ? lg + G * k : 0;
+        }
+        double xt = x[0];
+#pragma unroll
+        for (int k = 1; k < DL; ++k) xt = (Dc >> 6) == k ? x[k] : xt;
+        const auto tc = disp.tau_const(hasd ? group_read<64>(xt, Dc & 63) : 0.0);
+        double acc[DL][2];
+#pragma unroll
+        for (int k = 0; k < DL; ++k) acc[k][0] = acc[k][1] = 0.0;
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const int dp = uniform(DP);
+            // ---- eta of row k0 + lg
+            const d2* const row = (const d2*)(T + (int64_t)(k0 + lg) * RS);
+            double e0 = 0.0, e1 = 0.0;
+#pragma unroll
+            for (int k = 0; k < DL; ++k) {
+                const int jn = dp - 64 * k < 64 ? dp - 64 * k : 64;   // (wave-uniform; <= 0: the slot has no columns)
+#pragma unroll 4
+                for (int j = 0; j < jn; j += 2) {          // (j wave-uniform: the coefficients are scalar operands)
+                    const d2 v = row[(64 * k + j) >> 1];
+                    e0 = fma(group_read<64>(xb[k], j), v.x, e0);
+                    e1 = fma(group_read<64>(xb[k], j + 1), v.y, e1);
+                }
+            }
+            const double e = e0 + e1;
+            const d2 yl = row[dp >> 1];
+            double term, d, g = 0.0;
+            if (hasd) disp.obs(tc, e, yl.x, yl.y, term, d, g);
+            else glm.obs(e, yl.x, yl.y, term, d);
+            const bool live = k0 + lg < n;
+            ll += live ? term : 0.0;
+            gt += live ? g : 0.0;
+            d = live ? d : 0.0;
+            // ---- the chunk's 64 residuals read out as scalars: the lane's column of every slot, weighted by them
+            const double* const base = T + (int64_t)k0 * RS;
+#pragma unroll 4
+            for (int i = 0; i < 64; ++i) {
+                const double di = lane_value(d, i);
+                const double* const ri = base + (int64_t)i * RS;
+#pragma unroll
+                for (int k = 0; k < DL; ++k)
+                    if (64 * k < dp) acc[k][i & 1] = fma(di, ri[col[k]], acc[k][i & 1]);
+            }
+        }
+        double L, P, GT, u1;
+        wave_sum4(ll, lp, gt, 0.0, L, P, GT, u1);
+#pragma unroll
+        for (int k = 0; k < DL; ++k) {
+            const int c = lg + G * k;
+            gl[k] = c < Dc ? acc[k][0] + acc[k][1] : ((hasd && c == Dc) ? GT : 0.0);
+        }
+        llik = (hasd && tc.bad) ? -kInf : L;
+        lpri = P;
+    }
+};
+
+// ---------------------------------------------------------------------------
 // Categorical (multinomial logistic) regression, class 0 the reference (SMCN_MODEL_CATEGORICAL): K classes, Dc = p +
 // intercept columns,
 //   eta_i0 = 0, eta_ik = [b_k0 +] X_i b_k (k = 1..K-1),   log p(y_i) = eta_{i,y_i} - logsumexp(0, eta_i1, .., eta_i,K-1)

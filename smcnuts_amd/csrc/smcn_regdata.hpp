@@ -1,4 +1,4 @@
-// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL, _MLGLM) on the host: where the
+// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL, _MLGLM, _WGLM) on the host: where the
 // header, the priors, y, g (and z) and X sit in the caller's block, which table the functors read behind it, the check
 // of a caller's block and its repacking.  Plain C++17 with no HIP types: it compiles without a device compiler, so the code that
 // indexes by caller-supplied lengths runs under the host sanitizers (tests/test_regdata_host.py).  The layout helpers
@@ -68,12 +68,14 @@ struct RegLayout {
 };
 
 namespace regdata {
-// What differs between the five models' checks apart from arithmetic: texts and bounds.
+// What differs between the models' checks apart from arithmetic: texts and bounds.
 struct Spec {
     int nh;
     bool has_ic, has_J, has_R, need_cols;   // header slots 3 and 4 (J, or R with J_1..J_4 behind it); "no coefficients" refusal
     double kmax, pmax;
     const char *who, *layout, *slot0, *too_big, *sds;
+    double dmin, dmax;                      // the coordinates the model's functors cover: dmin <= D <= dmax
+    const char* too_small;                  // the refusal below dmin (none: dmin = 0)
 };
 inline const Spec* spec(int model) {
     static const Spec glm = {
@@ -83,7 +85,7 @@ inline const Spec* spec(int model) {
         "with a dispersion prior",
         "GLM target: the device functor covers D <= 64 coefficients; larger models run host-evaluated "
         "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)",
-        "GLM target: prior sds must be finite and > 0"};
+        "GLM target: prior sds must be finite and > 0", 0.0, 64.0, nullptr};
     static const Spec hglm = {
         5, true, true, false, false, 0.0, 1048576.0, "hierarchical GLM target: ",
         "hierarchical GLM target: data = [family, n, p, intercept, J, s_1..s_Dc, s_tau, (m_d, s_d: families "
@@ -93,7 +95,7 @@ inline const Spec* spec(int model) {
         "hierarchical GLM target: the device functor covers D = Dc + J + 1 (+ 1) <= 64 coordinates; larger models "
         "run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
         "HostTarget)",
-        "hierarchical GLM target: prior sds must be finite and > 0"};
+        "hierarchical GLM target: prior sds must be finite and > 0", 0.0, 64.0, nullptr};
     static const Spec cat = {
         4, true, false, false, true, (double)kCatMaxClasses, 1048576.0, "categorical target: ",
         "categorical target: data = [K, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], "
@@ -104,7 +106,7 @@ inline const Spec* spec(int model) {
         "categorical target: the device functor covers D = (K - 1) (p + intercept) <= 64 coefficients; larger "
         "models run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad "
         "through HostTarget)",
-        "categorical target: prior sds must be finite and > 0"};
+        "categorical target: prior sds must be finite and > 0", 0.0, 64.0, nullptr};
     static const Spec ord = {
         3, false, false, false, false, HUGE_VAL, HUGE_VAL, "ordinal target: ",
         "ordinal target: data = [K, n, p, s_1..s_p, t_1..t_{K-1}, y_1..y_n, X (n x p, row-major)], "
@@ -113,7 +115,7 @@ inline const Spec* spec(int model) {
         "ordinal target: the device functor covers D = p + K - 1 <= 64 coordinates; larger models run "
         "host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
         "HostTarget)",
-        "ordinal target: prior sds (s for the coefficients, t for the cutpoints) must be finite and > 0"};
+        "ordinal target: prior sds (s for the coefficients, t for the cutpoints) must be finite and > 0", 0.0, 64.0, nullptr};
     static const Spec ml = {
         9, true, false, true, false, 0.0, 1048576.0, "multilevel GLM target: ",
         "multilevel GLM target: data = [family, n, p, intercept, R, J_1, J_2, J_3, J_4 (0 beyond R), s_1..s_Dc, "
@@ -124,9 +126,20 @@ inline const Spec* spec(int model) {
         "multilevel GLM target: the device functor covers D = Dc + J_1 + .. + J_R + R (+ 1) <= 64 coordinates; larger "
         "models run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad "
         "through HostTarget)",
-        "multilevel GLM target: prior sds must be finite and > 0"};
+        "multilevel GLM target: prior sds must be finite and > 0", 0.0, 64.0, nullptr};
+    static const Spec wglm = {
+        4, true, false, false, true, 0.0, 1048576.0, "wide GLM target: ",
+        "wide GLM target: data = [family, n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)] (SMCN_MODEL_GLM's block)",
+        "wide GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log), or 2 (normal) or 3 (neg_binomial_2_log) "
+        "with a dispersion prior",
+        "wide GLM target: the device functor covers 65 <= D <= 256 coordinates; larger models run host-evaluated "
+        "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)",
+        "wide GLM target: prior sds must be finite and > 0", 65.0, 256.0,
+        "wide GLM target: the device functor covers 65 <= D <= 256 coordinates (D counts tau for families 2 and 3); "
+        "D <= 64 is SMCN_MODEL_GLM's (GLMTarget)"};
     switch (model) {
         case SMCN_MODEL_GLM: return &glm;
+        case SMCN_MODEL_WGLM: return &wglm;
         case SMCN_MODEL_HGLM: return &hglm;
         case SMCN_MODEL_CATEGORICAL: return &cat;
         case SMCN_MODEL_ORDINAL: return &ord;
@@ -143,7 +156,7 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     const regdata::Spec* const sp = regdata::spec(model);
     if (!sp) return "not a regression model";
     const auto say = [&](const char* what) { return std::string(sp->who) + what; };
-    const bool glm = model == SMCN_MODEL_GLM, hg = model == SMCN_MODEL_HGLM, cat = model == SMCN_MODEL_CATEGORICAL;
+    const bool glm = model == SMCN_MODEL_GLM || model == SMCN_MODEL_WGLM, hg = model == SMCN_MODEL_HGLM, cat = model == SMCN_MODEL_CATEGORICAL;
     const bool ml = model == SMCN_MODEL_MLGLM;
     const bool fams = glm || hg || ml;                 // slot 0 is a family, not a class count
     if (len < sp->nh) return sp->layout;
@@ -173,7 +186,8 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
                       : ml ? Dcd + Jsum + Rd + (disp ? 1 : 0)
                       : cat ? (s0 - 1.0) * Dcd
                             : pd + s0 - 1.0;
-    if (Dd > 64.0) return sp->too_big;
+    if (Dd > sp->dmax) return sp->too_big;
+    if (Dd < sp->dmin) return sp->too_small;
     // the priors: sds, then the named ones -- a mean (finite) or an sd (finite and > 0)
     struct { const char* name; bool mean; } named[kMlMaxTerms + 2];
     int nn = 0;
@@ -202,12 +216,12 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     if (len != l.len) {
         // a block laid out for families 0 / 1 but naming a dispersion family
         if (glm && disp && len == l.len - 2)
-            return "GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log) for a block without m_tau, s_tau; "
-                   "families 2 (normal) and 3 (neg_binomial_2_log) take data = [family, n, p, intercept, s_1..s_Dc, "
-                   "m_tau, s_tau, y_1..y_n, X]";
+            return say("family must be 0 (bernoulli_logit) or 1 (poisson_log) for a block without m_tau, s_tau; "
+                       "families 2 (normal) and 3 (neg_binomial_2_log) take data = [family, n, p, intercept, s_1..s_Dc, "
+                       "m_tau, s_tau, y_1..y_n, X]");
         if (glm && disp)
-            return "GLM target: data = [family, n, p, intercept, s_1..s_Dc, m_tau, s_tau, y_1..y_n, "
-                   "X (n x p, row-major)] for families 2 (normal) and 3 (neg_binomial_2_log)";
+            return say("data = [family, n, p, intercept, s_1..s_Dc, m_tau, s_tau, y_1..y_n, "
+                       "X (n x p, row-major)] for families 2 (normal) and 3 (neg_binomial_2_log)");
         return sp->layout;
     }
     const auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
@@ -265,7 +279,8 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
 // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1) (families; 0 for the normal, whose y may
 // be negative), g_i (hierarchical) or g_1i, z_1i, .., g_Ri, z_Ri (multilevel), 0 ..]; the ordinal model's K class counts n_0..n_{K-1} follow the table.
 inline void reg_repack(const RegLayout& L, const double* md, std::vector<double>& mup) {
-    const bool fams = L.model == SMCN_MODEL_GLM || L.model == SMCN_MODEL_HGLM || L.model == SMCN_MODEL_MLGLM;
+    const bool fams = L.model == SMCN_MODEL_GLM || L.model == SMCN_MODEL_HGLM || L.model == SMCN_MODEL_MLGLM ||
+                      L.model == SMCN_MODEL_WGLM;
     mup.assign(L.rlen, 0.0);
     std::copy(md, md + L.len, mup.begin());
     for (int64_t i = 0; i < L.n; ++i) {

@@ -260,7 +260,77 @@ class PRMwCDModel(DeviceTarget):
 GLM_FAMILIES = ("bernoulli_logit", "poisson_log", "normal", "neg_binomial_2_log")
 GLM_DISPERSION = {"normal": "sigma", "neg_binomial_2_log": "phi"}    # the families with a sampled scale, and its name
 GLM_MAX_DIM = 64
+WGLM_MAX_DIM = 256                         # WideGLMTarget: GLM_MAX_DIM < D <= this
 _NO_PRIOR = object()
+
+
+def _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior):
+    """GLMTarget's and WideGLMTarget's constructor: the checks (messages prefixed with the class's name), the
+    attributes and the SMCN_MODEL_GLM data block.  `limit(what, D)` raises where the class does not cover D."""
+    who = type(self).__name__
+    if family not in GLM_FAMILIES:
+        raise ValueError(f"{who}: family must be one of {GLM_FAMILIES}, not {family!r}")
+    disp = family in GLM_DISPERSION
+    if not disp and dispersion_prior is not _NO_PRIOR:
+        raise ValueError(f"{who}: {family} has no dispersion parameter; dispersion_prior is for "
+                         f"{tuple(GLM_DISPERSION)}")
+    if disp:
+        m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
+        try:
+            m_tau, s_tau = (float(v) for v in m_s)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: dispersion_prior must be a pair (m, s)") from None
+        if not math.isfinite(m_tau):
+            raise ValueError(f"{who}: dispersion_prior's m must be finite")
+        if not (math.isfinite(s_tau) and s_tau > 0.0):
+            raise ValueError(f"{who}: dispersion_prior's s must be finite and > 0")
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    if X.ndim != 2:
+        raise ValueError(f"{who}: X must be an (n, p) matrix")
+    n, p = X.shape
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.shape[0] != n:
+        raise ValueError(f"{who}: y must be a vector of the n = {n} observations X has rows for")
+    if n < 1:
+        raise ValueError(f"{who}: at least one observation")
+    ic = 1 if intercept else 0
+    Dc = p + ic
+    D = Dc + (1 if disp else 0)
+    if Dc < 1:
+        raise ValueError(f"{who}: no coefficients (p = 0 without an intercept)")
+    limit(f"D = {D} coefficients" if not disp else f"D = {D} coordinates ({Dc} coefficients and tau)", D)
+    if not np.all(np.isfinite(X)):
+        raise ValueError(f"{who}: X must be finite")
+    if family == "bernoulli_logit":
+        if not np.all((y == 0.0) | (y == 1.0)):
+            raise ValueError(f"{who}: bernoulli_logit needs y in {{0, 1}}")
+    elif family == "poisson_log":
+        if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
+            raise ValueError(f"{who}: poisson_log needs y in {{0, 1, 2, ...}}")
+    elif family == "normal":
+        if not np.all(np.isfinite(y)):
+            raise ValueError(f"{who}: normal needs finite y")
+    elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
+        raise ValueError(f"{who}: neg_binomial_2_log needs y in {{0, 1, 2, ..., 2^53}}")
+    s = np.asarray(prior_sd, dtype=np.float64)
+    if s.ndim == 0:
+        s = np.full(Dc, float(s))
+    if s.shape != (Dc,):
+        raise ValueError(f"{who}: prior_sd must be a scalar or one value per coefficient ({Dc})"
+                         if disp else f"{who}: prior_sd must be a scalar or one value per coefficient (D = {D})")
+    if not np.all(np.isfinite(s) & (s > 0.0)):
+        raise ValueError(f"{who}: prior_sd must be finite and > 0")
+    self.family, self.intercept = family, bool(intercept)
+    self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
+    self.dispersion_prior = (m_tau, s_tau) if disp else None
+    head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic)]
+    data = np.concatenate([head, s, [m_tau, s_tau] if disp else [], y, X.reshape(-1)])
+    names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)]
+    if disp:
+        names.append(GLM_DISPERSION[family])
+    DeviceTarget.__init__(self, data, D, names)
 
 
 class GLMTarget(PredictMixin, DeviceTarget):
@@ -272,7 +342,7 @@ class GLMTarget(PredictMixin, DeviceTarget):
       neg_binomial_2_log: y_i ~ neg_binomial_2_log(eta_i, phi)   (Stan's parameterisation: mean e^eta, var mu + mu^2 / phi)
     The two last families sample tau = log sigma / log phi as the last coordinate (D = Dc + 1), with the prior
     tau ~ N(m, s^2) for dispersion_prior = (m, s) -- sigma / phi ~ lognormal(m, s); `constrain` reports sigma / phi.
-    Coordinates are unconstrained; log pi_phi = lpri + phi * llik.  D <= 64 (larger models: HostTarget).
+    Coordinates are unconstrained; log pi_phi = lpri + phi * llik.  D <= 64 (65..256: WideGLMTarget; beyond: HostTarget).
 
     Data block (include/smcnuts_hip.h, SMCN_MODEL_GLM):
     [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], or
@@ -280,72 +350,12 @@ class GLMTarget(PredictMixin, DeviceTarget):
     model_id = _capi.MODEL_GLM
 
     def __init__(self, X, y, family="bernoulli_logit", prior_sd=2.5, intercept=True, dispersion_prior=_NO_PRIOR):
-        if family not in GLM_FAMILIES:
-            raise ValueError(f"GLMTarget: family must be one of {GLM_FAMILIES}, not {family!r}")
-        disp = family in GLM_DISPERSION
-        if not disp and dispersion_prior is not _NO_PRIOR:
-            raise ValueError(f"GLMTarget: {family} has no dispersion parameter; dispersion_prior is for "
-                             f"{tuple(GLM_DISPERSION)}")
-        if disp:
-            m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
-            try:
-                m_tau, s_tau = (float(v) for v in m_s)
-            except (TypeError, ValueError):
-                raise ValueError("GLMTarget: dispersion_prior must be a pair (m, s)") from None
-            if not math.isfinite(m_tau):
-                raise ValueError("GLMTarget: dispersion_prior's m must be finite")
-            if not (math.isfinite(s_tau) and s_tau > 0.0):
-                raise ValueError("GLMTarget: dispersion_prior's s must be finite and > 0")
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X.reshape(-1, 1)
-        if X.ndim != 2:
-            raise ValueError("GLMTarget: X must be an (n, p) matrix")
-        n, p = X.shape
-        y = np.asarray(y, dtype=np.float64)
-        if y.ndim != 1 or y.shape[0] != n:
-            raise ValueError(f"GLMTarget: y must be a vector of the n = {n} observations X has rows for")
-        if n < 1:
-            raise ValueError("GLMTarget: at least one observation")
-        ic = 1 if intercept else 0
-        Dc = p + ic
-        D = Dc + (1 if disp else 0)
-        if Dc < 1:
-            raise ValueError("GLMTarget: no coefficients (p = 0 without an intercept)")
-        if D > GLM_MAX_DIM:
-            what = f"D = {D} coefficients" if not disp else f"D = {D} coordinates ({Dc} coefficients and tau)"
-            raise ValueError(f"GLMTarget: {what}; the device functor covers D <= {GLM_MAX_DIM}. "
-                             "Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
-        if not np.all(np.isfinite(X)):
-            raise ValueError("GLMTarget: X must be finite")
-        if family == "bernoulli_logit":
-            if not np.all((y == 0.0) | (y == 1.0)):
-                raise ValueError("GLMTarget: bernoulli_logit needs y in {0, 1}")
-        elif family == "poisson_log":
-            if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
-                raise ValueError("GLMTarget: poisson_log needs y in {0, 1, 2, ...}")
-        elif family == "normal":
-            if not np.all(np.isfinite(y)):
-                raise ValueError("GLMTarget: normal needs finite y")
-        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
-            raise ValueError("GLMTarget: neg_binomial_2_log needs y in {0, 1, 2, ..., 2^53}")
-        s = np.asarray(prior_sd, dtype=np.float64)
-        if s.ndim == 0:
-            s = np.full(Dc, float(s))
-        if s.shape != (Dc,):
-            raise ValueError(f"GLMTarget: prior_sd must be a scalar or one value per coefficient ({Dc})"
-                             if disp else f"GLMTarget: prior_sd must be a scalar or one value per coefficient (D = {D})")
-        if not np.all(np.isfinite(s) & (s > 0.0)):
-            raise ValueError("GLMTarget: prior_sd must be finite and > 0")
-        self.family, self.intercept = family, bool(intercept)
-        self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
-        self.dispersion_prior = (m_tau, s_tau) if disp else None
-        head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic)]
-        data = np.concatenate([head, s, [m_tau, s_tau] if disp else [], y, X.reshape(-1)])
-        names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)]
-        if disp:
-            names.append(GLM_DISPERSION[family])
-        super().__init__(data, D, names)
+        def limit(what, D):
+            if D > GLM_MAX_DIM:
+                raise ValueError(f"GLMTarget: {what}; the device functor covers D <= {GLM_MAX_DIM}. "
+                                 f"WideGLMTarget covers the same model for {GLM_MAX_DIM} < D <= {WGLM_MAX_DIM}; beyond that, "
+                                 "wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
+        _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior)
 
     _PW_CHUNK = 1 << 25          # doubles of ll the device holds at once (256 MB)
 
@@ -385,6 +395,28 @@ class GLMTarget(PredictMixin, DeviceTarget):
         from ..psis import loo_from_context
         x2 = self._points(x)
         return loo_from_context(self._context(x2.shape[0]), None, x2, logw)
+
+
+class WideGLMTarget(DeviceTarget):
+    """GLMTarget's model -- the same four families, priors, arguments, coordinates and constrained space -- for
+    64 < D <= 256 coordinates (D = p + intercept, + 1 for tau in the dispersion families): dummy-coded factors,
+    interactions, spline bases.  The device functor holds up to four coordinates per lane of one wavefront
+    (smcn_models.hpp: GlmWideModel).  D <= 64 is GLMTarget's; D > 256 runs host-evaluated (HostTarget).  Sampling with the
+    forward and the asymptotic L-kernel, tempering, shards, moments and summary(); the pointwise criteria, LOO, prediction
+    and GaussianApproxLKernel are not implemented for wide rows.
+
+    Data block (include/smcnuts_hip.h, SMCN_MODEL_WGLM): SMCN_MODEL_GLM's, word for word."""
+    model_id = _capi.MODEL_WGLM
+
+    def __init__(self, X, y, family="bernoulli_logit", prior_sd=2.5, intercept=True, dispersion_prior=_NO_PRIOR):
+        def limit(what, D):
+            if D <= GLM_MAX_DIM:
+                raise ValueError(f"WideGLMTarget: {what}; the wide functor covers {GLM_MAX_DIM} < D <= {WGLM_MAX_DIM}. "
+                                 f"D <= {GLM_MAX_DIM} is GLMTarget's.")
+            if D > WGLM_MAX_DIM:
+                raise ValueError(f"WideGLMTarget: {what}; the device functor covers D <= {WGLM_MAX_DIM}. "
+                                 "Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
+        _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior)
 
 
 class HierarchicalGLM(PredictMixin, DeviceTarget):

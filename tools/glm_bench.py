@@ -2,7 +2,7 @@
 OrdinalRegression; MultilevelGLM, SMCN_MODEL_MLGLM) throughput on one MI355X: one JSON line per case.
 
     python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096] [--families normal,neg_binomial_2_log]
-                              [--models glm,hier,cat,ord,multi]
+                              [--models glm,hier,cat,ord,multi,wide] [--wide-cases bernoulli_logit:65,normal:256]
 
 GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
 (1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)}, poisson_log at (1 000, 25), and normal and neg_binomial_2_log
@@ -24,6 +24,14 @@ Multilevel cases (--models multi; MultilevelGLM, not in the default set): (a) th
 Dc = 5, J = 20) expressed as MultilevelGLM with one term and z = 1, against HierarchicalGLM on the same data, step and
 seed in one process, the two alternated five times -- both medians, their min..max and the ratio of the medians; (b)
 normal, n = 1 000, Dc = 3, an intercept and a slope on one factor of 18 levels.  Flop count 4 n (Dc + R) per leapfrog.
+Wide cases (--models wide; WideGLMTarget, SMCN_MODEL_WGLM, not in the default set; run with --N 16384): n = 1 000,
+bernoulli_logit at D = 65, 128, 129, 256 and normal at D = 128, 256 (--wide-cases: a subset, so that a caller can give
+every case a process and a time limit of its own).  The step is the ladder's (pilot launch >= 8 leapfrogs per tree at
+generation 0; the trees grow as the particles spread: 15 to 60 leapfrogs per tree over the run, `nleap_in_15_60`).  Per case the figures above and `fma_per_s` = 2 n DP leapfrog/s, DP = the row's padded
+column count: the evaluation's multiply-adds (eta and the column sums) per second.  With the bernoulli_logit D = 65 case,
+in the same process: GLMTarget at D = 64 on the first 63 columns of the same data (`wide_ref_glm_D64`: the per-FMA
+efficiency of the one-coordinate-per-lane functor), and the D = 65 model at --host-N particles both device-native and
+through HostTarget with the numpy density (`.._vs_host`: what a user had before).
 """
 import argparse
 import json
@@ -55,6 +63,10 @@ CAT_HOST_CASES = ((5, 1000, 6),)
 ORD_CASES = [(5, 100, 3), (5, 1000, 20), (10, 1000, 40)]
 ORD_HOST_CASES = ((5, 1000, 20),)
 MULTI_REPEATS = 5
+# wide: (family, D), n = 1 000; D counts tau
+WIDE_CASES = [("bernoulli_logit", 65), ("bernoulli_logit", 128), ("bernoulli_logit", 129), ("bernoulli_logit", 256),
+              ("normal", 128), ("normal", 256)]
+WIDE_N_OBS = 1000
 
 
 def pick_step(target, N, seed):
@@ -97,7 +109,8 @@ def main():
     ap.add_argument("--families", default=None, help="comma-separated subset of the families (default: all)")
     ap.add_argument("--models", default="glm,hier,cat,ord",
                     help="comma-separated: glm (GLMTarget cases), hier (HierarchicalGLM cases), cat (CategoricalRegression), "
-                         "ord (OrdinalRegression); multi (MultilevelGLM, not in the default set)")
+                         "ord (OrdinalRegression); multi (MultilevelGLM) and wide (WideGLMTarget), not in the default set")
+    ap.add_argument("--wide-cases", default=None, help="comma-separated family:D subset of the wide cases (default: all)")
     a = ap.parse_args()
     models = set(a.models.split(","))
     import _glm
@@ -137,6 +150,8 @@ def main():
         ordinal(a)
     if "multi" in models:
         multi(a)
+    if "wide" in models:
+        wide(a)
 
 
 def hier(a, fams):
@@ -255,6 +270,52 @@ def multi(a):
              step_size=eps, pilot_nleap=pilot, fp64_tflops=4.0 * n * (Dc + 2) * r["leapfrog_per_s"] / 1e12)
     r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
     print(json.dumps(r), flush=True)
+
+
+def wide(a):
+    import _glm
+    import _glm_disp
+    from smcnuts_amd import GLMTarget, WideGLMTarget
+    n = WIDE_N_OBS
+    want = None if a.wide_cases is None else {tuple(c.split(":")) for c in a.wide_cases.split(",")}
+    for family, D in WIDE_CASES:
+        if want is not None and (family, str(D)) not in want:
+            continue
+        disp = family in _glm_disp.DISP_FAMILIES
+        Dc = D - (1 if disp else 0)
+        if disp:
+            X, y = _glm_disp.synthetic(family, n, Dc - 1, 5000 + D, scale=0.5)
+            t = WideGLMTarget(X, y, family=family, prior_sd=2.0, dispersion_prior=(0.0, 2.5))
+        else:
+            X, y = _glm.synthetic(family, n, Dc - 1, 5000 + D, scale=0.5)
+            t = WideGLMTarget(X, y, family=family, prior_sd=2.0)
+        DP = (Dc + 1) // 2 * 2
+
+        def line(name, target, dp, dim, **more):
+            eps, pilot = pick_step(target, a.N, 5)
+            run(target, a.N, 2, eps, 6)                          # warm-up: code objects, allocations
+            r = run(target, a.N, a.K, eps, 7)
+            r.update(case=name, family=family, n=n, D=dim, DP=dp, N=a.N, K=a.K, step_size=eps, pilot_nleap=pilot,
+                     nleap_in_15_60=bool(15.0 <= r["nleap_mean"] <= 60.0), fma_per_s=2.0 * n * dp * r["leapfrog_per_s"],
+                     fp64_tflops=4.0 * n * dp * r["leapfrog_per_s"] / 1e12, library=os.environ.get("SMCN_LIB", "built"), **more)
+            r["fp64_fraction_of_peak"] = r["fp64_tflops"] * 1e12 / PEAK_FP64
+            print(json.dumps(r), flush=True)
+            return eps, r
+
+        eps, r = line(f"wide_{family}_n{n}_D{D}", t, DP, D)
+        if (family, D) == WIDE_CASES[0]:
+            # the reference lines, in this process: the narrow functor on the first 63 columns, the host-evaluated model
+            g = GLMTarget(X[:, :63], y, family=family, prior_sd=2.0)
+            _, rg = line(f"wide_ref_glm_{family}_n{n}_D64", g, 64, 64)
+            print(json.dumps(dict(case=f"wide_{family}_D{D}_over_glm_D64", leapfrog_rate_ratio=r["leapfrog_per_s"] / rg["leapfrog_per_s"],
+                                  fma_rate_ratio=r["fma_per_s"] / rg["fma_per_s"])), flush=True)
+            dev = run(t, a.host_N, a.host_K, eps, 8)
+            host = run(_glm.GLMNumpy(X, y, family, 2.0), a.host_N, a.host_K, eps, 8)
+            print(json.dumps(dict(case=f"wide_{family}_n{n}_D{D}_vs_host", N=a.host_N, K=a.host_K, step_size=eps,
+                                  device=dev, host=host, same_leapfrogs=dev["leapfrogs"] == host["leapfrogs"],
+                                  wide_full_N_leapfrog_per_s=r["leapfrog_per_s"],
+                                  wide_faster_than_host=bool(r["leapfrog_per_s"] > host["leapfrog_per_s"]),
+                                  speedup=host["run_s"] / dev["run_s"])), flush=True)
 
 
 if __name__ == "__main__":
