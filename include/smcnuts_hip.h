@@ -666,6 +666,32 @@ int smcn_summary_cdf(smcn_ctx* ctx, int T, const double* at /* [Dc][T] */, doubl
 int smcn_summary_last_ms(const smcn_ctx* ctx, double* ms);
 int smcn_summary_pass_ms(const smcn_ctx* ctx, double* ms /* [8] */);
 
+/* ---- posterior covariance: weighted second moments of the constrained coordinates (every model) ----
+ * Definition.  Over the particles with a finite log-weight, w_p = exp(lw_p - mw) (mw: the largest finite log-weight of
+ * ALL shards), W = sum w_p, v_p the constrained vector (Dc values):
+ *   m_i = sum w_p v_ip / W        C_ij = sum w_p (v_ip - m_i)(v_jp - m_j) / W       (weights normalised to one, no
+ * small-sample correction: diag C is the variance estimate).  A particle of weight 0 contributes nothing and its values
+ * are never multiplied; a non-finite value in a particle of positive weight reaches row and column i alone.
+ * The device never forms sum w v v^T - m m^T.  It sums about a centre c near the mean,
+ *   G_ij = sum w_p (v_ip - c_i)(v_jp - c_j),   S1_i = sum w_p (v_ip - c_i),   W,
+ * as one symmetric product of the population with one constant coordinate "1" appended (fp64 MFMA, smcn_cov.hpp), and
+ * the caller finishes: d = S1 / W, C = G / W - d d^T, m = c + d.  Partials of disjoint sets of particles with the same
+ * centre and the same mw add.
+ *
+ * smcn_cov_partials runs on the population staged by the last smcn_summary_begin (resident, x, or v).  lw_max: mw.
+ * centre [Dc], or NULL: the shard's own weighted mean (0 where the shard has no weight).  slices: particle slices of the
+ * launch, 0 for the rule's own count (a function of M and Dc alone; smcn_cov_dims) or 1 .. the cap -- the slices'
+ * partials stay below 64 MiB and 1024 slices.  A result depends on (population, lw_max, centre, slices) alone: slices
+ * are merged per entry in slice order, 16 at a time and then the groups, with no atomics.  out [Dc+1][Dc+1]: the
+ * symmetric augmented matrix [[G, S1], [S1^T, W]], un-normalised; NULL: only the centre is formed.  centre_out [Dc]
+ * (or NULL): the centre used.  Dc <= 1023.
+ * smcn_cov_dims: out[4] = {M, Dc, the rule's slices, the cap} of the staged population (the last two 0 for Dc > 1023).
+ * smcn_cov_last_ms: device time of the last smcn_cov_partials' kernels (HIP events on the context's stream). */
+int smcn_cov_partials(smcn_ctx* ctx, double lw_max, const double* centre_or_null /* [Dc] */, int64_t slices,
+                      double* out /* [Dc+1][Dc+1] */, double* centre_out /* [Dc] */);
+int smcn_cov_dims(const smcn_ctx* ctx, int64_t* out /* [4] */);
+int smcn_cov_last_ms(const smcn_ctx* ctx, double* ms);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build. */

@@ -159,6 +159,9 @@ SIGNATURES = {
     "smcn_summary_cdf": ([_ctx, C.c_int, _dp, _dp], C.c_int),
     "smcn_summary_last_ms": ([_ctx, _dp], C.c_int),
     "smcn_summary_pass_ms": ([_ctx, _dp], C.c_int),
+    "smcn_cov_partials": ([_ctx, C.c_double, _dp, C.c_int64, _dp, _dp], C.c_int),
+    "smcn_cov_dims": ([_ctx, C.POINTER(C.c_int64)], C.c_int),
+    "smcn_cov_last_ms": ([_ctx, _dp], C.c_int),
 }
 
 _lib = None
@@ -603,6 +606,37 @@ class Context:
         if self._lib.smcn_summary_pass_ms(self._h, dptr(ms)) != 0:
             raise SmcnError("smcn_summary_pass_ms failed")
         return ms
+
+    # ---- posterior covariance (every model; the population staged by summary_begin) -----
+    def cov_dims(self):
+        """(M, Dc, the slice rule's count, the most slices a call may ask for) of the staged population."""
+        out = (C.c_int64 * 4)()
+        if self._lib.smcn_cov_dims(self._h, out) != 0:
+            raise SmcnError("smcn_cov_dims: call summary_begin first")
+        return tuple(int(v) for v in out)
+
+    def cov_partials(self, lw_max, Dc, centre=None, slices=0):
+        """(augmented sums [Dc+1][Dc+1] = [[G, S1], [S1', W]] about the centre, the centre [Dc] the device used) of the
+        staged population against the log-weight maximum lw_max of all shards (include/smcnuts_hip.h)."""
+        out, cen = np.empty((Dc + 1, Dc + 1)), np.empty(Dc)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float64)
+        if c is not None and c.shape != (Dc,):
+            raise ValueError(f"centre must hold {Dc} values")
+        self.call("smcn_cov_partials", float(lw_max), dptr(c), int(slices), dptr(out), dptr(cen))
+        return out, cen
+
+    def cov_centre(self, lw_max, Dc):
+        """The staged shard's own weighted mean [Dc] (zeros where it has no weight): the centre kernel alone."""
+        cen = np.empty(Dc)
+        self.call("smcn_cov_partials", float(lw_max), None, 0, None, dptr(cen))
+        return cen
+
+    def cov_last_ms(self):
+        """Device time of the last cov_partials' kernels (HIP events on the context's stream)."""
+        ms = C.c_double(0.0)
+        if self._lib.smcn_cov_last_ms(self._h, C.byref(ms)) != 0:
+            raise SmcnError("smcn_cov_last_ms failed")
+        return ms.value
 
     def timers(self, reset=False):
         t = np.zeros(6)

@@ -33,6 +33,7 @@
 #include "smcn_predict_draws.hpp"
 #include "smcn_quantile.hpp"
 #include "smcn_psis.hpp"
+#include "smcn_cov.hpp"
 
 using namespace smcn;
 
@@ -207,6 +208,11 @@ struct smcn_ctx {
     std::vector<unsigned long long> sm_pfx_h, sm_thr_h;
     hipEvent_t sm_ev[10] = {};
     double sm_ms = 0.0, sm_pass_ms[8] = {};
+    // posterior covariance (smcn_cov_*): weights, centre, slice and group partials, result
+    double* cov_buf = nullptr;
+    int64_t cov_len = 0;
+    hipEvent_t cov_ev[2] = {};
+    double cov_ms = 0.0;
 };
 
 #define CHECK_CTX(c)             \
@@ -527,7 +533,7 @@ static void free_all(smcn_ctx* c) {
                     c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
                     c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
                     c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->ps_buf, c->pr_md, c->dr_buf, c->sm_buf, c->sm_hist};
+                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->ps_buf, c->pr_md, c->dr_buf, c->sm_buf, c->sm_hist, c->cov_buf};
     if (c->rows_h) (void)hipHostFree(c->rows_h);
     if (c->hist_h) (void)hipHostFree(c->hist_h);
     if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
@@ -536,6 +542,8 @@ static void free_all(smcn_ctx* c) {
     for (hipEvent_t e : c->ps_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->sm_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->cov_ev)
         if (e) (void)hipEventDestroy(e);
     // ONE wait for everything this context has in flight (its own stream, the history stream); the buffers below were
     // used by these streams only
@@ -3730,6 +3738,82 @@ int smcn_summary_last_ms(const smcn_ctx* c, double* ms) {
 int smcn_summary_pass_ms(const smcn_ctx* c, double* ms) {
     if (!c || !ms) return -1;
     for (int i = 0; i < 8; ++i) ms[i] = c->sm_pass_ms[i];
+    return 0;
+}
+
+// ---- posterior covariance (smcn_cov.hpp) ---------------------------------------------------------------------------------
+int smcn_cov_dims(const smcn_ctx* c, int64_t* out) {
+    if (!c || !out) return -1;
+    if (c->sm_stage_state < 1) return -3;
+    out[0] = c->sm_M;
+    out[1] = c->sm_Dc;
+    out[2] = c->sm_Dc <= kCovMaxDc ? cov_slices(c->sm_M, c->sm_Dc) : 0;
+    out[3] = c->sm_Dc <= kCovMaxDc ? cov_slice_cap(c->sm_Dc) : 0;
+    return 0;
+}
+
+int smcn_cov_partials(smcn_ctx* c, double lw_max, const double* centre, int64_t slices, double* out, double* centre_out) {
+    CHECK_CTX(c);
+    if (c->sm_stage_state < 1) FAIL(c, "smcn_cov_partials: call smcn_summary_begin first");
+    if (!out && !centre_out) FAIL(c, "smcn_cov_partials: bad arguments");
+    if (!std::isfinite(lw_max)) FAIL(c, "smcn_cov_partials: lw_max must be finite (no particle with positive weight?)");
+    const int Dc = c->sm_Dc;
+    const int64_t M = c->sm_M;
+    if (Dc > kCovMaxDc)
+        FAIL(c, "smcn_cov_partials: at most 1023 constrained coordinates, not " + std::to_string(Dc));
+    const int64_t cap = cov_slice_cap(Dc);
+    if (slices < 0 || slices > cap)
+        FAIL(c, "smcn_cov_partials: slices must be 0 (the rule's own count) or 1 .. " + std::to_string(cap) +
+                    " for " + std::to_string(Dc) + " coordinates");
+    if (slices == 0) slices = cov_slices(M, Dc);
+    const int T = cov_tiles(Dc), Da = Dc + 1, NB = (T + kCovBlock - 1) / kCovBlock;
+    const int64_t entries = cov_tile_pairs(Dc) * 256, groups = (slices + kCovGroup - 1) / kCovGroup;
+    const int64_t chunks = (M + 15) / 16, cps = (chunks + slices - 1) / slices;
+    // cov_buf: [w M | centre 16 T | slice partials | group partials | result Da Da | the centre's chunk sums 2 Dc nch]
+    const int64_t nch = (M + kCovCentreChunk - 1) / kCovCentreChunk;
+    const int64_t o_c = (M + 15) / 16 * 16, o_part = o_c + 16 * T, o_grp = o_part + slices * entries;
+    const int64_t o_out = o_grp + groups * entries, o_cp = o_out + (int64_t)Da * Da, words = o_cp + 2 * Dc * nch;
+    if (words > c->cov_len) {
+        if (c->cov_buf) (void)cached_free(c->cov_buf);
+        c->cov_buf = nullptr;
+        c->cov_len = 0;
+        HIPC(c, dalloc(&c->cov_buf, words));
+        c->cov_len = words;
+    }
+    for (hipEvent_t& e : c->cov_ev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    const SmLayout L = sm_layout(c);
+    double *const w = c->cov_buf, *const cen = c->cov_buf + o_c, *const part = c->cov_buf + o_part;
+    double *const grp = c->cov_buf + o_grp, *const res = c->cov_buf + o_out;
+    if (centre) HIPC(c, hipMemcpyAsync(cen, centre, sizeof(double) * Dc, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipEventRecord(c->cov_ev[0], c->stream));
+    cov_weight_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(L.lw, M, lw_max, w);
+    if (!centre) {
+        double* const cp = c->cov_buf + o_cp;
+        cov_centre_partial_kernel<<<dim3((unsigned)nch, (unsigned)Dc), kRedBlock, 0, c->stream>>>(L.vals, w, M, nch, cp);
+        cov_centre_final_kernel<<<Dc, kRedBlock, 0, c->stream>>>(cp, nch, cen);
+    }
+    if (out) {
+        cov_partials_kernel<kCovBlock><<<dim3((unsigned)(NB * (NB + 1) / 2), (unsigned)slices), 64, 0, c->stream>>>(
+            L.vals, w, cen, M, Dc, T, NB, cps, part);
+        cov_combine_kernel<false><<<dim3((unsigned)grid_for(entries, 256), (unsigned)groups), 256, 0, c->stream>>>(
+            part, slices, entries, T, Da, grp);
+        cov_combine_kernel<true><<<grid_for(entries, 256), 256, 0, c->stream>>>(grp, groups, entries, T, Da, res);
+    }
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(c->cov_ev[1], c->stream));
+    if (out) HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * Da * Da, hipMemcpyDeviceToHost, c->stream));
+    if (centre_out) HIPC(c, hipMemcpyAsync(centre_out, cen, sizeof(double) * Dc, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    float ms = 0.f;
+    HIPC(c, hipEventElapsedTime(&ms, c->cov_ev[0], c->cov_ev[1]));
+    c->cov_ms = (double)ms;
+    return 0;
+}
+
+int smcn_cov_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    *ms = c->cov_ms;
     return 0;
 }
 

@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from .. import _capi
+from .. import covariance as _covariance
 from .. import summary as _summary
 from ..predict import PredictMixin
 
@@ -96,6 +97,16 @@ class DeviceTarget:
         lw = _summary.check_logw(logw, x2.shape[0])
         probs, at = _summary.check_probs(probs), _summary.check_at(at, self.constrained_dim)
         return _summary.target_summary(self, self._context(x2.shape[0]), np.ascontiguousarray(x2), lw, probs, at)
+
+    def covariance(self, x, logw=None):
+        """covariance.PosteriorCovariance of the points x [M][D] (unconstrained) with log-weights logw (None: equal):
+        weighted mean, covariance and correlation of the constrained coordinates -- constrained and summed on the device
+        (one fp64 MFMA product) about the points' own weighted mean."""
+        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
+        if x2.ndim != 2 or x2.shape[1] != self.dim:
+            raise ValueError(f"{type(self).__name__}: x must be [{self.dim}] or [M, {self.dim}]")
+        lw = _summary.check_logw(logw, x2.shape[0])
+        return _covariance.target_covariance(self, self._context(x2.shape[0]), np.ascontiguousarray(x2), lw)
 
 
 class GaussianTarget(DeviceTarget):
@@ -180,6 +191,20 @@ class HostTarget:
         if ctx is None:
             ctx = self._sum_ctx = _capi.Context(256, self.model_id, self.model_data, device=self.device)
         return _summary.target_summary(self, ctx, x2, lw, probs, at, v=v)
+
+    def covariance(self, x, logw=None):
+        """DeviceTarget.covariance with the wrapped model's own constrain() on the host and the sums on the device."""
+        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
+        if x2.ndim != 2 or x2.shape[1] != self.dim:
+            raise ValueError(f"HostTarget: x must be [{self.dim}] or [M, {self.dim}]")
+        lw = _summary.check_logw(logw, x2.shape[0])
+        v = np.ascontiguousarray(np.atleast_2d(self.constrain(x2)), dtype=np.float64)
+        if v.shape != (x2.shape[0], self.constrained_dim):
+            raise ValueError(f"HostTarget: constrain() returned shape {v.shape}, not {(x2.shape[0], self.constrained_dim)}")
+        ctx = getattr(self, "_sum_ctx", None)
+        if ctx is None:
+            ctx = self._sum_ctx = _capi.Context(256, self.model_id, self.model_data, device=self.device)
+        return _covariance.target_covariance(self, ctx, x2, lw, v=v)
 
     def attach(self, ctx):
         """Register the density callback with a context created for this target."""
@@ -402,8 +427,8 @@ class WideGLMTarget(DeviceTarget):
     64 < D <= 256 coordinates (D = p + intercept, + 1 for tau in the dispersion families): dummy-coded factors,
     interactions, spline bases.  The device functor holds up to four coordinates per lane of one wavefront
     (smcn_models.hpp: GlmWideModel).  D <= 64 is GLMTarget's; D > 256 runs host-evaluated (HostTarget).  Sampling with the
-    forward and the asymptotic L-kernel, tempering, shards, moments and summary(); the pointwise criteria, LOO, prediction
-    and GaussianApproxLKernel are not implemented for wide rows.
+    forward and the asymptotic L-kernel, tempering, shards, moments, summary() and covariance(); the pointwise criteria,
+    LOO, prediction and GaussianApproxLKernel are not implemented for wide rows.
 
     Data block (include/smcnuts_hip.h, SMCN_MODEL_WGLM): SMCN_MODEL_GLM's, word for word."""
     model_id = _capi.MODEL_WGLM

@@ -579,6 +579,37 @@ class SMCSampler:
         return sm.PosteriorSummary(names, self.mean_estimate[self.K].copy(), np.sqrt(self.variance_estimate[self.K]),
                                    probs, q, cdf, at, self.ess[self.K], self.N)
 
+    def covariance(self):
+        """Posterior covariance and correlation (covariance.PosteriorCovariance: mean, cov, corr, sd, contrast(),
+        pairs()) of the constrained parameters of the final generation and its weights, after sample() / finalise():
+        one symmetric matrix product over the resident particles on the device (fp64 MFMA) about the centre
+        mean_estimate[K]; nothing is downloaded but the [Dc+1][Dc+1] sums.  Several shards: one host all-gather of the
+        weights' headers and one of the partials; every rank returns the same object.  A host-evaluated target's own
+        constrain() runs on the host (as for the moments)."""
+        from . import covariance as cv
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError("covariance(): the asymptotic L-kernel's estimates pool generations; covariances over "
+                                      "the pooled generations are not implemented")
+        if not self._finalised:
+            raise RuntimeError("covariance(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"covariance(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do "
+                               "not target the posterior")
+        Dc = self.mean_estimate.shape[1]
+        ctx, t = self.samples.ctx, self.target
+        centre = np.ascontiguousarray(self.mean_estimate[self.K], dtype=np.float64)
+        ctx.call("smcn_synchronize")
+        if getattr(t, "host_evaluated", False) and callable(getattr(t.target, "constrain", None)):
+            x, lw, _ = ctx.get_state()
+            v = np.ascontiguousarray(t.constrain(x), dtype=np.float64)
+            mean, cov, corr, _, _ = cv.device_covariance(ctx, self.comm, centre=centre, v=v, logw=lw)
+        else:
+            mean, cov, corr, _, _ = cv.device_covariance(ctx, self.comm, centre=centre)
+        names = list(t.param_names())
+        if len(names) != Dc:
+            names = [f"x.{i + 1}" for i in range(Dc)]
+        return cv.PosteriorCovariance(names, mean, cov, corr, self.ess[self.K], self.N, centre=centre)
+
     def predict(self, X_new, y_new=None, groups_new=None):
         """Posterior predictive summaries at new rows (predict.Prediction: mean / variance or class probabilities, and with
         y_new the log predictive density of each held-out row) of the final generation and its weights, after sample() /
