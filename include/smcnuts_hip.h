@@ -72,6 +72,17 @@ typedef struct smcn_ctx smcn_ctx;
                               Sampling, moments, summaries and shards as for any device model; the pointwise criteria,
                               PSIS-LOO, prediction and predictive draws keep a row in registers and stay with
                               SMCN_MODEL_GLM; smcn_gauss_lkernel_sums refuses D > 64 as for every model */
+#define SMCN_MODEL_OGLM 10   /* GLM with per-observation offsets and / or weights: SMCN_MODEL_GLM's families 0..3, priors,
+                              coordinates and constrained space (b [, e^tau]), D <= 64, with
+                                eta_i = [b_0 +] X_i b + o_i,   llik = sum_i w_i l(y_i | eta_i [, tau]);
+                              data = [family, n, p, intercept, flags, s_1..s_Dc, (m_tau, s_tau: families 2, 3), y_1..y_n,
+                              o_1..o_n (flags & 1), w_1..w_n (flags & 2), X (n x p, row-major)], flags in {1, 2, 3} (0 is
+                              SMCN_MODEL_GLM's model: refused).  o finite; w finite and >= 0, at least one > 0.  A row with
+                              w_i = 0 adds exactly 0 to llik and to every gradient sum whatever its term is (an overflowing
+                              e^eta_i included), and the families' -inf rules look at the rows with w_i != 0 only.
+                              Pointwise log-likelihoods, prediction and predictive draws as for SMCN_MODEL_GLM (new rows:
+                              [family, m, p, intercept, flags, y, o (flags & 1), w = 1.. (flags & 2), X]); the pointwise
+                              criteria and PSIS-LOO are refused for a fit with weights (flags & 2) */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */
@@ -472,7 +483,9 @@ int smcn_bench_resample(smcn_ctx* ctx, int reps, int64_t iteration, double* ms_t
 /* ---- pointwise log-likelihood and predictive criteria (SMCN_MODEL_GLM, all four families, D <= 64, any n) ----
  * ll[p][i] = log p(y_i | x_p), the per-observation term exactly as the density forms it (sum_i ll[p][i] is the llik of
  * smcn_target_eval; the -lgamma(y + 1) constants included), finite or -inf.  Contexts of every other model fail with a
- * message (smcn_last_error) that says so.
+ * message (smcn_last_error) that says so.  SMCN_MODEL_OGLM with offsets alone (flags = 1) is served as SMCN_MODEL_GLM,
+ * eta_i taking o_i; with weights (flags & 2) these functions and smcn_psis_* fail with a message of their own: the
+ * criteria of a weighted fit are not implemented.
  *
  * smcn_pointwise_dims: n and the column count Q (= 11) of a partials block.
  * smcn_pointwise_loglik: ll as [M][n] row-major for M caller-supplied points x[M][D] (the plain form, for problems small
@@ -547,12 +560,15 @@ int smcn_psis_loo(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const dou
                   double* out /* [n][6] */, double* head_or_null /* [4] */);
 int smcn_psis_last_ms(const smcn_ctx* ctx, double* ms /* [4] */);
 
-/* ---- held-out prediction at new rows (SMCN_MODEL_GLM, SMCN_MODEL_HGLM, SMCN_MODEL_CATEGORICAL, SMCN_MODEL_ORDINAL) ----
+/* ---- held-out prediction at new rows (SMCN_MODEL_GLM, SMCN_MODEL_OGLM, SMCN_MODEL_HGLM, SMCN_MODEL_CATEGORICAL,
+ * SMCN_MODEL_ORDINAL) ----
  * Posterior predictive summaries at rows the model was not fitted to, and log p(y_new_i | x_p) when y_new is given.
- * Contexts of every other model (arma, PRMwCD, Gaussian, host-evaluated) fail with a message that names these four.
+ * Contexts of every other model (arma, PRMwCD, Gaussian, host-evaluated) fail with a message that names these.
  *
  * smcn_predict_set_data: the new rows, as the model's own data block WITHOUT the priors:
  *   SMCN_MODEL_GLM          [family, m, p, intercept, y_1..y_m, X (m x p, row-major)]
+ *   SMCN_MODEL_OGLM         [family, m, p, intercept, flags, y_1..y_m, o_1..o_m (flags & 1), w_1..w_m = 1 (flags & 2), X]
+ *                           (the new rows' own offsets; their weights are not read: a term is log p(y_i | x))
  *   SMCN_MODEL_HGLM         [family, m, p, intercept, J, y_1..y_m, g_1..g_m, X]     (g: existing groups 0..J-1 only)
  *   SMCN_MODEL_CATEGORICAL  [K, m, p, intercept, y_1..y_m, X]
  *   SMCN_MODEL_ORDINAL      [K, m, p, y_1..y_m, X]

@@ -28,6 +28,7 @@
 #include "smcn_glk.hpp"
 #include "smcn_step.hpp"
 #include "smcn_comm.hpp"
+#include "smcn_glm_offset.hpp"
 #include "smcn_pointwise.hpp"
 #include "smcn_predict.hpp"
 #include "smcn_predict_draws.hpp"
@@ -474,6 +475,15 @@ static int with_model(smcn_ctx* c, F&& f) {
         if (c->D <= 16) return f(GlmModel<8, 2>{});
         return f(GlmModel<64, 1>{});
     }
+    if (c->model == SMCN_MODEL_OGLM) {
+        // (checked at creation: D <= 64; the shapes from the resource report, DESIGN.md 4.4, Offsets and weights)
+        if (c->reg.disp()) {
+            if (c->D <= kOglmDispG8) return f(GlmOffDispModel<8, 1>{});
+            return f(GlmOffDispModel<64, 1>{});
+        }
+        if (c->D <= kOglmG8) return f(GlmOffModel<8, kOglmG8 / 8>{});
+        return f(GlmOffModel<64, 1>{});
+    }
     // (smcn_ctx_create has checked the data and refused D > 64)
     if (c->model == SMCN_MODEL_HGLM) return f(GlmHierModel<64, 1>{});
     if (c->model == SMCN_MODEL_MLGLM) return f(GlmMultiModel<64, 1>{});
@@ -601,7 +611,8 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
         case SMCN_MODEL_CATEGORICAL:
         case SMCN_MODEL_ORDINAL:
         case SMCN_MODEL_MLGLM:
-        case SMCN_MODEL_WGLM: {
+        case SMCN_MODEL_WGLM:
+        case SMCN_MODEL_OGLM: {
             const std::string why = reg_check(model_id, model_data, model_data_len, &c->reg);
             if (!why.empty()) {
                 g_create_error = "smcn_ctx_create: " + why;
@@ -619,7 +630,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     c->Dc = c->D;
     // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
     // constrain_coord applies to arma's log sigma (the other models keep their own id)
-    c->cmodel = ((model_id == SMCN_MODEL_GLM || model_id == SMCN_MODEL_WGLM) && c->reg.disp()) ? SMCN_MODEL_ARMA : model_id;
+    c->cmodel = ((model_id == SMCN_MODEL_GLM || model_id == SMCN_MODEL_WGLM || model_id == SMCN_MODEL_OGLM) && c->reg.disp()) ? SMCN_MODEL_ARMA : model_id;
     // hierarchical and multilevel GLM, ordinal: the constrained space is not coordinate-wise; the moment kernels read a constrained copy
     // of the population (model_constrained) with the identity
     if (model_id == SMCN_MODEL_HGLM || model_id == SMCN_MODEL_ORDINAL || model_id == SMCN_MODEL_MLGLM)
@@ -3124,6 +3135,14 @@ static const char* kPwScope =
     "pointwise criteria cover the SMCN_MODEL_GLM families (bernoulli_logit, poisson_log, normal, neg_binomial_2_log) "
     "only; hierarchical, categorical, ordinal, arma, PRMwCD, Gaussian and host-evaluated targets are not implemented";
 
+static const char* kPwWeighted =
+    "pointwise criteria and LOO of a fit with weights (SMCN_MODEL_OGLM, flags & 2) are not implemented: what a weighted "
+    "row's leave-one-out term and the standard error of the sum should be is not settled here";
+// "" or why the pointwise entry points do not serve this context
+static std::string pw_refusal(const smcn_ctx* c) {
+    if (c->model == SMCN_MODEL_OGLM) return (c->reg.flags & 2) ? kPwWeighted : "";
+    return c->model == SMCN_MODEL_GLM ? "" : kPwScope;
+}
 // the GLM walk's arguments over the image `md` of the block L describes (the training data, or the new rows)
 static PwArgs pw_args(const RegLayout& L, const double* md, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
     PwArgs a;
@@ -3152,6 +3171,13 @@ static void row_cap(int Dc, F&& f) {
 template <class F>
 static void row_cap_disp(int Dc, int fam, F&& f) {
     row_cap(Dc, [&](auto dp) { fam >= 2 ? f(dp, std::true_type{}) : f(dp, std::false_type{}); });
+}
+// f(row capacity, dispersion family, offset table): the GLM walk's instantiation for the block L describes
+template <class F>
+static void row_cap_glm(const RegLayout& L, F&& f) {
+    row_cap_disp(L.Dc, L.fam, [&](auto dp, auto disp) {
+        L.model == SMCN_MODEL_OGLM ? f(dp, disp, std::true_type{}) : f(dp, disp, std::false_type{});
+    });
 }
 // categorical: f(row capacity, non-reference classes), the pairs that cover (K - 1) Dc <= 64
 template <class F>
@@ -3189,7 +3215,7 @@ extern "C" {
 int smcn_pointwise_dims(const smcn_ctx* cc, int64_t* n_obs, int* n_cols) {
     smcn_ctx* c = const_cast<smcn_ctx*>(cc);
     if (!c) return -1;
-    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_dims: ") + kPwScope);
+    if (!pw_refusal(c).empty()) FAIL(c, "smcn_pointwise_dims: " + pw_refusal(c));
     if (n_obs) *n_obs = c->reg.n;
     if (n_cols) *n_cols = kPwCols;
     return 0;
@@ -3197,7 +3223,7 @@ int smcn_pointwise_dims(const smcn_ctx* cc, int64_t* n_obs, int* n_cols) {
 
 int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
     CHECK_CTX(c);
-    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_loglik: ") + kPwScope);
+    if (!pw_refusal(c).empty()) FAIL(c, "smcn_pointwise_loglik: " + pw_refusal(c));
     if (!x || !out || M < 1) FAIL(c, "smcn_pointwise_loglik: bad arguments");
     const int64_t n = c->reg.n, tiles = (n + 63) / 64;
     int64_t cps = 1;
@@ -3208,8 +3234,8 @@ int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) 
     if ((rc = pw_ensure(c, M * n))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
     const PwArgs a = pw_args(c->reg, c->mdata, c->stage, c->D, 1, M, cps);
-    row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
-        pointwise_loglik_kernel<decltype(dp)::value, decltype(disp)::value>
+    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
+        pointwise_loglik_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
             <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, c->pw_buf);
     });
     HIPC(c, hipGetLastError());
@@ -3220,7 +3246,7 @@ int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) 
 
 int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
     CHECK_CTX(c);
-    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string("smcn_pointwise_partials: ") + kPwScope);
+    if (!pw_refusal(c).empty()) FAIL(c, "smcn_pointwise_partials: " + pw_refusal(c));
     if (!out || M < 1) FAIL(c, "smcn_pointwise_partials: bad arguments");
     if (!x && (M != c->N || logw)) FAIL(c, "smcn_pointwise_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
     const int64_t n = c->reg.n, tiles = (n + 63) / 64, npad = tiles * 64;
@@ -3247,8 +3273,8 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
     const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, cps);
     HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
     pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
-    row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
-        pointwise_stats_kernel<decltype(dp)::value, decltype(disp)::value>
+    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
+        pointwise_stats_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
             <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, lw, head, part);
     });
     // (groups <= 256 blocks in y: pointwise_slices keeps the slices near 4096)
@@ -3283,7 +3309,7 @@ constexpr int64_t kPsSlab = 1ll << 25;     // doubles of ll staged at once (256 
 }  // namespace
 
 static int ps_layout(smcn_ctx* c, const char* who, int64_t M, int64_t S_bound, PsLayout* L) {
-    if (c->model != SMCN_MODEL_GLM) FAIL(c, std::string(who) + ": " + kPwScope);
+    if (!pw_refusal(c).empty()) FAIL(c, std::string(who) + ": " + pw_refusal(c));
     if (M < 1 || M > 2147483647LL) FAIL(c, std::string(who) + ": bad arguments");
     if (S_bound < 1) FAIL(c, std::string(who) + ": no contributing particle (S < 1)");
     L->stride = psis_tail_len(S_bound) + 1;
@@ -3330,8 +3356,8 @@ static void ps_run_candidates(smcn_ctx* c, const PsLayout& L, const PwArgs& a, c
     double* const B = c->ps_buf;
     for (int64_t t0 = 0; t0 < L.tiles; t0 += L.slab_tiles) {
         const int64_t nt = L.tiles - t0 < L.slab_tiles ? L.tiles - t0 : L.slab_tiles;
-        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
-            psis_stage_kernel<decltype(dp)::value, decltype(disp)::value>
+        row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
+            psis_stage_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
                 <<<(int)(nt * L.slices), 64, 0, c->stream>>>(a, t0, nt, lw, B, L.Mpad, B + L.o_stage);
         });
         psis_select_kernel<<<(int)(nt * 64), kPsBlock, 0, c->stream>>>(B + L.o_stage, L.Mpad, lw, B, L.M, t0 * 64, L.n,
@@ -3340,8 +3366,8 @@ static void ps_run_candidates(smcn_ctx* c, const PsLayout& L, const PwArgs& a, c
 }
 static void ps_run_body(smcn_ctx* c, const PsLayout& L, const PwArgs& a, const double* lw) {
     double* const B = c->ps_buf;
-    row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
-        psis_body_kernel<decltype(dp)::value, decltype(disp)::value>
+    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
+        psis_body_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
             <<<(int)(L.tiles * L.slices), 64, 0, c->stream>>>(a, L.tiles, lw, B, B + L.o_cut, B + L.o_part);
     });
     psis_body_combine_kernel<false><<<dim3((unsigned)grid_for(L.n, 64), (unsigned)L.groups), 64, 0, c->stream>>>(
@@ -3820,11 +3846,11 @@ int smcn_cov_last_ms(const smcn_ctx* c, double* ms) {
 }  // extern "C"
 // ---- held-out prediction at new rows (smcn_predict.hpp) ----------------------------------------------------------------
 static const char* kPrScope =
-    "held-out prediction covers the regression targets (SMCN_MODEL_GLM, SMCN_MODEL_HGLM, SMCN_MODEL_CATEGORICAL, "
-    "SMCN_MODEL_ORDINAL); arma, PRMwCD, Gaussian and host-evaluated targets are not supported";
+    "held-out prediction covers the regression targets (SMCN_MODEL_GLM, SMCN_MODEL_OGLM, SMCN_MODEL_HGLM, "
+    "SMCN_MODEL_CATEGORICAL, SMCN_MODEL_ORDINAL); arma, PRMwCD, Gaussian and host-evaluated targets are not supported";
 static bool pr_model(const smcn_ctx* c) {
-    return c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_CATEGORICAL ||
-           c->model == SMCN_MODEL_ORDINAL;
+    return c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM || c->model == SMCN_MODEL_HGLM ||
+           c->model == SMCN_MODEL_CATEGORICAL || c->model == SMCN_MODEL_ORDINAL;
 }
 static int pr_cols(const smcn_ctx* c) {
     const int K = c->reg.K;
@@ -3872,13 +3898,13 @@ static void pr_launch(smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int6
                       int64_t blocks, const double* lw, const double* head, double* out) {
     const int g = (int)blocks;
     hipStream_t st = c->stream;
-    if (c->model == SMCN_MODEL_GLM) {
+    if (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM) {
         const PwArgs a = pw_args(c->pr, c->pr_md, x, rs, cs, M, cps);
-        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
+        row_cap_glm(c->pr, [&](auto dp, auto disp, auto ow) {
             constexpr int DP = decltype(dp)::value;
-            constexpr bool DI = decltype(disp)::value;
-            if constexpr (STATS) predict_glm_stats_kernel<DP, DI><<<g, 64, 0, st>>>(a, tiles, lw, head, out);
-            else pointwise_loglik_kernel<DP, DI><<<g, 64, 0, st>>>(a, tiles, out);
+            constexpr bool DI = decltype(disp)::value, OW = decltype(ow)::value;
+            if constexpr (STATS) predict_glm_stats_kernel<DP, DI, OW><<<g, 64, 0, st>>>(a, tiles, lw, head, out);
+            else pointwise_loglik_kernel<DP, DI, OW><<<g, 64, 0, st>>>(a, tiles, out);
         });
         return;
     }
@@ -3975,7 +4001,7 @@ int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int6
     PR_CHECK_LDS(c, true, "smcn_predict_partials");
     if (!x && (M != c->N || logw)) FAIL(c, "smcn_predict_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
     const int64_t m = c->pr.n, tiles = (m + 63) / 64, mpad = tiles * 64;
-    const int Q = pr_cols(c), mom = (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_HGLM) ? 1 : 0;
+    const int Q = pr_cols(c), mom = (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM || c->model == SMCN_MODEL_HGLM) ? 1 : 0;
     int64_t cps = 1;
     const int64_t slices = pointwise_slices(M, m, &cps);
     if (tiles * slices > 2147483647LL) FAIL(c, "smcn_predict_partials: too many rows");
@@ -4036,13 +4062,13 @@ static void dr_launch(smcn_ctx* c, const double* xg, int64_t n, const DrawArgs& 
     const auto second = [&](int fam, bool disp, int tau_coord) {
         draws_sample_kernel<<<grid_for(n * m, 256), 256, 0, st>>>(fam, m, n, d, disp ? xg + (int64_t)tau_coord * n : nullptr, out);
     };
-    if (c->model == SMCN_MODEL_GLM) {
+    if (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM) {
         const PwArgs a = pw_args(c->pr, c->pr_md, xg, 1, n, n, cps);
-        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
+        row_cap_glm(c->pr, [&](auto dp, auto disp, auto ow) {
             constexpr int DP = decltype(dp)::value;
             constexpr bool DI = decltype(disp)::value;
             constexpr bool FU = kDrawsFusedGlm<DP, DI>;
-            draws_glm_kernel<DP, DI, FU><<<g, 64, 0, st>>>(a, tiles, d, out);
+            draws_glm_kernel<DP, DI, FU, decltype(ow)::value><<<g, 64, 0, st>>>(a, tiles, d, out);
             if (!FU) second(a.fam, DI, a.Dc);
         });
         return;

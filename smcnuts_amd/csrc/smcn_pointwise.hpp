@@ -1,4 +1,4 @@
-// Pointwise log-likelihood of the SMCN_MODEL_GLM families, ll[p, i] = log p(y_i | x_p), and its weighted reductions
+// Pointwise log-likelihood of the SMCN_MODEL_GLM families (and SMCN_MODEL_OGLM's, eta_i with the row's offset), ll[p, i] = log p(y_i | x_p), and its weighted reductions
 // OVER PARTICLES per observation (lppd, WAIC, importance-sampling LOO, fitted values) without ever forming the matrix.
 //
 // Shape: the transpose of GlmModel<64, 1>.  A LANE owns an observation and keeps its table row in registers (DP <= 16 /
@@ -74,12 +74,15 @@ struct PwArgs {
 // Walks the slice's particles for the tile's 64 observations.  `chunk(lane's particle index, live)` returns the
 // particle's log-weight term (per lane: one particle each); f(t, lwq, wq, term, mean) takes one term of the lane's
 // observation, with t, lwq and wq = exp(lwq) wave-uniform.  Particles for which chunk() returns a non-finite value are passed over.
-template <int DPMAX, bool DISP, class Chunk, class Term>
+// OW: SMCN_MODEL_OGLM's table -- a row carries o_i and w_i behind lgamma(y_i + 1), the table lies at oglm_table_offset, and
+// eta_i takes o_i.  A parameter, off by default, so that the walks of SMCN_MODEL_GLM keep their instruction streams.
+template <int DPMAX, bool DISP, bool OW = false, class Chunk, class Term>
 __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t slice, Chunk&& chunk, Term&& f) {
     using d2 = double __attribute__((ext_vector_type(2)));
     const int lane = (int)(threadIdx.x & 63u);
-    const int Dc = a.Dc, DP = (Dc + 1) & ~1, RS = glm_row_doubles(Dc);
-    const double* const T = a.md + glm_table_offset(DISP ? Dc + 2 : Dc, a.n, a.p);
+    const int Dc = a.Dc, DP = (Dc + 1) & ~1, RS = OW ? oglm_row_doubles(Dc) : glm_row_doubles(Dc);
+    const int npri = DISP ? Dc + 2 : Dc;
+    const double* const T = a.md + (OW ? oglm_table_offset(npri, a.n, a.p) : glm_table_offset(npri, a.n, a.p));
     // the lane's row (rows are padded to a multiple of 64 with zeros: unmasked)
     const d2* const rowp = (const d2*)(T + (tile * 64 + lane) * RS);
     double row[DPMAX];
@@ -91,6 +94,9 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
     }
     const d2 yl = rowp[DP >> 1];
     const double y = yl.x, lgy = yl.y;
+    // (the weight slot is not read: a term is log p(y_i | x); weights belong to the training likelihood's sum)
+    double off = 0.0;
+    if constexpr (OW) off = rowp[(DP >> 1) + 1].x;
     GlmDispModel<64, 1> dm;       // (tau_const() and obs() read `nb` only)
     dm.nb = a.fam == 3;
     const bool poisson = a.fam == 1;
@@ -120,7 +126,8 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
                     e1 = fma(group_read<64>(xc[j + 1], q), row[j + 1], e1);
                 }
             }
-            const double eta = e0 + e1;
+            double eta = e0 + e1;
+            if constexpr (OW) eta += off;
             double term, mean;
             if constexpr (DISP) {
                 typename GlmDispModel<64, 1>::TauConst k;
@@ -145,11 +152,11 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
 }
 
 // ll as [M][n] row-major
-template <int DPMAX, bool DISP>
+template <int DPMAX, bool DISP, bool OW = false>
 __global__ void __launch_bounds__(64) pointwise_loglik_kernel(PwArgs a, int64_t tiles, double* __restrict__ out) {
     const int64_t tile = blockIdx.x % tiles, slice = blockIdx.x / tiles;
     const int64_t i = tile * 64 + (threadIdx.x & 63u);
-    pw_walk<DPMAX, DISP>(
+    pw_walk<DPMAX, DISP, OW>(
         a, tile, slice, [](int64_t, bool) { return 0.0; },
         [&](int64_t t, double, double, double term, double) {
             if (i < a.n) out[t * a.n + i] = term;
@@ -188,7 +195,7 @@ __global__ void __launch_bounds__(kRedBlock) pointwise_header_kernel(const doubl
 }
 
 // the slices' partials of a tile: part[(slice * kPwCols + col) * npad + i]
-template <int DPMAX, bool DISP>
+template <int DPMAX, bool DISP, bool OW = false>
 __global__ void __launch_bounds__(64) pointwise_stats_kernel(PwArgs a, int64_t tiles, const double* __restrict__ lw,
                                                              const double* __restrict__ head, double* __restrict__ part) {
     const int64_t tile = blockIdx.x % tiles, slice = blockIdx.x / tiles;
@@ -196,7 +203,7 @@ __global__ void __launch_bounds__(64) pointwise_stats_kernel(PwArgs a, int64_t t
     const double mw = head[0];
     double ma = -kInf, Sa = 0.0, mb = -kInf, Sb = 0.0, Sb2 = 0.0;
     double c = __builtin_nan(""), SW = 0.0, S1 = 0.0, S2 = 0.0, F = 0.0, ninf = 0.0;
-    pw_walk<DPMAX, DISP>(
+    pw_walk<DPMAX, DISP, OW>(
         a, tile, slice, [&](int64_t t, bool have) { return have ? lw[t] - mw : -kInf; },
         [&](int64_t, double lwq, double wq, double term, double mean) {
             const bool fin = term > -kInf;

@@ -122,7 +122,7 @@ __device__ __forceinline__ void pr_store_glm(double* o, int64_t mpad, const PrLp
 // ---- GLM families: pw_walk on the new rows' table ----------------------------------------------------------------------
 // (a.md is laid out as the context's model data, so pw_walk finds the table where it looks for it; the matrix form is
 // pointwise_loglik_kernel itself)
-template <int DPMAX, bool DISP>
+template <int DPMAX, bool DISP, bool OW = false>
 __global__ void __launch_bounds__(64) predict_glm_stats_kernel(PwArgs a, int64_t tiles, const double* __restrict__ lw,
                                                                const double* __restrict__ head, double* __restrict__ part) {
     const int64_t tile = blockIdx.x % tiles, slice = blockIdx.x / tiles;
@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(64) predict_glm_stats_kernel(PwArgs a, int64_t
     int tbad = 0;
     PrLpd L;
     PrMom Mo;
-    pw_walk<DPMAX, DISP>(
+    pw_walk<DPMAX, DISP, OW>(
         a, tile, slice,
         [&](int64_t t, bool have) {
             if constexpr (DISP) {

@@ -172,14 +172,14 @@ __global__ void draws_gather_kernel(const double* __restrict__ x, int64_t rs, in
 }
 
 // ---- GLM families ----------------------------------------------------------------------------------------------------
-template <int DPMAX, bool DISP, bool FUSED>
+template <int DPMAX, bool DISP, bool FUSED, bool OW = false>
 __global__ void __launch_bounds__(64) draws_glm_kernel(PwArgs a, int64_t tiles, DrawArgs d, double* __restrict__ out) {
     const int64_t tile = blockIdx.x % tiles, slice = blockIdx.x / tiles;
     const int64_t i = tile * 64 + (threadIdx.x & 63u);
     const double nbmax = exp_fast(kLogDblMax);      // what pw_walk's NB2 mean is clamped to: e^eta overflows
     double dv = 1.0;                                // (per lane: one particle of the chunk)
     int bv = 0;
-    pw_walk<DPMAX, DISP>(
+    pw_walk<DPMAX, DISP, OW>(
         a, tile, slice,
         [&](int64_t t, bool have) {
             if constexpr (DISP) dv = draw_disp(a.fam, have ? a.x[t * a.rs + a.Dc * a.cs] : 0.0, bv);

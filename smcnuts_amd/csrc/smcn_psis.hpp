@@ -49,7 +49,7 @@ __device__ __forceinline__ int psis_cap(const double* head, int cap) {
 
 // ll of a slab of `slab_tiles` observation tiles from tile0 on: stage[(local observation) * Mpad + particle].  Particles
 // with a non-finite log-weight are passed over (their slots are never read).
-template <int DPMAX, bool DISP>
+template <int DPMAX, bool DISP, bool OW = false>
 __global__ void __launch_bounds__(64) psis_stage_kernel(PwArgs a, int64_t tile0, int64_t slab_tiles,
                                                         const double* __restrict__ lw,
                                                         const double* __restrict__ head, int64_t Mpad,
@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(64) psis_stage_kernel(PwArgs a, int64_t tile0,
     const int64_t lt = blockIdx.x % slab_tiles, slice = blockIdx.x / slab_tiles;
     const double mw = head[0];
     double* const row = stage + (lt * 64 + (int64_t)(threadIdx.x & 63u)) * Mpad;
-    pw_walk<DPMAX, DISP>(
+    pw_walk<DPMAX, DISP, OW>(
         a, tile0 + lt, slice, [&](int64_t t, bool have) { return have ? lw[t] - mw : -kInf; },
         [&](int64_t t, double, double, double term, double) { row[t] = term; });
 }
@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(kPsBlock) psis_select_kernel(const double* __r
 }
 
 // the slices' body partials of a tile: part[(slice * kPsBodyCols + col) * npad + i]
-template <int DPMAX, bool DISP>
+template <int DPMAX, bool DISP, bool OW = false>
 __global__ void __launch_bounds__(64) psis_body_kernel(PwArgs a, int64_t tiles, const double* __restrict__ lw,
                                                        const double* __restrict__ head,
                                                        const double* __restrict__ cutoff, double* __restrict__ part) {
@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(64) psis_body_kernel(PwArgs a, int64_t tiles, 
     const int64_t i = tile * 64 + (threadIdx.x & 63u), npad = tiles * 64;
     const double cut = i < a.n ? cutoff[i] : -kInf;
     double mb = -kInf, Sb = 0.0, Sb2 = 0.0, Sw = 0.0;
-    pw_walk<DPMAX, DISP>(
+    pw_walk<DPMAX, DISP, OW>(
         a, tile, slice, [&](int64_t t, bool have) { return have ? lw[t] - mw : -kInf; },
         [&](int64_t, double lwq, double wq, double term, double) {
             const bool fin = term > -kInf;

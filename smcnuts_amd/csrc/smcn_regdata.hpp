@@ -1,4 +1,4 @@
-// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL, _MLGLM, _WGLM) on the host: where the
+// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL, _MLGLM, _WGLM, _OGLM) on the host: where the
 // header, the priors, y, g (and z) and X sit in the caller's block, which table the functors read behind it, the check
 // of a caller's block and its repacking.  Plain C++17 with no HIP types: it compiles without a device compiler, so the code that
 // indexes by caller-supplied lengths runs under the host sanitizers (tests/test_regdata_host.py).  The layout helpers
@@ -27,6 +27,13 @@ SMCN_HD inline int64_t glm_table_offset(int64_t D, int64_t n, int64_t p) {
 }
 SMCN_HD inline int glm_row_doubles(int D) { return ((D + 1) & ~1) + 2; }
 SMCN_HD inline int64_t glm_table_rows(int64_t n) { return (n + 63) / 64 * 64; }
+// GLM with offsets / weights (SMCN_MODEL_OGLM): five header slots; the table sits where it would for a block with both o
+// and w, so that its place -- like everything else the functors read -- does not depend on the flags; a row carries o_i
+// and w_i behind lgamma(y_i + 1)
+SMCN_HD inline int64_t oglm_table_offset(int64_t npri, int64_t n, int64_t p) {
+    return (5 + npri + 3 * n + n * p + 15) / 16 * 16;
+}
+SMCN_HD inline int oglm_row_doubles(int Dc) { return ((Dc + 1) & ~1) + 4; }
 // hierarchical GLM: the doubles before y, the table behind y, g and X, its row with the group slot
 SMCN_HD inline int64_t hglm_head(int64_t Dc, bool disp) { return 5 + Dc + 1 + (disp ? 2 : 0); }
 SMCN_HD inline int64_t hglm_table_offset(int64_t head, int64_t n, int64_t p) {
@@ -57,9 +64,11 @@ struct RegLayout {
     int R = 0;                  // multilevel: varying terms, and the levels of each (0 beyond R)
     int64_t Jr[kMlMaxTerms] = {0, 0, 0, 0};
     int ic = 0;                 // intercept flag
+    int flags = 0;              // SMCN_MODEL_OGLM: 1 offsets, 2 weights
     int Dc = 0, D = 0;          // columns of a table row (p for the ordinal model), coordinates
     int64_t nh = 0, npri = 0;   // header doubles, prior doubles
     int64_t y0 = 0, g0 = 0, X0 = 0, len = 0;      // offsets in the block (g0 = 0: no groups; multilevel: g_1), the block's length
+    int64_t o0 = 0, w0 = 0;     // SMCN_MODEL_OGLM: offsets of o and w in the block (0: absent)
     int64_t t0 = 0, rows = 0;   // the table: offset, padded row count,
     int RS = 0, ys = 0;         // row width, y slot (lgamma(y + 1) and g, or the (g_r, z_r) pairs, follow it)
     int64_t c0 = 0;             // ordinal: offset of the class counts (0 otherwise)
@@ -76,6 +85,7 @@ struct Spec {
     const char *who, *layout, *slot0, *too_big, *sds;
     double dmin, dmax;                      // the coordinates the model's functors cover: dmin <= D <= dmax
     const char* too_small;                  // the refusal below dmin (none: dmin = 0)
+    bool has_fl = false;                    // header slot 4 holds the flags (offsets, weights)
 };
 inline const Spec* spec(int model) {
     static const Spec glm = {
@@ -137,7 +147,17 @@ inline const Spec* spec(int model) {
         "wide GLM target: prior sds must be finite and > 0", 65.0, 256.0,
         "wide GLM target: the device functor covers 65 <= D <= 256 coordinates (D counts tau for families 2 and 3); "
         "D <= 64 is SMCN_MODEL_GLM's (GLMTarget)"};
+    static const Spec oglm = {
+        5, true, false, false, true, 0.0, 1048576.0, "offset GLM target: ",
+        "offset GLM target: data = [family, n, p, intercept, flags, s_1..s_D, y_1..y_n, o_1..o_n (flags & 1), "
+        "w_1..w_n (flags & 2), X (n x p, row-major)]",
+        "offset GLM target: family must be 0 (bernoulli_logit) or 1 (poisson_log), or 2 (normal) or 3 (neg_binomial_2_log) "
+        "with a dispersion prior",
+        "offset GLM target: the device functor covers D <= 64 coefficients; larger models run host-evaluated "
+        "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)",
+        "offset GLM target: prior sds must be finite and > 0", 0.0, 64.0, nullptr, true};
     switch (model) {
+        case SMCN_MODEL_OGLM: return &oglm;
         case SMCN_MODEL_GLM: return &glm;
         case SMCN_MODEL_WGLM: return &wglm;
         case SMCN_MODEL_HGLM: return &hglm;
@@ -156,7 +176,8 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     const regdata::Spec* const sp = regdata::spec(model);
     if (!sp) return "not a regression model";
     const auto say = [&](const char* what) { return std::string(sp->who) + what; };
-    const bool glm = model == SMCN_MODEL_GLM || model == SMCN_MODEL_WGLM, hg = model == SMCN_MODEL_HGLM, cat = model == SMCN_MODEL_CATEGORICAL;
+    const bool og = model == SMCN_MODEL_OGLM;
+    const bool glm = model == SMCN_MODEL_GLM || model == SMCN_MODEL_WGLM || og, hg = model == SMCN_MODEL_HGLM, cat = model == SMCN_MODEL_CATEGORICAL;
     const bool ml = model == SMCN_MODEL_MLGLM;
     const bool fams = glm || hg || ml;                 // slot 0 is a family, not a class count
     if (len < sp->nh) return sp->layout;
@@ -166,6 +187,11 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     if (!(icd == 0.0 || icd == 1.0)) return say("intercept must be 0 or 1");
     if (!whole(nd, 1.0, 2147483647.0)) return say("n must be an integer >= 1");
     if (!whole(pd, 0.0, sp->pmax)) return say("p must be an integer >= 0");
+    const double fld = sp->has_fl ? md[4] : 0.0;
+    if (sp->has_fl && fld == 0.0)
+        return say("flags = 0 (neither offsets nor weights) is SMCN_MODEL_GLM's model: pass the block without the flags "
+                   "slot as SMCN_MODEL_GLM");
+    if (sp->has_fl && !whole(fld, 1.0, 3.0)) return say("flags must be 1 (offsets), 2 (weights) or 3 (both)");
     if (sp->has_J && !whole(Jd, 1.0, 1048576.0)) return say("J must be an integer >= 1 (the number of groups)");
     // multilevel: R terms, their level counts in the four slots behind R
     const double Rd = sp->has_R ? md[4] : 0.0;
@@ -211,17 +237,22 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     l.npri = nsd + nn;
     l.y0 = hg ? hglm_head(l.Dc, disp) : l.nh + l.npri;
     l.g0 = hg || ml ? l.y0 + n : 0;
-    l.X0 = l.y0 + (hg ? 2 : 1 + 2 * l.R) * n;
+    l.flags = (int)fld;
+    l.o0 = (l.flags & 1) ? l.y0 + n : 0;
+    l.w0 = (l.flags & 2) ? l.y0 + ((l.flags & 1) ? 2 : 1) * n : 0;
+    l.X0 = l.y0 + (hg ? 2 : 1 + 2 * l.R + (l.o0 ? 1 : 0) + (l.w0 ? 1 : 0)) * n;
     l.len = l.X0 + n * p;
     if (len != l.len) {
         // a block laid out for families 0 / 1 but naming a dispersion family
         if (glm && disp && len == l.len - 2)
             return say("family must be 0 (bernoulli_logit) or 1 (poisson_log) for a block without m_tau, s_tau; "
-                       "families 2 (normal) and 3 (neg_binomial_2_log) take data = [family, n, p, intercept, s_1..s_Dc, "
-                       "m_tau, s_tau, y_1..y_n, X]");
+                       "families 2 (normal) and 3 (neg_binomial_2_log) take data = [family, n, p, intercept, ") +
+                   (og ? "flags, s_1..s_Dc, m_tau, s_tau, y_1..y_n, o, w, X]" : "s_1..s_Dc, m_tau, s_tau, y_1..y_n, X]");
         if (glm && disp)
-            return say("data = [family, n, p, intercept, s_1..s_Dc, m_tau, s_tau, y_1..y_n, "
-                       "X (n x p, row-major)] for families 2 (normal) and 3 (neg_binomial_2_log)");
+            return say("data = [family, n, p, intercept, ") +
+                   (og ? "flags, s_1..s_Dc, m_tau, s_tau, y_1..y_n, o_1..o_n (flags & 1), w_1..w_n (flags & 2), "
+                       : "s_1..s_Dc, m_tau, s_tau, y_1..y_n, ") +
+                   "X (n x p, row-major)] for families 2 (normal) and 3 (neg_binomial_2_log)";
         return sp->layout;
     }
     const auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
@@ -256,14 +287,26 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
         for (int64_t i = 0; i < n; ++i)
             if (!std::isfinite(gr[n + i])) return say("z must be finite");
     }
+    for (int64_t i = 0; l.o0 && i < n; ++i)
+        if (!std::isfinite(md[l.o0 + i])) return say("the offsets o must be finite");
+    if (l.w0) {
+        bool any = false;
+        for (int64_t i = 0; i < n; ++i) {
+            const double w = md[l.w0 + i];
+            if (!(std::isfinite(w) && w >= 0.0)) return say("the weights w must be finite and >= 0");
+            any = any || w > 0.0;
+        }
+        if (!any) return say("at least one weight w must be > 0");
+    }
     for (int64_t t = 0; t < n * p; ++t)
         if (!std::isfinite(md[l.X0 + t])) return say("X must be finite");
     // the table, found as the functors find it (smcn_models.hpp)
-    l.t0 = glm  ? glm_table_offset(l.npri, n, p)
+    l.t0 = og   ? oglm_table_offset(l.npri, n, p)
+           : glm ? glm_table_offset(l.npri, n, p)
            : hg ? hglm_table_offset(l.y0, n, p)
            : ml ? mlglm_table_offset(l.y0, l.R, n, p)
                 : glm_table_offset(l.D, n, p);
-    l.RS = hg ? hglm_row_doubles(l.Dc) : ml ? mlglm_row_doubles(l.Dc, l.R) : glm_row_doubles(l.Dc);
+    l.RS = og ? oglm_row_doubles(l.Dc) : hg ? hglm_row_doubles(l.Dc) : ml ? mlglm_row_doubles(l.Dc, l.R) : glm_row_doubles(l.Dc);
     l.rows = glm_table_rows(n);
     l.ys = (l.Dc + 1) & ~1;
     l.rlen = l.t0 + l.rows * l.RS;
@@ -277,10 +320,11 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
 
 // The image the functors read, from a checked block: `mup` becomes [block | padding | table (| class counts)].  A row is
 // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1) (families; 0 for the normal, whose y may
-// be negative), g_i (hierarchical) or g_1i, z_1i, .., g_Ri, z_Ri (multilevel), 0 ..]; the ordinal model's K class counts n_0..n_{K-1} follow the table.
+// be negative), g_i (hierarchical) or g_1i, z_1i, .., g_Ri, z_Ri (multilevel) or o_i (0 if absent), w_i (1 if absent)
+// (offsets / weights: a padding row is all zero, so its weight is 0), 0 ..]; the ordinal model's K class counts n_0..n_{K-1} follow the table.
 inline void reg_repack(const RegLayout& L, const double* md, std::vector<double>& mup) {
     const bool fams = L.model == SMCN_MODEL_GLM || L.model == SMCN_MODEL_HGLM || L.model == SMCN_MODEL_MLGLM ||
-                      L.model == SMCN_MODEL_WGLM;
+                      L.model == SMCN_MODEL_WGLM || L.model == SMCN_MODEL_OGLM;
     mup.assign(L.rlen, 0.0);
     std::copy(md, md + L.len, mup.begin());
     for (int64_t i = 0; i < L.n; ++i) {
@@ -291,6 +335,10 @@ inline void reg_repack(const RegLayout& L, const double* md, std::vector<double>
         row[L.ys] = y;
         if (fams) row[L.ys + 1] = L.fam == 2 ? 0.0 : std::lgamma(y + 1.0);
         if (L.g0 && !L.R) row[L.ys + 2] = md[L.g0 + i];
+        if (L.model == SMCN_MODEL_OGLM) {
+            row[L.ys + 2] = L.o0 ? md[L.o0 + i] : 0.0;
+            row[L.ys + 3] = L.w0 ? md[L.w0 + i] : 1.0;
+        }
         for (int r = 0; r < L.R; ++r) {
             row[L.ys + 2 + 2 * r] = md[L.g0 + 2 * r * L.n + i];
             row[L.ys + 3 + 2 * r] = md[L.g0 + (2 * r + 1) * L.n + i];
@@ -306,6 +354,10 @@ inline std::string reg_splice(const RegLayout& train, const double* train_block,
                               std::vector<double>& full) {
     const int64_t nh = train.nh;
     if (!block || len < nh) return "smcn_predict_set_data: the block is the model's data block without the priors";
+    if (train.model == SMCN_MODEL_OGLM && block[4] != train_block[4])
+        return "smcn_predict_set_data: the new rows' flags must repeat the training block's (" +
+               std::to_string(train.flags) + ": new rows carry o where the model was fitted with offsets, and w = 1 where "
+               "it was fitted with weights)";
     for (int64_t q = 0; q < nh; ++q)
         if (q != 1 && block[q] != train_block[q])
             return "smcn_predict_set_data: the new rows' header must repeat the training block's (family or K, p, "

@@ -289,9 +289,21 @@ WGLM_MAX_DIM = 256                         # WideGLMTarget: GLM_MAX_DIM < D <= t
 _NO_PRIOR = object()
 
 
-def _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior):
+def _row_vector(who, name, v, n, what):
+    """offset / weights / exposure as a float vector of the n observations."""
+    try:
+        a = np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: {name} must be numeric") from None
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(f"{who}: {name} must be a vector of {what}")
+    return a
+
+
+def _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior, offset=None, weights=None):
     """GLMTarget's and WideGLMTarget's constructor: the checks (messages prefixed with the class's name), the
-    attributes and the SMCN_MODEL_GLM data block.  `limit(what, D)` raises where the class does not cover D."""
+    attributes and the SMCN_MODEL_GLM data block -- with `offset` or `weights` (GLMTarget only), SMCN_MODEL_OGLM's.
+    `limit(what, D)` raises where the class does not cover D."""
     who = type(self).__name__
     if family not in GLM_FAMILIES:
         raise ValueError(f"{who}: family must be one of {GLM_FAMILIES}, not {family!r}")
@@ -350,8 +362,26 @@ def _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior)
     self.family, self.intercept = family, bool(intercept)
     self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
     self.dispersion_prior = (m_tau, s_tau) if disp else None
+    self.offset = self.weights = None
+    if offset is not None:
+        o = _row_vector(who, "offset", offset, n, f"the n = {n} observations' offsets")
+        if not np.all(np.isfinite(o)):
+            raise ValueError(f"{who}: offset must be finite")
+        self.offset = o.copy()
+    if weights is not None:
+        w = _row_vector(who, "weights", weights, n, f"the n = {n} observations' weights")
+        if not np.all(np.isfinite(w) & (w >= 0.0)):
+            raise ValueError(f"{who}: weights must be finite and >= 0")
+        if not np.any(w > 0.0):
+            raise ValueError(f"{who}: at least one weight must be > 0")
+        self.weights = w.copy()
+    flags = (1 if self.offset is not None else 0) | (2 if self.weights is not None else 0)
     head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic)]
-    data = np.concatenate([head, s, [m_tau, s_tau] if disp else [], y, X.reshape(-1)])
+    if flags:
+        self.model_id = _capi.MODEL_OGLM
+        head.append(float(flags))
+    data = np.concatenate([head, s, [m_tau, s_tau] if disp else [], y,
+                           self.offset if flags & 1 else [], self.weights if flags & 2 else [], X.reshape(-1)])
     names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)]
     if disp:
         names.append(GLM_DISPERSION[family])
@@ -369,22 +399,41 @@ class GLMTarget(PredictMixin, DeviceTarget):
     tau ~ N(m, s^2) for dispersion_prior = (m, s) -- sigma / phi ~ lognormal(m, s); `constrain` reports sigma / phi.
     Coordinates are unconstrained; log pi_phi = lpri + phi * llik.  D <= 64 (65..256: WideGLMTarget; beyond: HostTarget).
 
+    offset (a vector o of n finite values) enters the linear predictor, eta_i = [b_0 +] X_i b + o_i: log(exposure) of a
+    Poisson or negative-binomial regression on rates.  weights (a vector w of n finite values >= 0, not all 0) multiply
+    the observations' terms, llik = sum_i w_i log p(y_i | eta_i): frequency or survey weights, k successes out of m as
+    two rows with weights k and m - k; a row with weight 0 is dropped whatever its term is.  With either, the object is
+    SMCN_MODEL_OGLM's (model_id, block); with neither, it is what it was without the keywords.  After a fit with
+    weights, predict() and predict_draws() work (new rows carry weight 1) and pointwise(), pointwise_loglik() and loo()
+    raise NotImplementedError.
+
     Data block (include/smcnuts_hip.h, SMCN_MODEL_GLM):
     [family (0 bernoulli_logit, 1 poisson_log), n, p, intercept, s_1..s_D, y_1..y_n, X (n x p, row-major)], or
-    [family (2 normal, 3 neg_binomial_2_log), n, p, intercept, s_1..s_Dc, m, s, y_1..y_n, X]."""
+    [family (2 normal, 3 neg_binomial_2_log), n, p, intercept, s_1..s_Dc, m, s, y_1..y_n, X];
+    with offset / weights (SMCN_MODEL_OGLM): [family, n, p, intercept, flags (1 offset | 2 weights), s_1..s_Dc, (m, s),
+    y_1..y_n, o_1..o_n (flags & 1), w_1..w_n (flags & 2), X]."""
     model_id = _capi.MODEL_GLM
 
-    def __init__(self, X, y, family="bernoulli_logit", prior_sd=2.5, intercept=True, dispersion_prior=_NO_PRIOR):
+    def __init__(self, X, y, family="bernoulli_logit", prior_sd=2.5, intercept=True, dispersion_prior=_NO_PRIOR,
+                 offset=None, weights=None):
         def limit(what, D):
             if D > GLM_MAX_DIM:
                 raise ValueError(f"GLMTarget: {what}; the device functor covers D <= {GLM_MAX_DIM}. "
                                  f"WideGLMTarget covers the same model for {GLM_MAX_DIM} < D <= {WGLM_MAX_DIM}; beyond that, "
                                  "wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
-        _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior)
+        _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior, offset, weights)
 
     _PW_CHUNK = 1 << 25          # doubles of ll the device holds at once (256 MB)
 
+    def _refuse_weighted(self):
+        if self.weights is not None:
+            raise NotImplementedError(
+                "GLMTarget: pointwise log-likelihoods, the criteria built on them (WAIC, IS-LOO, fitted values) and LOO "
+                "are not implemented for a fit with weights: what a weighted row's leave-one-out term and the standard "
+                "error of the sum should be is not settled (predict() and predict_draws() do work)")
+
     def _points(self, x):
+        self._refuse_weighted()
         x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
         if x2.ndim != 2 or x2.shape[1] != self.dim:
             raise ValueError(f"GLMTarget: x must be [{self.dim}] or [M, {self.dim}]")
@@ -842,28 +891,51 @@ class OrdinalRegression(PredictMixin, DeviceTarget):
         super().__init__(data, D, names)
 
 
-def LogisticRegression(X, y, prior_sd=2.5, intercept=True):
+def LogisticRegression(X, y, prior_sd=2.5, intercept=True, offset=None, weights=None):
     """Bayesian logistic regression: GLMTarget(X, y, family="bernoulli_logit", ...)."""
-    return GLMTarget(X, y, family="bernoulli_logit", prior_sd=prior_sd, intercept=intercept)
+    return GLMTarget(X, y, family="bernoulli_logit", prior_sd=prior_sd, intercept=intercept, offset=offset,
+                     weights=weights)
 
 
-def PoissonRegression(X, y, prior_sd=2.5, intercept=True):
-    """Bayesian Poisson regression with a log link: GLMTarget(X, y, family="poisson_log", ...)."""
-    return GLMTarget(X, y, family="poisson_log", prior_sd=prior_sd, intercept=intercept)
+def _exposure_offset(who, offset, exposure):
+    """offset, or log(exposure): one of the two at the most (GLMTarget checks the length, as an offset's)."""
+    if exposure is None:
+        return offset
+    if offset is not None:
+        raise ValueError(f"{who}: give offset or exposure, not both (exposure is offset = log(exposure))")
+    try:
+        e = np.asarray(exposure, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: exposure must be numeric") from None
+    if e.ndim != 1:
+        raise ValueError(f"{who}: exposure must be a vector of the observations' exposures")
+    if not np.all(np.isfinite(e) & (e > 0.0)):
+        raise ValueError(f"{who}: exposure must be finite and > 0")
+    return np.log(e)
 
 
-def LinearRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True):
+def PoissonRegression(X, y, prior_sd=2.5, intercept=True, offset=None, weights=None, exposure=None):
+    """Bayesian Poisson regression with a log link: GLMTarget(X, y, family="poisson_log", ...).  exposure (finite, > 0)
+    is offset = log(exposure): y_i ~ poisson(exposure_i e^eta_i)."""
+    offset = _exposure_offset("PoissonRegression", offset, exposure)
+    return GLMTarget(X, y, family="poisson_log", prior_sd=prior_sd, intercept=intercept, offset=offset, weights=weights)
+
+
+def LinearRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True, offset=None, weights=None):
     """Bayesian linear regression, y ~ normal(eta, sigma) with log sigma ~ N(m, s^2):
     GLMTarget(X, y, family="normal", ...).  The last coordinate is log sigma; constrain() reports sigma."""
-    return GLMTarget(X, y, family="normal", prior_sd=prior_sd, intercept=intercept, dispersion_prior=dispersion_prior)
+    return GLMTarget(X, y, family="normal", prior_sd=prior_sd, intercept=intercept, dispersion_prior=dispersion_prior,
+                     offset=offset, weights=weights)
 
 
-def NegativeBinomialRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True):
+def NegativeBinomialRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True, offset=None,
+                               weights=None, exposure=None):
     """Bayesian negative-binomial (NB2) regression with a log link, y ~ neg_binomial_2_log(eta, phi) with
     log phi ~ N(m, s^2): GLMTarget(X, y, family="neg_binomial_2_log", ...).  The last coordinate is log phi;
-    constrain() reports phi."""
+    constrain() reports phi.  exposure (finite, > 0) is offset = log(exposure)."""
+    offset = _exposure_offset("NegativeBinomialRegression", offset, exposure)
     return GLMTarget(X, y, family="neg_binomial_2_log", prior_sd=prior_sd, intercept=intercept,
-                     dispersion_prior=dispersion_prior)
+                     dispersion_prior=dispersion_prior, offset=offset, weights=weights)
 
 
 def StanModel(model_name, model_path=None, data_path=None):

@@ -262,11 +262,13 @@ class PredictMixin:
             return "ord", self.n_classes
         return "glm", 0
 
-    def _predict_block(self, X_new, y_new=None, groups_new=None, new_groups=False):
+    def _predict_block(self, X_new, y_new=None, groups_new=None, new_groups=False, offset_new=None):
         """(block, has_y): the new rows as the model's data block without the priors, checked.  new_groups (predict_draws):
-        labels >= J name new groups; such rows carry group 0 in the block and (block, has_y, labels) is returned."""
+        labels >= J name new groups; such rows carry group 0 in the block and (block, has_y, labels) is returned.
+        A GLMTarget with offsets takes offset_new, one per new row; after a fit with weights the new rows carry weight 1."""
         name = type(self).__name__
         hier = self.model_id == _capi.MODEL_HGLM
+        oglm = self.model_id == _capi.MODEL_OGLM
         X = np.asarray(X_new, dtype=np.float64)
         p = self.X.shape[1]
         if X.ndim == 1:
@@ -298,6 +300,24 @@ class PredictMixin:
                                  "(predictions for new, unseen groups are not implemented)")
         elif groups_new is not None:
             raise ValueError(f"{name}.predict: groups_new is for HierarchicalGLM only")
+        ow = []
+        if oglm and self.offset is not None:
+            if offset_new is None:
+                raise ValueError(f"{name}.predict: offset_new is required (each new row's offset: the model was fitted "
+                                 "with offsets)")
+            try:
+                o = np.asarray(offset_new, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name}.predict: offset_new must be numeric") from None
+            if o.ndim != 1 or o.shape[0] != m:
+                raise ValueError(f"{name}.predict: offset_new must be a vector of the m = {m} rows X_new has")
+            if not np.all(np.isfinite(o)):
+                raise ValueError(f"{name}.predict: offset_new must be finite")
+            ow.append(o)
+        elif offset_new is not None:
+            raise ValueError(f"{name}.predict: offset_new is for a GLMTarget fitted with offsets only")
+        if oglm and self.weights is not None:
+            ow.append(np.ones(m))
         has_y = y_new is not None
         if has_y:
             y = np.asarray(y_new)
@@ -321,10 +341,10 @@ class PredictMixin:
                 raise ValueError(f"{name}.predict: {self.family} needs y_new in {{0, 1, 2, ...}}")
         else:
             y = np.zeros(m)
-        nh = 3 if self.model_id == _capi.MODEL_ORDINAL else (5 if hier else 4)
+        nh = 3 if self.model_id == _capi.MODEL_ORDINAL else (5 if hier or oglm else 4)
         head = np.array(self.model_data[:nh], dtype=np.float64)
         head[1] = float(m)
-        block = np.concatenate([head, y, gf if hier else [], X.reshape(-1)])
+        block = np.concatenate([head, y, gf if hier else [], *ow, X.reshape(-1)])
         if new_groups:
             return block, has_y, (labels if hier else None)
         return block, has_y
@@ -337,12 +357,12 @@ class PredictMixin:
 
     _PR_CHUNK = 1 << 25          # doubles of the matrix the device holds at once (256 MB)
 
-    def predict_loglik(self, x, X_new, y_new, groups_new=None):
+    def predict_loglik(self, x, X_new, y_new, groups_new=None, offset_new=None):
         """log p(y_new_i | x_p): [m] for a 1-D x, [M, m] for 2-D.  The matrix is formed on the device in slabs of
         particles; it has to fit on the host.  At the training rows its row sums are logpdf_parts(x)[1]."""
         if y_new is None:
             raise ValueError(f"{type(self).__name__}.predict_loglik: y_new is required")
-        block, _ = self._predict_block(X_new, y_new, groups_new)
+        block, _ = self._predict_block(X_new, y_new, groups_new, offset_new=offset_new)
         x2 = self._predict_points(x)
         M, m = x2.shape[0], int(block[1])
         step = max(1, min(M, self._PR_CHUNK // m))
@@ -353,22 +373,22 @@ class PredictMixin:
             out[m0:m0 + step] = ctx.predict_loglik(x2[m0:m0 + step])
         return out[0] if np.ndim(x) == 1 else out
 
-    def predict_partials(self, x, X_new, y_new=None, groups_new=None, logw=None):
+    def predict_partials(self, x, X_new, y_new=None, groups_new=None, logw=None, offset_new=None):
         """The mergeable partials of x's rows at the new rows ([1 + m][Q], include/smcnuts_hip.h)."""
-        block, has_y = self._predict_block(X_new, y_new, groups_new)
+        block, has_y = self._predict_block(X_new, y_new, groups_new, offset_new=offset_new)
         x2 = self._predict_points(x)
         ctx = self._context(x2.shape[0])
         ctx.predict_set_data(block, has_y)
         return ctx.predict_partials(x2, logw)
 
-    def predict(self, x, X_new, y_new=None, groups_new=None, logw=None):
+    def predict(self, x, X_new, y_new=None, groups_new=None, logw=None, offset_new=None):
         """Posterior predictive summaries of the weighted points (x [M, D], logw unnormalised or None for equal weights)
         at the new rows -> Prediction; with y_new, the log predictive density of each held-out row as well."""
-        part = self.predict_partials(x, X_new, y_new, groups_new, logw)
+        part = self.predict_partials(x, X_new, y_new, groups_new, logw, offset_new)
         kind, K = self._predict_kind()
         return combine_predict_partials([part], kind, K, y_new is not None)
 
-    def _draws_args(self, X_new, n_draws, groups_new, ancestors, M):
+    def _draws_args(self, X_new, n_draws, groups_new, ancestors, M, offset_new=None):
         """predict_draws' host checks -> (block, labels, S, ancestors)."""
         name = type(self).__name__
         if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or not 1 <= n_draws < 2 ** 31:
@@ -376,7 +396,7 @@ class PredictMixin:
         S = int(n_draws)
         if groups_new is not None and self.model_id != _capi.MODEL_HGLM:
             raise ValueError(f"{name}.predict_draws: groups_new is for HierarchicalGLM only")
-        block, _, labels = self._predict_block(X_new, None, groups_new, new_groups=True)
+        block, _, labels = self._predict_block(X_new, None, groups_new, new_groups=True, offset_new=offset_new)
         if labels is not None and not np.any(labels >= self.n_groups):
             labels = None
         if ancestors is not None:
@@ -388,13 +408,13 @@ class PredictMixin:
             ancestors = a.astype(np.int64)
         return block, labels, S, ancestors
 
-    def predict_draws(self, x, X_new, n_draws, seed=0, groups_new=None, logw=None, ancestors=None):
+    def predict_draws(self, x, X_new, n_draws, seed=0, groups_new=None, logw=None, ancestors=None, offset_new=None):
         """n_draws replicated data sets at the new rows from the weighted points (x [M, D], logw unnormalised or None
         for equal weights; ancestors: the particle of each draw instead of the systematic resampling) ->
         PredictiveDraws.  HierarchicalGLM: groups_new labels >= J are NEW groups, their intercept drawn per data set."""
         x2 = self._predict_points(x)
         M = x2.shape[0]
-        block, labels, S, ancestors = self._draws_args(X_new, n_draws, groups_new, ancestors, M)
+        block, labels, S, ancestors = self._draws_args(X_new, n_draws, groups_new, ancestors, M, offset_new)
         if logw is not None and np.shape(logw) != (M,):
             raise ValueError(f"{type(self).__name__}.predict_draws: logw must hold one log-weight per row of x")
         ctx = self._context(M)

@@ -514,6 +514,8 @@ class SMCSampler:
                                       "pooled generations are not implemented")
         if not hasattr(self.target, "pointwise_partials"):
             self.target.pointwise(None)         # raises NotImplementedError naming the supported targets
+        if hasattr(self.target, "_refuse_weighted"):
+            self.target._refuse_weighted()      # (a GLMTarget fitted with weights: NotImplementedError)
         if not self._finalised:
             raise RuntimeError("pointwise(): run sample() (or step() K times and finalise()) first")
         if self.phi[self.K] != 1.0:
@@ -539,6 +541,8 @@ class SMCSampler:
                                       "pooled generations are not implemented")
         if not hasattr(self.target, "pointwise_partials"):
             self.target.loo(None)               # raises NotImplementedError naming the supported targets
+        if hasattr(self.target, "_refuse_weighted"):
+            self.target._refuse_weighted()
         if not self._finalised:
             raise RuntimeError("loo(): run sample() (or step() K times and finalise()) first")
         if self.phi[self.K] != 1.0:
@@ -610,7 +614,7 @@ class SMCSampler:
             names = [f"x.{i + 1}" for i in range(Dc)]
         return cv.PosteriorCovariance(names, mean, cov, corr, self.ess[self.K], self.N, centre=centre)
 
-    def predict(self, X_new, y_new=None, groups_new=None):
+    def predict(self, X_new, y_new=None, groups_new=None, offset_new=None):
         """Posterior predictive summaries at new rows (predict.Prediction: mean / variance or class probabilities, and with
         y_new the log predictive density of each held-out row) of the final generation and its weights, after sample() /
         finalise(): computed from the resident particles, nothing is uploaded but the new rows and nothing downloaded but
@@ -623,7 +627,7 @@ class SMCSampler:
         if not hasattr(self.target, "predict_partials"):
             raise NotImplementedError(f"{type(self.target).__name__}: held-out prediction is implemented for GLMTarget, "
                                       "HierarchicalGLM, CategoricalRegression and OrdinalRegression")
-        block, has_y = self.target._predict_block(X_new, y_new, groups_new)
+        block, has_y = self.target._predict_block(X_new, y_new, groups_new, offset_new=offset_new)
         if not self._finalised:
             raise RuntimeError("predict(): run sample() (or step() K times and finalise()) first")
         if self.phi[self.K] != 1.0:
@@ -639,10 +643,11 @@ class SMCSampler:
             return combine_predict_partials([p.reshape(part.shape) for p in allp], kind, K, has_y)
         return combine_predict_partials([part], kind, K, has_y)
 
-    def predict_draws(self, X_new=None, n_draws=1000, seed=None, groups_new=None):
+    def predict_draws(self, X_new=None, n_draws=1000, seed=None, groups_new=None, offset_new=None):
         """Posterior predictive draws (predict.PredictiveDraws: n_draws replicated data sets at the rows X_new, each from
         one particle of the final generation chosen by systematic resampling of its weights), after sample() /
-        finalise().  X_new=None: the training rows (for HierarchicalGLM with their groups).  seed=None: derived from the
+        finalise().  X_new=None: the training rows (for HierarchicalGLM with their groups, for a GLMTarget with offsets with
+        their offsets; otherwise offset_new gives the new rows' offsets).  seed=None: derived from the
         sampler's rng.  Several shards: one host all-gather of the ranks' weight totals assigns every rank the slots of
         the comb that fall in its share, each rank draws its own, one host all-gather assembles [S][m]."""
         from .predict import PredictiveDraws, shard_slots
@@ -656,7 +661,9 @@ class SMCSampler:
             X_new = self.target.X
             if groups_new is None and hasattr(self.target, "groups"):
                 groups_new = self.target.groups
-        block, labels, S, _ = self.target._draws_args(X_new, n_draws, groups_new, None, None)
+            if offset_new is None:
+                offset_new = getattr(self.target, "offset", None)
+        block, labels, S, _ = self.target._draws_args(X_new, n_draws, groups_new, None, None, offset_new)
         if not self._finalised:
             raise RuntimeError("predict_draws(): run sample() (or step() K times and finalise()) first")
         if self.phi[self.K] != 1.0:

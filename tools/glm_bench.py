@@ -2,7 +2,7 @@
 OrdinalRegression; MultilevelGLM, SMCN_MODEL_MLGLM) throughput on one MI355X: one JSON line per case.
 
     python tools/glm_bench.py [--K 10] [--N 65536] [--host-N 4096] [--families normal,neg_binomial_2_log]
-                              [--models glm,hier,cat,ord,multi,wide] [--wide-cases bernoulli_logit:65,normal:256]
+                              [--models glm,hier,cat,ord,multi,wide,offset] [--wide-cases bernoulli_logit:65,normal:256]
 
 GPU only; run every invocation under `timeout`.  Cases: bernoulli_logit at N = 65 536 with (n, D) in {(100, 8),
 (1 000, 25), (10 000, 64), (1 000, 16), (1 000, 17)}, poisson_log at (1 000, 25), and normal and neg_binomial_2_log
@@ -32,6 +32,11 @@ column count: the evaluation's multiply-adds (eta and the column sums) per secon
 in the same process: GLMTarget at D = 64 on the first 63 columns of the same data (`wide_ref_glm_D64`: the per-FMA
 efficiency of the one-coordinate-per-lane functor), and the D = 65 model at --host-N particles both device-native and
 through HostTarget with the numpy density (`.._vs_host`: what a user had before).
+Offset cases (--models offset; GLMTarget(offset=, weights=), SMCN_MODEL_OGLM, not in the default set): the (1 000, 16),
+(1 000, 17) and (1 000, 25) cases of each family (--families: a subset) as GLMTarget and as the offset model with o = 0 and
+w = 1 -- the same posterior -- on the same data, step and seed in one process, the two alternated five times: both
+medians, their min..max and the ratio of the medians, one JSON line per case, also appended to
+profiles/glm_offset_bench.jsonl.
 """
 import argparse
 import json
@@ -67,6 +72,10 @@ MULTI_REPEATS = 5
 WIDE_CASES = [("bernoulli_logit", 65), ("bernoulli_logit", 128), ("bernoulli_logit", 129), ("bernoulli_logit", 256),
               ("normal", 128), ("normal", 256)]
 WIDE_N_OBS = 1000
+# offset: (n, D) of each family; D counts tau.  16 / 17 sit on either side of the canonical families' shape boundary; the
+# dispersion families are one wavefront per particle at all three
+OFFSET_CASES = [(1000, 16), (1000, 17), (1000, 25)]
+OFFSET_FAMILIES = ("bernoulli_logit", "poisson_log", "normal", "neg_binomial_2_log")
 
 
 def pick_step(target, N, seed):
@@ -109,7 +118,8 @@ def main():
     ap.add_argument("--families", default=None, help="comma-separated subset of the families (default: all)")
     ap.add_argument("--models", default="glm,hier,cat,ord",
                     help="comma-separated: glm (GLMTarget cases), hier (HierarchicalGLM cases), cat (CategoricalRegression), "
-                         "ord (OrdinalRegression); multi (MultilevelGLM) and wide (WideGLMTarget), not in the default set")
+                         "ord (OrdinalRegression); multi (MultilevelGLM), wide (WideGLMTarget) and offset (GLMTarget with "
+                         "offset= / weights=), not in the default set")
     ap.add_argument("--wide-cases", default=None, help="comma-separated family:D subset of the wide cases (default: all)")
     a = ap.parse_args()
     models = set(a.models.split(","))
@@ -152,6 +162,52 @@ def main():
         multi(a)
     if "wide" in models:
         wide(a)
+    if "offset" in models:
+        offset(a, fams)
+
+
+def offset(a, fams):
+    import _glm
+    import _glm_disp
+    from smcnuts_amd import GLMTarget, _capi
+    out = os.path.join(ROOT, "profiles", "glm_offset_bench.jsonl")
+    for family in OFFSET_FAMILIES:
+        if fams is not None and family not in fams:
+            continue
+        for n, D in OFFSET_CASES:
+            disp = family in _glm_disp.DISP_FAMILIES
+            if disp:
+                X, y = _glm_disp.synthetic(family, n, D - 2, 1000 + D, scale=0.5)
+                kw = dict(family=family, prior_sd=2.0, dispersion_prior=(0.0, 2.5))
+            else:
+                X, y = _glm.synthetic(family, n, D - 1, 1000 + D, scale=0.5)
+                kw = dict(family=family, prior_sd=2.0)
+            tg = GLMTarget(X, y, **kw)
+            to = GLMTarget(X, y, offset=np.zeros(n), weights=np.ones(n), **kw)
+            assert tg.model_id == _capi.MODEL_GLM and to.model_id == _capi.MODEL_OGLM
+            eps, pilot = pick_step(tg, a.N, 5)
+            run(tg, a.N, 2, eps, 6)                              # warm-up: code objects, allocations
+            run(to, a.N, 2, eps, 6)
+            rg, ro = [], []
+            for _ in range(MULTI_REPEATS):
+                rg.append(run(tg, a.N, a.K, eps, 7))
+                ro.append(run(to, a.N, a.K, eps, 7))
+
+            def stats(rs):
+                v = sorted(r["leapfrog_per_s"] for r in rs)
+                return dict(median=v[len(v) // 2], min=v[0], max=v[-1])
+            sg, so = stats(rg), stats(ro)
+            ms = lambda rs: sorted(r["nuts_ms_per_launch"] for r in rs)[len(rs) // 2]
+            r = dict(case=f"offset_{family}_n{n}_D{D}_vs_glm", family=family, n=n, D=D, N=a.N, K=a.K, step_size=eps,
+                     pilot_nleap=pilot, repeats=MULTI_REPEATS, nleap_mean=ro[-1]["nleap_mean"],
+                     offset_leapfrog_per_s=so, glm_leapfrog_per_s=sg, ratio_offset_over_glm=so["median"] / sg["median"],
+                     offset_nuts_ms_per_launch=ms(ro), glm_nuts_ms_per_launch=ms(rg),
+                     glm_spread=(sg["max"] - sg["min"]) / sg["median"],
+                     same_leapfrogs=all(q["leapfrogs"] == rg[0]["leapfrogs"] for q in rg + ro))
+            line = json.dumps(r)
+            print(line, flush=True)
+            with open(out, "a") as f:
+                f.write(line + "\n")
 
 
 def hier(a, fams):
