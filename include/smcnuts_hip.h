@@ -438,6 +438,11 @@ int smcn_device_cache_trim(int device, int64_t* released_bytes, int64_t* idle_by
 /* Test hook for smcn_set_wide_eval: the four sums of the arma recurrence (sum err^2 and its three sensitivity sums) of
  * n rows x[n][4], by one lane (out[i][0..3]) and by a group of `lanes` (64, 32, 16, 8 or 4) lanes (out[i][4..7]). */
 int smcn_selftest_wide(smcn_ctx* ctx, int lanes, const double* x, int64_t n, double* out);
+/* Test hook for the settled mu-sensitivity of the arma recurrence: n rows x[n][4], 64 consecutive rows
+ * to a wavefront in row order.  out[i][0..3] = the four sums of the full recurrence, out[i][4..7] = those of the form the
+ * kernels run (the mu-sensitivity no longer updated once it repeats with period <= 2 on every lane of the wavefront),
+ * out[i][8] = the number of full steps before that wavefront switched (0: it never did).  Arma contexts only. */
+int smcn_selftest_recur(smcn_ctx* ctx, const double* x, int64_t n, double* out);
 
 /* ---- shards: one process per GPU; the reference has no counterpart (single thread) ----
  * In-library communicator: RCCL over xGMI (looked up at run time; no link-time dependency).  Rank 0 obtains the

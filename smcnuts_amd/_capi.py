@@ -114,6 +114,7 @@ SIGNATURES = {
     "smcn_selftest_math": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
     "smcn_measure_peaks": ([_ctx, _dp], C.c_int),
     "smcn_selftest_wide": ([_ctx, C.c_int, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_selftest_recur": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
     "smcn_device_cache_trim": ([C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
     "smcn_debug_profile": ([_ctx, C.POINTER(C.c_uint64), C.c_int], C.c_int),
     "smcn_bench_resample": ([_ctx, C.c_int, C.c_int64, _dp], C.c_int),

@@ -3128,6 +3128,22 @@ int smcn_selftest_wide(smcn_ctx* c, int lanes, const double* x, int64_t n, doubl
     return 0;
 }
 
+int smcn_selftest_recur(smcn_ctx* c, const double* x, int64_t n, double* out) {
+    CHECK_CTX(c);
+    if (c->model != SMCN_MODEL_ARMA || !c->lane_kernel) FAIL(c, "smcn_selftest_recur: arma contexts only");
+    if (!x || !out || n < 1) FAIL(c, "smcn_selftest_recur: bad arguments");
+    int rc = ensure_stage(c, 4 * n);
+    if (rc) return rc;
+    if ((rc = ensure_stage2(c, 9 * n))) return rc;
+    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * 4 * n, hipMemcpyHostToDevice, c->stream));
+    const int blocks = (int)((n + 63) / 64);
+    selftest_recur_kernel<ArmaLaneModel><<<blocks, 64, 0, c->stream>>>(c->mdata, c->stage, n, c->stage2);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, c->stage2, sizeof(double) * 9 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
 }  // extern "C"
 
 // ---- pointwise log-likelihood and its reductions over particles (smcn_pointwise.hpp) ------------------------------------

@@ -9,8 +9,8 @@
 // particle the T-step recurrence needs a two-pass scan (2 x the FMAs) and the whole per-particle
 // scalar work -- density tail, leapfrog, tree state machine -- is issued once per 64/G particles.
 // With one particle per lane the recurrence is the plain serial loop (10 fp64 instructions per
-// time step, y_t in SGPRs, no scan, no DPP) and every other instruction is issued once per 64
-// particles.  64 trees advance in lock step through the evaluation; the divergent tree
+// time step, 9 once the mu-sensitivity has settled; y_t in SGPRs, no scan, no DPP) and every other
+// instruction is issued once per 64 particles.  64 trees advance in lock step through the evaluation; the divergent tree
 // bookkeeping is predicated per lane.
 //
 // Occupancy: N = 65 536 particles are 1 024 wavefronts = ONE per SIMD of the chip.  A wavefront
@@ -44,7 +44,8 @@ constexpr int kN3ReadyWords = 64;   // lane queue: 64-bit ready words of a wavef
 // sigma = exp(s); mdata = [T, y_1..y_T].  Forward sensitivities of err_t:
 //   err_t = y_t - mu - beta y_{t-1} - theta err_{t-1}          (t = 1: y_0 := mu, err_0 := 0)
 //   d err_t / d(mu, beta, theta) = -(1, y_{t-1}, err_{t-1}) - theta * d err_{t-1}
-// ten fp64 instructions per time step; y_t is wave-uniform and comes from scalar loads.
+// ten fp64 instructions per time step (nine once d err / d mu repeats: recur); y_t is wave-uniform and comes from
+// scalar loads.
 // The fp64 constants of ArmaLaneModel::finish (exp_fast, log_ge1 of smcn_device.hpp, the same values in the same
 // order of use).  As literals they become ~30 scalar register PAIRS that the compiler keeps alive across the whole leaf
 // loop -- and, with 100 scalar registers taken, spills to vector lanes and back around every evaluation; read by scalar
@@ -80,8 +81,30 @@ struct ArmaLaneModel {
     }
 
     // The T-step recurrence: ss = sum err_t^2 and gm, gb, gt = sum err_t * d err_t / d(mu, beta, theta).
+    //
+    // SETTLE (what every kernel ships): d err_t / d mu =: dm never sees the data -- dm <- fma(-theta, dm, -1) from
+    // -(1 + beta) -- and for |theta| < 1 that map is a contraction, so in fp64 dm lands within a few dozen steps on an
+    // orbit that repeats EXACTLY: a fixed point or (theta > 0 only) a 2-cycle.  After every 32 full steps the wavefront
+    // asks whether f(f(dm)) == dm holds on all its executing lanes; from then on every later dm is one of dm, d1 = f(dm):
+    // the whole 32-step trips that follow drop the update (nine instructions per step) and gm takes d1, dm, d1, .. in
+    // turn.  An even number of such steps leaves dm the value the full step expects, so the last 0..31 steps run the full
+    // step again, from the same code as a wavefront that never switched (measured: DESIGN.md 4.1).  The bits are those of
+    // the full recurrence by construction.  A NaN, a theta at or beyond +-1 that never becomes periodic, or a series of
+    // fewer than 33 observations leave the wavefront on the full step throughout.
+    // SETTLE = false is the full recurrence alone, kept for smcn_selftest_recur.
+    // sw_o = the number of full steps before the switch (wave-uniform; 0 = never).
+    template <bool SETTLE = true>
     __device__ __forceinline__ void recur(const double (&x)[4], double& ss_o, double& gm_o, double& gb_o,
                                           double& gt_o) const {
+        int sw;
+        recur_sw<SETTLE>(x, ss_o, gm_o, gb_o, gt_o, sw);
+    }
+
+    template <bool SETTLE>
+    __device__ __forceinline__ void recur_sw(const double (&x)[4], double& ss_o, double& gm_o, double& gb_o, double& gt_o,
+                                             int& sw_o) const {
+        using full_t = std::false_type;
+        using settled_t = std::true_type;
         const double mu = x[0], beta = x[1], theta = x[2];
         const double nth = -theta, nbeta = -beta;
         // The series is read 8 steps at a time into scalar registers, one chunk AHEAD of its use (a
@@ -91,22 +114,24 @@ struct ArmaLaneModel {
         double c0 = y[0];
         double err = fma(nbeta, mu, c0 - mu);
         double dm = -(1.0 + beta), db = -mu, dt = 0.0;
+        double d1 = 0.0;                             // settled phase: f(dm); f(d1) == dm
         double ss = err * err, gm = err * dm, gb = err * db, gt = 0.0;
-        auto step = [&](double yp, double yt) {   // t >= 2: yp = y_{t-1}, yt = y_t
+        // t >= 2: yp = y_{t-1}, yt = y_t.  S: the settled step, the k-th of its round (rounds are 16 steps: the parity is static)
+        auto step = [&](auto S, int k, double yp, double yt) __attribute__((always_inline)) {
             dt = fma(nth, dt, -err);                 // uses err_{t-1}
-            dm = fma(nth, dm, -1.0);
+            if constexpr (!decltype(S)::value) dm = fma(nth, dm, -1.0);
             db = fma(nth, db, -yp);
             const double c = fma(nbeta, yp, yt - mu);
             err = fma(nth, err, c);
             ss = fma(err, err, ss);
-            gm = fma(err, dm, gm);
+            gm = fma(err, (decltype(S)::value && !(k & 1)) ? d1 : dm, gm);
             gb = fma(err, db, gb);
             gt = fma(err, dt, gt);
         };
-        auto chunk = [&](double cy, const double (&Y)[8]) {   // 8 steps; cy = the y before Y[0]
-            step(cy, Y[0]);
+        auto chunk = [&](double cy, const double (&Y)[8]) __attribute__((always_inline)) {   // 8 full steps; cy = the y before Y[0]
+            step(full_t{}, 0, cy, Y[0]);
 #pragma unroll
-            for (int k = 1; k < 8; ++k) step(Y[k - 1], Y[k]);
+            for (int k = 1; k < 8; ++k) step(full_t{}, k, Y[k - 1], Y[k]);
         };
         // two register sets take turns: A = y[t .. t+7], B = y[t+8 .. t+15] (0-based), c0 = y[t-1]
         double A[8], B[8];
@@ -119,70 +144,103 @@ struct ArmaLaneModel {
         // Scalar loads return out of order, so a wait is always for ALL of them: each load is therefore issued
         // right AFTER the wait for the previous one (behind the first step of the chunk that consumes it) and has
         // the other seven steps of that chunk plus the first of the next to land.
-        auto round16 = [&](int tt) __attribute__((always_inline)) {   // 16 steps from A = y[tt ..]; leaves A = y[tt + 16 ..]
-            step(c0, A[0]);
+        auto round16 = [&](auto S, int tt) __attribute__((always_inline)) {   // 16 steps from A = y[tt ..]; leaves A = y[tt + 16 ..]
+            step(S, 0, c0, A[0]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 8; ++k) B[k] = y[tt + 8 + k];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 1; k < 8; ++k) step(A[k - 1], A[k]);
+            for (int k = 1; k < 8; ++k) step(S, k, A[k - 1], A[k]);
             c0 = A[7];
             __builtin_amdgcn_sched_barrier(0);       // (nothing of the next chunk moves up in front of its wait)
-            step(c0, B[0]);
+            step(S, 0, c0, B[0]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 8; ++k) A[k] = y[tt + 16 + k];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 1; k < 8; ++k) step(B[k - 1], B[k]);
+            for (int k = 1; k < 8; ++k) step(S, k, B[k - 1], B[k]);
             c0 = B[7];
             __builtin_amdgcn_sched_barrier(0);
         };
-        // four rounds per trip: a taken branch costs a lone wavefront ~30 cycles of instruction refetch
-        for (; t + 64 <= T; t += 64) {
-            round16(t);
-            round16(t + 16);
-            round16(t + 32);
-            round16(t + 48);
-        }
-        if (t + 32 <= T) {
-            round16(t);
-            round16(t + 16);
-            t += 32;
-        }
-        if (t + 16 <= T) {
-            round16(t);
-            t += 16;
-        }
-        int rem = T - t;                             // 0..15 steps left; A holds the first 8 of their y
-        if (rem >= 8) {
+        // everything from step t to the end by the full step; LONG: 32 steps or more may be left
+        auto rest = [&](auto LONG) __attribute__((always_inline)) {
+            constexpr full_t S{};
+            if constexpr (decltype(LONG)::value) {
+                // four rounds per trip: a taken branch costs a lone wavefront ~30 cycles of instruction refetch
+                for (; t + 64 <= T; t += 64) {
+                    round16(S, t);
+                    round16(S, t + 16);
+                    round16(S, t + 32);
+                    round16(S, t + 48);
+                }
+                if (t + 32 <= T) {
+                    round16(S, t);
+                    round16(S, t + 16);
+                    t += 32;
+                }
+            }
+            if (t + 16 <= T) {
+                round16(S, t);
+                t += 16;
+            }
+            int rem = T - t;                         // 0..15 steps left; A holds the first 8 of their y
+            if (rem >= 8) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) B[k] = y[t + 8 + k];
-            __builtin_amdgcn_sched_barrier(0);
-            chunk(c0, A);
-            c0 = A[7];
+                for (int k = 0; k < 8; ++k) B[k] = y[t + 8 + k];
+                __builtin_amdgcn_sched_barrier(0);
+                chunk(c0, A);
+                c0 = A[7];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) A[k] = B[k];
-            rem -= 8;
-        }
-        // 0..7 steps left, taken 4, 2, 1 at a time (three scalar branches, not seven: each one a lone wavefront
-        // takes costs it ~20 cycles); A is shifted down behind each group
-        if (rem >= 4) {
-            step(c0, A[0]); step(A[0], A[1]); step(A[1], A[2]); step(A[2], A[3]);
-            c0 = A[3];
+                for (int k = 0; k < 8; ++k) A[k] = B[k];
+                rem -= 8;
+            }
+            // 0..7 steps left, taken 4, 2, 1 at a time (three scalar branches, not seven: each one a lone wavefront
+            // takes costs it ~20 cycles); A is shifted down behind each group
+            if (rem >= 4) {
+                step(S, 0, c0, A[0]); step(S, 1, A[0], A[1]); step(S, 0, A[1], A[2]); step(S, 1, A[2], A[3]);
+                c0 = A[3];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) A[k] = A[k + 4];
-            rem -= 4;
+                for (int k = 0; k < 4; ++k) A[k] = A[k + 4];
+                rem -= 4;
+            }
+            if (rem >= 2) {
+                step(S, 0, c0, A[0]); step(S, 1, A[0], A[1]);
+                c0 = A[1];
+                A[0] = A[2];
+                rem -= 2;
+            }
+            if (rem >= 1) step(S, 0, c0, A[0]);
+        };
+        int sw = 0;
+        if constexpr (!SETTLE) {
+            rest(std::true_type{});
+        } else {
+            // full steps in trips of 32 until f(f(dm)) == dm on every executing lane (written so that a NaN never
+            // passes; the ballot sees the lanes that execute here and no others: a scalar, wave-uniform branch)
+            bool settled = false;
+            while (t + 32 <= T) {
+                round16(full_t{}, t);
+                round16(full_t{}, t + 16);
+                t += 32;
+                d1 = fma(nth, dm, -1.0);
+                const double d2 = fma(nth, d1, -1.0);
+                if (__ballot(!(d2 == dm)) == 0) {
+                    settled = true;
+                    break;
+                }
+            }
+            if (settled) {
+                sw = t - 1;
+                for (; t + 32 <= T; t += 32) {
+                    round16(settled_t{}, t);
+                    round16(settled_t{}, t + 16);
+                }
+            }
+            rest(std::false_type{});                 // (fewer than 32 steps; dm is where the full step expects it)
         }
-        if (rem >= 2) {
-            step(c0, A[0]); step(A[0], A[1]);
-            c0 = A[1];
-            A[0] = A[2];
-            rem -= 2;
-        }
-        if (rem >= 1) step(c0, A[0]);
-        ss_o = ss; gm_o = gm; gb_o = gb; gt_o = gt;
+        ss_o = ss; gm_o = gm; gb_o = gb; gt_o = gt; sw_o = sw;
     }
 
     // Priors, Jacobian and the likelihood's closed part, from the recurrence's four sums.
@@ -477,6 +535,27 @@ __global__ void __launch_bounds__(64) selftest_wide_kernel(const double* mdata, 
     if (act) {
         double* o = out + row * 8;
         o[0] = n0; o[1] = n1; o[2] = n2; o[3] = n3; o[4] = w0; o[5] = w1; o[6] = w2; o[7] = w3;
+    }
+}
+
+// Selftest of the settled mu-sensitivity (smcn_selftest_recur): block b evaluates rows [64 b, 64 b + 64) in row order,
+// one per lane, so the caller decides which rows share a wavefront; out[row] = the four sums of the full recurrence
+// (recur<false>), those of the shipped form, and the number of full steps before the shipped form switched (0: never).
+template <class Model>
+__global__ void __launch_bounds__(64) selftest_recur_kernel(const double* mdata, const double* x, int64_t M, double* out) {
+    Model model;
+    model.init(mdata);
+    const int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (row < M) {
+        double xv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xv[c] = x[row * 4 + c];
+        double f0, f1, f2, f3, s0, s1, s2, s3;
+        int sw;
+        model.template recur<false>(xv, f0, f1, f2, f3);
+        model.template recur_sw<true>(xv, s0, s1, s2, s3, sw);
+        double* o = out + row * 9;
+        o[0] = f0; o[1] = f1; o[2] = f2; o[3] = f3; o[4] = s0; o[5] = s1; o[6] = s2; o[7] = s3; o[8] = (double)sw;
     }
 }
 
