@@ -28,7 +28,6 @@
 #include "smcn_glk.hpp"
 #include "smcn_step.hpp"
 #include "smcn_comm.hpp"
-#include "smcn_glm_offset.hpp"
 #include "smcn_pointwise.hpp"
 #include "smcn_predict.hpp"
 #include "smcn_predict_draws.hpp"
@@ -435,6 +434,21 @@ void pool_give(int dev, hipStream_t s) {
 }  // namespace
 
 // ---- model dispatch ------------------------------------------------------------
+// The flat GLM's shape, with (OW: SMCN_MODEL_OGLM) or without offsets and weights: 8 lanes per particle up to these D (D
+// counts tau), one wavefront per particle above.  (smcn_ctx_create has checked the data and refused D > 64.)
+// The dispersion families stop at 8, with one coordinate per lane: GlmModel<8, 2, true>'s NUTS kernel needs 256 VGPRs +
+// 152 B of scratch (the shapes with offsets and weights from the resource report there).
+constexpr int kGlmG8 = 16, kGlmDispG8 = 8;
+template <bool OW, class F>
+static int with_flat_glm(smcn_ctx* c, F&& f) {
+    if (c->reg.disp()) {                                  // normal / neg_binomial_2_log
+        if (c->D <= kGlmDispG8) return f(GlmModel<8, kGlmDispG8 / 8, true, OW>{});
+        return f(GlmModel<64, 1, true, OW>{});
+    }
+    if (c->D <= kGlmG8) return f(GlmModel<8, kGlmG8 / 8, false, OW>{});
+    return f(GlmModel<64, 1, false, OW>{});
+}
+
 // Calls f(Model{}) with the device functor matching (model id, data).
 template <class F>
 static int with_model(smcn_ctx* c, F&& f) {
@@ -465,25 +479,8 @@ static int with_model(smcn_ctx* c, F&& f) {
         FAIL(c, "PRMwCD target: the device functor holds up to N=100 observations and Clength=11 columns (M = Clength + 1); "
                 "larger data: pass the model object as a host-evaluated target");
     }
-    if (c->model == SMCN_MODEL_GLM) {
-        // (smcn_ctx_create has checked the data and refused D > 64)
-        if (c->reg.disp()) {                              // normal / neg_binomial_2_log: D counts tau
-            // (G = 8 up to D = 8 only: GlmDispModel<8, 2>'s NUTS kernel needs 256 VGPRs + 152 B of scratch)
-            if (c->D <= 8) return f(GlmDispModel<8, 1>{});
-            return f(GlmDispModel<64, 1>{});
-        }
-        if (c->D <= 16) return f(GlmModel<8, 2>{});
-        return f(GlmModel<64, 1>{});
-    }
-    if (c->model == SMCN_MODEL_OGLM) {
-        // (checked at creation: D <= 64; the shapes from the resource report, DESIGN.md 4.4, Offsets and weights)
-        if (c->reg.disp()) {
-            if (c->D <= kOglmDispG8) return f(GlmOffDispModel<8, 1>{});
-            return f(GlmOffDispModel<64, 1>{});
-        }
-        if (c->D <= kOglmG8) return f(GlmOffModel<8, kOglmG8 / 8>{});
-        return f(GlmOffModel<64, 1>{});
-    }
+    if (c->model == SMCN_MODEL_GLM) return with_flat_glm<false>(c, f);
+    if (c->model == SMCN_MODEL_OGLM) return with_flat_glm<true>(c, f);
     // (smcn_ctx_create has checked the data and refused D > 64)
     if (c->model == SMCN_MODEL_HGLM) return f(GlmHierModel<64, 1>{});
     if (c->model == SMCN_MODEL_MLGLM) return f(GlmMultiModel<64, 1>{});

@@ -23,6 +23,7 @@
 #pragma once
 #include "smcn_device.hpp"
 #include "smcn_regdata.hpp"   // where the regression models' tables lie (glm_table_offset and its kin)
+#include "smcn_glm_family.hpp"   // the regression families' per-observation terms
 
 namespace smcn {
 
@@ -401,341 +402,150 @@ struct PrmwcdDistModel {
 };
 
 // ---------------------------------------------------------------------------
-// Canonical-link GLM (SMCN_MODEL_GLM): Bernoulli-logit or Poisson-log likelihood of a linear predictor
-// eta = X beta (+ intercept), independent Gaussian priors N(0, s_c^2) on the D <= 64 coefficients.
-// The density works on the table reg_repack (smcn_regdata.hpp) lays behind the caller's data (glm_table_offset): a row per
-// observation, [1 (intercept only), X_i1 .. X_ip, 0 (to an even column count DP), y_i, lgamma(y_i + 1)], RS = DP + 2
-// doubles, at a 128-byte boundary, zero rows up to a multiple of 64 -- every lane reads whole rows, unmasked, with
-// 16-byte loads.  The design stays in global memory (L2 / Infinity Cache): the G lanes of every particle group of a
-// wavefront read the same rows in the same instructions (nuts_kernel's lock step), so a row is fetched once per
-// wavefront.  The family is a wave-uniform runtime branch.
-//   G = 8 (D <= 16): coordinate c on lane c % 8; every lane gathers the D coefficients, lane lg evaluates observations
-//                    lg, lg + 8, .. and the D gradient partials are reduce-scattered over the group.
-//   G = 64 (D <= 64): one particle per wavefront, coordinate c on lane c.  Observations go in chunks of 64, one per lane:
-//                    eta with the coefficients read out as scalars (v_readlane), then the chunk's 64 residuals read out
-//                    the same way and lane c accumulates column c of the chunk's rows -- the column sums come out on the
-//                    lane that owns the coordinate, with no butterfly at all.
+// Flat GLM (SMCN_MODEL_GLM, SMCN_MODEL_OGLM): the likelihood of a linear predictor eta = X beta (+ intercept),
+// independent Gaussian priors N(0, s_c^2) on the Dc <= 64 coefficients.  Two compile-time parameters:
+//   DISP  false: the canonical-link families, 0 bernoulli_logit and 1 poisson_log; x = (b_1..b_Dc), D = Dc.
+//         true:  the families with a dispersion coordinate, 2 normal and 3 neg_binomial_2_log (smcn_glm_family.hpp);
+//                x = (b_1..b_Dc, tau), D = Dc + 1, tau last and unconstrained, prior N(m_tau, s_tau^2) on tau (= a
+//                lognormal prior on sigma / phi = e^tau with its Jacobian).  tau is read like any coordinate and its
+//                gradient is one more sum over the observations, which lands on the lane that owns coordinate Dc.
+//                Everything that depends on tau alone is formed once per evaluation (TauConst).
+//   OW    true:  per-observation offsets and weights (SMCN_MODEL_OGLM),
+//                eta_i = [b_0 +] X_i b + o_i,   llik = sum_i w_i l(y_i | eta_i [, tau]),   grad = sum_i w_i d_i X_i
+//                (tau: sum_i w_i gt_i).
+// What differs is behind `if constexpr`: every instantiation compiles to the instruction stream it had when the four were
+// separate structs (GlmModel, GlmDispModel, GlmOffModel, GlmOffDispModel; tools/asm_compare.py,
+// profiles/glm_family_merge_asm.txt).  Within a pair the family is a wave-uniform runtime branch.
+// The density works on the table reg_repack (smcn_regdata.hpp) lays behind the caller's data (glm_table_offset;
+// oglm_table_offset: the same place whatever the flags): a row per observation, [1 (intercept only), X_i1 .. X_ip,
+// 0 (to an even column count DP), y_i, lgamma(y_i + 1) (unused by `normal`)], RS = DP + 2 doubles, at a 128-byte
+// boundary, zero rows up to a multiple of 64 -- every lane reads whole rows, unmasked, with 16-byte loads.  The design
+// stays in global memory (L2 / Infinity Cache): the G lanes of every particle group of a wavefront read the same rows in
+// the same instructions (nuts_kernel's lock step), so a row is fetched once per wavefront.
+// OW rows are [.., y_i, lgamma(y_i + 1), o_i, w_i], RS = DP + 4 doubles; o_i = 0 and w_i = 1 where the caller gave none,
+// and the kernels always read both.  A padding row is all zero, so its weight is 0: `w != 0` is the one test for "this row
+// counts", and a row that does not count adds exactly 0 to every sum whatever its term is (-inf or NaN included: e^eta
+// may overflow there) -- it is selected out, not multiplied out.
+//   G = 8:  coordinate c on lane c % 8; every lane gathers the Dc coefficients, lane lg evaluates observations
+//           lg, lg + 8, .. and the gradient partials are reduce-scattered over the group.  D <= 16 with two coordinates
+//           per lane (canonical; its NUTS kernel is at 246 VGPRs), D <= 8 with one (DISP: the two-coordinate form spills).
+//   G = 64: one particle per wavefront, coordinate c on lane c, D <= 64.  Observations go in chunks of 64, one per lane:
+//           eta with the coefficients read out as scalars (v_readlane), then the chunk's 64 residuals read out
+//           the same way and lane c accumulates column c of the chunk's rows -- the column sums come out on the
+//           lane that owns the coordinate, with no butterfly at all.
 // ---------------------------------------------------------------------------
-template <int G_, int DL_>
+template <int G_, int DL_, bool DISP = false, bool OW = false>
 struct GlmModel {
     static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
     static constexpr bool DIST = true;
     static constexpr int DMAX = G_ * DL_;
     static_assert(G_ == 64 ? DL_ == 1 : (DMAX % 2) == 0, "GlmModel: 64 lanes with one coordinate each, or an even capacity");
+    static constexpr int HEAD = OW ? 5 : 4;   // doubles of the data block in front of the priors
     using d2 = double __attribute__((ext_vector_type(2)));
-    int lg, D, DP, RS, n;
-    bool poisson;
+    int lg, D, Dc, DP, RS, n;
+    bool alt;             // the pair's second family: poisson_log, or (DISP) neg_binomial_2_log
     const double* T;      // the repacked table
-    double inv_s2[DL], lc[DL];   // 1 / s_c^2 and -log s_c - log(2 pi) / 2 of the lane's coordinates (0 beyond D)
+    double mc[DL], inv_s2[DL], lc[DL];   // (DISP) prior mean; 1 / s^2 and -log s - log(2 pi) / 2 of the lane's coordinates (0 beyond D)
 
     __device__ int dim() const { return D; }
     __device__ void init(const double* md, int lg_, double*) {
         lg = lg_;
-        poisson = md[0] != 0.0;
+        alt = DISP ? md[0] == 3.0 : md[0] != 0.0;
         n = (int)md[1];
         const int p = (int)md[2];
-        D = p + (int)md[3];
-        DP = (D + 1) & ~1;
-        RS = glm_row_doubles(D);
-        T = md + glm_table_offset(D, n, p);
+        Dc = p + (int)md[3];
+        D = DISP ? Dc + 1 : Dc;
+        DP = (Dc + 1) & ~1;
+        RS = OW ? oglm_row_doubles(Dc) : glm_row_doubles(Dc);
+        const int npri = DISP ? Dc + 2 : Dc;
+        T = md + (OW ? oglm_table_offset(npri, n, p) : glm_table_offset(npri, n, p));
 #pragma unroll
         for (int i = 0; i < DL; ++i) {
             const int c = lg + G * i;
-            const double s = c < D ? md[4 + c] : 1.0;
+            const double s = c < Dc ? md[HEAD + c] : ((DISP && c == Dc) ? md[HEAD + 1 + Dc] : 1.0);
+            if constexpr (DISP) mc[i] = c == Dc ? md[HEAD + Dc] : 0.0;
             inv_s2[i] = c < D ? 1.0 / (s * s) : 0.0;
             lc[i] = c < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
         }
     }
-    // one observation: log-likelihood term and residual y - E[y | eta]
-    __device__ __forceinline__ void obs(double eta, double y, double lgy, double& term, double& d) const {
-        if (poisson) {
-            const double mu = exp_fast(eta);
-            term = ((y == 0.0 ? 0.0 : y * eta) - mu) - lgy;
-            term = mu < kInf ? term : -kInf;             // poisson_log_lpmf: exp(eta) overflows
-            d = y - mu;
+    // one observation: log-likelihood term, d term / d eta and (DISP) d term / d tau
+    __device__ __forceinline__ void obs(const TauConst& k, double eta, d2 yl, double& term, double& d, double& g) const {
+        if constexpr (DISP) {
+            glm_disp_obs(alt, k, eta, yl.x, yl.y, term, d, g);
         } else {
-            // y eta - softplus(eta), softplus(eta) = max(eta, 0) + log1p(e^-|eta|); y eta - max(eta, 0) is min(eta, 0) for
-            // y = 1 and -max(eta, 0) for y = 0, without the cancellation
-            const double t = exp_fast(-fabs(eta));
-            double inv;
-            const double l1 = log1p_pos(t, inv);          // inv = 1 / (1 + e^-|eta|) = sigmoid(|eta|)
-            term = (y != 0.0 ? fmin(eta, 0.0) : -fmax(eta, 0.0)) - l1;
-            d = y - (eta >= 0.0 ? inv : t * inv);
+            double mean;
+            glm_canon_obs(alt, eta, yl.x, yl.y, term, mean);
+            d = yl.x - mean;
         }
     }
+    // (OW) o_i and w_i of a row.  Spelled at every use, not held in a local: it is one load either way, and a local that
+    // the plain instantiations declare without using it changed their register allocation.
+    __device__ __forceinline__ d2 ow(const d2* row) const { return row[(DP >> 1) + 1]; }
+    // a row's share v of a sum: weighted (OW), and exactly 0 -- selected out, not multiplied out -- where the row does not
+    // count
+    __device__ __forceinline__ double share(bool live, const d2* row, double v) const {
+        if constexpr (OW) v = ow(row).y * v;
+        return live ? v : 0.0;
+    }
     __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
-        double ll = 0.0, lp = 0.0;
+        double ll = 0.0, lp = 0.0, gt = 0.0;
 #pragma unroll
         for (int i = 0; i < DL; ++i) {
-            gp[i] = -x[i] * inv_s2[i];
-            lp += fma(-0.5 * x[i], x[i] * inv_s2[i], lc[i]);
+            double v = x[i];
+            if constexpr (DISP) v = x[i] - mc[i];
+            gp[i] = -v * inv_s2[i];
+            lp += fma(-0.5 * v, v * inv_s2[i], lc[i]);
+        }
+        TauConst k{};
+        if constexpr (DISP) {
+            double xt = x[0];
+#pragma unroll
+            for (int i = 1; i < DL; ++i) xt = Dc / G == i ? x[i] : xt;
+            k = glm_tau_const(alt, group_read<G>(xt, Dc % G));
         }
         if constexpr (G_ == 64) {
             // (four accumulators for the column sums and two for eta: one wavefront per SIMD is all the tree stack in LDS
             //  leaves room for, so dependent FMA chains are not hidden behind other wavefronts)
             double acc[4] = {0.0, 0.0, 0.0, 0.0};
             const int col = lg < DP ? lg : 0;
+            const double xb = (!DISP || lg < Dc) ? x[0] : 0.0;   // (DISP: tau is not a coefficient: 0 on the pad column)
             for (int k0 = 0; k0 < n; k0 += 64) {
-                const double* const rowp = T + (int64_t)(k0 + lg) * RS;
-                const d2* const row = (const d2*)rowp;
+                const d2* const row = (const d2*)(T + (int64_t)(k0 + lg) * RS);
                 double e0 = 0.0, e1 = 0.0;
                 for (int j = 0; j < DP; j += 2) {          // (j wave-uniform: the coefficients are scalar operands)
                     const d2 v = row[j >> 1];
-                    e0 = fma(group_read<64>(x[0], j), v.x, e0);
-                    e1 = fma(group_read<64>(x[0], j + 1), v.y, e1);
+                    e0 = fma(group_read<64>(xb, j), v.x, e0);
+                    e1 = fma(group_read<64>(xb, j + 1), v.y, e1);
                 }
-                const double e = e0 + e1;
                 const d2 yl = row[DP >> 1];
-                double term, d;
-                obs(e, yl.x, yl.y, term, d);
-                const bool live = k0 + lg < n;
-                ll += live ? term : 0.0;
-                d = live ? d : 0.0;
+                double e = e0 + e1;
+                if constexpr (OW) e += ow(row).x;
+                double term, d, g;
+                obs(k, e, yl, term, d, g);
+                const bool live = OW ? ow(row).y != 0.0 : k0 + lg < n;   // (OW: a padding row's weight is 0)
+                ll += share(live, row, term);
+                if constexpr (DISP) gt += share(live, row, g);
+                d = share(live, row, d);
                 // column `lg` of the chunk's 64 rows, weighted by their residuals (read out as scalars)
                 const double* const colp = T + (int64_t)k0 * RS + col;
 #pragma unroll 16
                 for (int i = 0; i < 64; ++i) acc[i & 3] = fma(lane_value(d, i), colp[(int64_t)i * RS], acc[i & 3]);
             }
-            gl[0] = lg < D ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.0;
-            double L, P, u0, u1;
-            wave_sum4(ll, lp, 0.0, 0.0, L, P, u0, u1);
-            llik = L;
-            lpri = P;
-        } else {
-            // ---- 1. the D coefficients to every lane of the group
-            double b[DMAX];
-#pragma unroll
-            for (int j = 0; j < DMAX; ++j) b[j] = group_read<G>(x[j / G], j % G);
-            // ---- 2. this lane's observations lg, lg + G, ..
-            double acc[DMAX];
-#pragma unroll
-            for (int j = 0; j < DMAX; ++j) acc[j] = 0.0;
-            const int S = (n + G - 1) / G;
-#pragma unroll 1
-            for (int k = 0; k < S; ++k) {
-                const int i = lg + G * k;
-                const d2* const row = (const d2*)(T + (int64_t)i * RS);
-                double e = 0.0;
-#pragma unroll
-                for (int j2 = 0; j2 < DMAX / 2; ++j2) {
-                    if (2 * j2 < DP) {                    // (DP wave-uniform)
-                        const d2 v = row[j2];
-                        e = fma(b[2 * j2], v.x, e);
-                        e = fma(b[2 * j2 + 1], v.y, e);
-                    }
-                }
-                const d2 yl = row[DP >> 1];
-                double term, d;
-                obs(e, yl.x, yl.y, term, d);
-                const bool live = i < n;
-                ll += live ? term : 0.0;
-                d = live ? d : 0.0;
-                // (the row again, from the cache: holding it across the residual costs 2 DMAX registers)
-#pragma unroll
-                for (int j2 = 0; j2 < DMAX / 2; ++j2) {
-                    if (2 * j2 < DP) {
-                        const d2 v = row[j2];
-                        acc[2 * j2] = fma(d, v.x, acc[2 * j2]);
-                        acc[2 * j2 + 1] = fma(d, v.y, acc[2 * j2 + 1]);
-                    }
-                }
-            }
-            // ---- 3. reduce-scatter of the gradient partials: lane c % G ends with the sum of column c
-#pragma unroll
-            for (int j = 0; j < DMAX; ++j) acc[j] = j < DP ? group_sum<G>(acc[j]) : 0.0;
-#pragma unroll
-            for (int i = 0; i < DL; ++i) {
-                double v = 0.0;
-#pragma unroll
-                for (int j = i * G; j < (i + 1) * G; ++j) v = (j - i * G == lg) ? acc[j] : v;
-                gl[i] = (lg + G * i) < D ? v : 0.0;
-            }
-            llik = group_sum<G>(ll);
-            lpri = group_sum<G>(lp);
-        }
-    }
-};
-
-
-// ---------------------------------------------------------------------------
-// GLM with a dispersion coordinate (SMCN_MODEL_GLM families 2 and 3): x = (b_1..b_Dc, tau), D = Dc + 1, tau last and
-// unconstrained, prior N(m_tau, s_tau^2) on tau (= a lognormal prior on sigma / phi = e^tau with its Jacobian).
-//   2 normal:             y ~ N(eta, sigma^2), sigma = e^tau
-//   3 neg_binomial_2_log: y ~ NB2(mu = e^eta, phi = e^tau) (Stan's parameterisation)
-// The table and both shapes are GlmModel's (row width from Dc; column `aux` = lgamma(y + 1), unused by `normal`); tau
-// is read like any coordinate and its gradient is one more sum over the observations, which lands on the lane that owns
-// coordinate Dc.  A sibling of GlmModel rather than a template switch on it, so that GlmModel's instruction streams and
-// register allocation stay as they are (its G = 8 NUTS kernel is at 246 VGPRs).  Shapes: G = 8 with one coordinate per
-// lane for D <= 8 (the two-coordinate form spills), G = 64 for 9 <= D <= 64.
-// NB accuracy where phi >> y + mu: for phi >= kGammaAsym, lgamma(y + phi) - lgamma(phi) - y tau and psi(y + phi) - psi(phi)
-// are formed from Stirling's series with log1p(y / phi) -- no lgamma(phi)-sized or phi tau-sized intermediate; below,
-// as differences of lgamma / psi, each from a shift up to >= kGammaAsym and the same series (lgamma(phi) and psi(phi)
-// are O(1 + |tau|) there; the device library's lgamma inlined into the observation loop made the kernels spill).
-// Everything that depends on tau alone is
-// formed once per evaluation.  Non-finite: -inf when e^-2tau (normal), e^eta or e^tau (NB) overflows, or e^tau
-// leaves the normal range (NB, tau < -708.39).
-// ---------------------------------------------------------------------------
-constexpr double kLogDblMax = 709.782712893384;        // log(DBL_MAX), rounded down: exp(v) is finite for v <= this
-constexpr double kLogDblMinNormal = -708.3964185322641;   // log(DBL_MIN), rounded up
-
-template <int G_, int DL_>
-struct GlmDispModel {
-    static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
-    static constexpr bool DIST = true;
-    static constexpr int DMAX = G_ * DL_;
-    static_assert(G_ == 64 ? DL_ == 1 : (DMAX % 2) == 0, "GlmDispModel: 64 lanes with one coordinate each, or an even capacity");
-    using d2 = double __attribute__((ext_vector_type(2)));
-    int lg, D, Dc, DP, RS, n;
-    bool nb;
-    const double* T;      // the repacked table
-    double mc[DL], inv_s2[DL], lc[DL];   // prior mean, 1 / s^2 and -log s - log(2 pi) / 2 of the lane's coordinates
-
-    // what one evaluation derives from tau alone (the two families share the registers)
-    struct TauConst {
-        double tau;
-        double phi, iphi;             // normal: e^-2tau, -tau - log(2 pi) / 2;  NB: e^tau, 1 / phi
-        double c1, c2;                // NB: Stirling and digamma tails of phi (big), or lgamma(phi) and psi(phi)
-        bool big, bad;
-    };
-
-    __device__ int dim() const { return D; }
-    __device__ void init(const double* md, int lg_, double*) {
-        lg = lg_;
-        nb = md[0] == 3.0;
-        n = (int)md[1];
-        const int p = (int)md[2];
-        Dc = p + (int)md[3];
-        D = Dc + 1;
-        DP = (Dc + 1) & ~1;
-        RS = glm_row_doubles(Dc);
-        T = md + glm_table_offset(Dc + 2, n, p);
-#pragma unroll
-        for (int i = 0; i < DL; ++i) {
-            const int c = lg + G * i;
-            const double s = c < Dc ? md[4 + c] : (c == Dc ? md[5 + Dc] : 1.0);
-            mc[i] = c == Dc ? md[4 + Dc] : 0.0;
-            inv_s2[i] = c < D ? 1.0 / (s * s) : 0.0;
-            lc[i] = c < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
-        }
-    }
-    __device__ __forceinline__ TauConst tau_const(double tau) const {
-        TauConst k;
-        k.tau = tau;
-        if (!nb) {
-            k.bad = -2.0 * tau > kLogDblMax;
-            k.phi = exp_fast(-2.0 * tau);
-            k.iphi = -tau - 0.5 * kLog2Pi;
-            k.c1 = k.c2 = 0.0;
-            k.big = false;
-        } else {
-            k.bad = !(tau <= kLogDblMax && tau >= kLogDblMinNormal);
-            k.phi = k.bad ? 1.0 : exp_fast(tau);
-            k.iphi = 1.0 / k.phi;
-            k.big = k.phi >= kGammaAsym;
-            if (k.big) {
-                k.c1 = stirling_tail(k.iphi);
-                k.c2 = digamma_tail(k.iphi);
-            } else {
-                lgamma_digamma_pos(k.phi, k.c1, k.c2);
-            }
-        }
-        return k;
-    }
-    // one observation: log-likelihood term, d term / d eta and d term / d tau
-    __device__ __forceinline__ void obs(const TauConst& k, double eta, double y, double lgy, double& term, double& d,
-                                        double& gt) const {
-        if (!nb) {
-            const double r = y - eta;
-            const double rw = r * k.phi;                 // (phi: e^-2tau, iphi: -tau - log(2 pi) / 2)
-            const double q = r * rw;
-            term = fma(-0.5, q, k.iphi);
-            d = rw;
-            gt = q - 1.0;
-        } else {
-            const double x = y + k.phi;
-            // A = lgamma(y + phi) - lgamma(phi) [- y tau when big], B = psi(y + phi) - psi(phi); both 0 at y = 0.  One
-            // pair of asymptotic tails either way: at y + phi (big), or at y + phi shifted up to >= kGammaAsym
-            double P, S;
-            const double xs = k.big ? x : gamma_shift(y == 0.0 ? kGammaAsym : x, P, S);
-            const double ix = 1.0 / xs;
-            const double st = stirling_tail(ix), dt = digamma_tail(ix);
-            double A, B, ts;
-            if (k.big) {
-                double ir;                                   // 1 / (1 + y / phi) = phi / x
-                const double l1 = log1p_pos(y * k.iphi, ir);   // log(x / phi)
-                A = fma(x - 0.5, l1, -y) + (st - k.c1);
-                B = fma(0.5 * y, ix * k.iphi, l1) - (dt - k.c2);
-                ts = 0.0;
-            } else {                                         // (xs >= 10 and P >= 1: log_ge1)
-                const double lx = log_ge1(xs);
-                A = ((fma(xs - 0.5, lx, -xs) + (0.5 * kLog2Pi + st)) - log_ge1(P)) - k.c1;
-                B = (((lx - 0.5 * ix) - dt) - S) - k.c2;
-                ts = k.tau;
-            }
-            A = y == 0.0 ? 0.0 : A;
-            B = y == 0.0 ? 0.0 : B;
-            // softplus(eta - tau) = log(mu + phi) - tau, sigmoid(eta - tau) = mu / (mu + phi) and its complement
-            const double z = eta - k.tau;
-            const double t = exp_fast(-fabs(z));
-            double inv;
-            const double sp = fmax(z, 0.0) + log1p_pos(t, inv);
-            const double ti = t * inv;
-            const double sg = z >= 0.0 ? inv : ti, sc = z >= 0.0 ? ti : inv;
-            term = ((A - lgy) - x * sp) + y * (eta - ts);
-            term = eta <= kLogDblMax ? term : -kInf;           // e^eta overflows
-            d = fma(-x, sg, y);
-            gt = fma(k.phi, (B - sp) + sg, -y * sc);
-        }
-    }
-    __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
-        double ll = 0.0, lp = 0.0, gt = 0.0;
-#pragma unroll
-        for (int i = 0; i < DL; ++i) {
-            const double v = x[i] - mc[i];
-            gp[i] = -v * inv_s2[i];
-            lp += fma(-0.5 * v, v * inv_s2[i], lc[i]);
-        }
-        double xt = x[0];
-#pragma unroll
-        for (int i = 1; i < DL; ++i) xt = Dc / G == i ? x[i] : xt;
-        const TauConst k = tau_const(group_read<G>(xt, Dc % G));
-        if constexpr (G_ == 64) {
-            double acc[4] = {0.0, 0.0, 0.0, 0.0};
-            const int col = lg < DP ? lg : 0;
-            const double xb = lg < Dc ? x[0] : 0.0;           // (tau is not a coefficient: 0 on the pad column)
-            for (int k0 = 0; k0 < n; k0 += 64) {
-                const double* const rowp = T + (int64_t)(k0 + lg) * RS;
-                const d2* const row = (const d2*)rowp;
-                double e0 = 0.0, e1 = 0.0;
-                for (int j = 0; j < DP; j += 2) {
-                    const d2 v = row[j >> 1];
-                    e0 = fma(group_read<64>(xb, j), v.x, e0);
-                    e1 = fma(group_read<64>(xb, j + 1), v.y, e1);
-                }
-                const double e = e0 + e1;
-                const d2 yl = row[DP >> 1];
-                double term, d, g;
-                obs(k, e, yl.x, yl.y, term, d, g);
-                const bool live = k0 + lg < n;
-                ll += live ? term : 0.0;
-                gt += live ? g : 0.0;
-                d = live ? d : 0.0;
-                const double* const colp = T + (int64_t)k0 * RS + col;
-#pragma unroll 16
-                for (int i = 0; i < 64; ++i) acc[i & 3] = fma(lane_value(d, i), colp[(int64_t)i * RS], acc[i & 3]);
-            }
             double L, P, GT, u1;
+            // (the lane's column sum in front of the wave-wide sums, or behind them where tau's lane takes one of them: each
+            //  case in the statement order its kernels have always been compiled from -- the other order moves registers)
+            if constexpr (!DISP) gl[0] = lg < Dc ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.0;
             wave_sum4(ll, lp, gt, 0.0, L, P, GT, u1);
-            gl[0] = lg < Dc ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : (lg == Dc ? GT : 0.0);
-            llik = k.bad ? -kInf : L;
+            if constexpr (DISP) gl[0] = lg < Dc ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : (lg == Dc ? GT : 0.0);
+            llik = (DISP && k.bad) ? -kInf : L;
             lpri = P;
         } else {
-            // ---- 1. the Dc coefficients to every lane of the group (0 in tau's slot and beyond)
+            // ---- 1. the Dc coefficients to every lane of the group (DISP: 0 in tau's slot and beyond)
             double b[DMAX];
 #pragma unroll
             for (int j = 0; j < DMAX; ++j) {
                 const double v = group_read<G>(x[j / G], j % G);
-                b[j] = j < Dc ? v : 0.0;
+                b[j] = (!DISP || j < Dc) ? v : 0.0;
             }
             // ---- 2. this lane's observations lg, lg + G, ..
             double acc[DMAX];
@@ -749,19 +559,21 @@ struct GlmDispModel {
                 double e = 0.0;
 #pragma unroll
                 for (int j2 = 0; j2 < DMAX / 2; ++j2) {
-                    if (2 * j2 < DP) {
+                    if (2 * j2 < DP) {                    // (DP wave-uniform)
                         const d2 v = row[j2];
                         e = fma(b[2 * j2], v.x, e);
                         e = fma(b[2 * j2 + 1], v.y, e);
                     }
                 }
                 const d2 yl = row[DP >> 1];
+                if constexpr (OW) e += ow(row).x;
                 double term, d, g;
-                obs(k, e, yl.x, yl.y, term, d, g);
-                const bool live = i < n;
-                ll += live ? term : 0.0;
-                gt += live ? g : 0.0;
-                d = live ? d : 0.0;
+                obs(k, e, yl, term, d, g);
+                const bool live = OW ? ow(row).y != 0.0 : i < n;
+                ll += share(live, row, term);
+                if constexpr (DISP) gt += share(live, row, g);
+                d = share(live, row, d);
+                // (the row again, from the cache: holding it across the residual costs 2 DMAX registers)
 #pragma unroll
                 for (int j2 = 0; j2 < DMAX / 2; ++j2) {
                     if (2 * j2 < DP) {
@@ -771,19 +583,22 @@ struct GlmDispModel {
                     }
                 }
             }
-            // ---- 3. reduce-scatter of the gradient partials; tau's sum to the lane that owns coordinate Dc
+            // ---- 3. reduce-scatter of the gradient partials: lane c % G ends with the sum of column c; (DISP) tau's sum
+            //         to the lane that owns coordinate Dc
+            const int nsum = DISP ? Dc : DP;
 #pragma unroll
-            for (int j = 0; j < DMAX; ++j) acc[j] = j < Dc ? group_sum<G>(acc[j]) : 0.0;
-            const double GT = group_sum<G>(gt);
+            for (int j = 0; j < DMAX; ++j) acc[j] = j < nsum ? group_sum<G>(acc[j]) : 0.0;
+            double GT = 0.0;
+            if constexpr (DISP) GT = group_sum<G>(gt);
 #pragma unroll
             for (int i = 0; i < DL; ++i) {
                 double v = 0.0;
 #pragma unroll
                 for (int j = i * G; j < (i + 1) * G; ++j) v = (j - i * G == lg) ? acc[j] : v;
                 const int c = lg + G * i;
-                gl[i] = c < Dc ? v : (c == Dc ? GT : 0.0);
+                gl[i] = c < Dc ? v : ((DISP && c == Dc) ? GT : 0.0);
             }
-            llik = k.bad ? -kInf : group_sum<G>(ll);
+            llik = (DISP && k.bad) ? -kInf : group_sum<G>(ll);
             lpri = group_sum<G>(lp);
         }
     }
@@ -803,8 +618,8 @@ struct GlmDispModel {
 //   the 64-step read-out of the chunk's residuals: lane c < Dc accumulates d_i X_ic, lane Dc + j accumulates d_i [g_i == j]
 //        (the broadcast group index compared with its own j; no column load), multiplied by e^lt once at the end;
 //   d / d lt = sum_i d_i alpha_{g_i} (a per-lane term) and the dispersion sum go through wave_sum4 with llik and lpri.
-// The per-observation terms are GlmModel's / GlmDispModel's own obs() (and tau_const()), called on members of which only
-// the family flag is set.  Non-finite: the GLM rules, and -inf (lpri and llik) when e^(2 lt) overflows.
+// The per-observation terms are the flat GLM's (smcn_glm_family.hpp).  Non-finite: the GLM rules, and -inf (lpri and
+// llik) when e^(2 lt) overflows.
 // ---------------------------------------------------------------------------
 template <int G_, int DL_>
 struct GlmHierModel {
@@ -812,8 +627,7 @@ struct GlmHierModel {
     static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = 2, LDS_LEVELS = 2;
     static constexpr bool DIST = true;
     using d2 = double __attribute__((ext_vector_type(2)));
-    GlmModel<64, 1> glm;          // families 0 / 1: obs() (only `poisson` is set)
-    GlmDispModel<64, 1> disp;     // families 2 / 3: tau_const() and obs() (only `nb` is set)
+    bool poisson, nb;             // family 1 among the canonical pair 0 / 1, family 3 among the dispersion pair 2 / 3
     int lg, D, Dc, J, DP, RS, n;
     int role;                     // this lane's coordinate: 0 coefficient, 1 group z_j, 2 lt, 3 ld, 4 none
     bool hasd;
@@ -825,8 +639,8 @@ struct GlmHierModel {
         lg = lg_;
         const double fam = md[0];
         hasd = fam >= 2.0;
-        glm.poisson = fam == 1.0;
-        disp.nb = fam == 3.0;
+        poisson = fam == 1.0;
+        nb = fam == 3.0;
         n = (int)md[1];
         const int p = (int)md[2];
         Dc = p + (int)md[3];
@@ -850,7 +664,7 @@ struct GlmHierModel {
         const double lt = group_read<64>(x[0], Dc + J);
         const double tau = exp_fast(lt), e2 = tau * tau;
         const bool bad = !(e2 < kInf);                     // e^(2 lt) overflows
-        const auto k = disp.tau_const(hasd ? group_read<64>(x[0], Dc + J + 1) : 0.0);
+        const auto k = glm_tau_const(nb, hasd ? group_read<64>(x[0], Dc + J + 1) : 0.0);
         // ---- prior of the lane's coordinate
         double lp, g0;
         if (role == 2) {
@@ -880,8 +694,13 @@ struct GlmHierModel {
             const double a = tau * __shfl(x[0], Dc + gi, 64);   // alpha_{g_i}
             const double e = (e0 + e1) + a;
             double term, d, g = 0.0;
-            if (hasd) disp.obs(k, e, yl.x, yl.y, term, d, g);
-            else glm.obs(e, yl.x, yl.y, term, d);
+            if (hasd) {
+                glm_disp_obs(nb, k, e, yl.x, yl.y, term, d, g);
+            } else {
+                double mean;
+                glm_canon_obs(poisson, e, yl.x, yl.y, term, mean);
+                d = yl.x - mean;
+            }
             const bool live = k0 + lg < n;
             ll += live ? term : 0.0;
             gt += live ? g : 0.0;
@@ -935,8 +754,7 @@ struct GlmMultiModel {
     static constexpr bool DIST = true;
     static constexpr int RM = kMlMaxTerms;
     using d2 = double __attribute__((ext_vector_type(2)));
-    GlmModel<64, 1> glm;          // families 0 / 1: obs() (only `poisson` is set)
-    GlmDispModel<64, 1> disp;     // families 2 / 3: tau_const() and obs() (only `nb` is set)
+    bool poisson, nb;             // family 1 among the canonical pair 0 / 1, family 3 among the dispersion pair 2 / 3
     int lg, D, Dc, R, LT0, DP, RS, n;
     int off[RM];                  // first lane of term r's u (wave-uniform)
     int role;                     // this lane's coordinate: 0 coefficient, 1 a level's u, 2 an lt, 3 ld, 4 none
@@ -950,8 +768,8 @@ struct GlmMultiModel {
         lg = lg_;
         const double fam = md[0];
         hasd = fam >= 2.0;
-        glm.poisson = fam == 1.0;
-        disp.nb = fam == 3.0;
+        poisson = fam == 1.0;
+        nb = fam == 3.0;
         n = (int)md[1];
         const int p = (int)md[2];
         Dc = p + (int)md[3];
@@ -995,7 +813,7 @@ struct GlmMultiModel {
                 tauo = tr == r ? tau[r] : tauo;
             }
         }
-        const auto k = disp.tau_const(hasd ? group_read<64>(x[0], LT0 + R) : 0.0);
+        const auto k = glm_tau_const(nb, hasd ? group_read<64>(x[0], LT0 + R) : 0.0);
         // ---- prior of the lane's coordinate
         double lp, g0;
         if (role == 2) {
@@ -1035,8 +853,13 @@ struct GlmMultiModel {
             }
             const double e = (e0 + e1) + as;
             double term, d, g = 0.0;
-            if (hasd) disp.obs(k, e, yl.x, yl.y, term, d, g);
-            else glm.obs(e, yl.x, yl.y, term, d);
+            if (hasd) {
+                glm_disp_obs(nb, k, e, yl.x, yl.y, term, d, g);
+            } else {
+                double mean;
+                glm_canon_obs(poisson, e, yl.x, yl.y, term, mean);
+                d = yl.x - mean;
+            }
             const bool live = k0 + lg < n;
             ll += live ? term : 0.0;
             gt += live ? g : 0.0;
@@ -1085,10 +908,9 @@ struct GlmMultiModel {
 // ---------------------------------------------------------------------------
 // Wide GLM (SMCN_MODEL_WGLM): SMCN_MODEL_GLM's density -- the four families, the same data block, the same table -- for
 // 65 <= D <= 256 coordinates.  One wavefront per particle, coordinate c = lane + 64 k in slot k of lane `lane`
-// (DL = 2: D <= 128, DL = 4: D <= 256); x = (b_1..b_Dc [, tau]), tau on lane Dc % 64, slot Dc / 64.  A sibling of
-// GlmModel<64, 1> / GlmDispModel<64, 1>, not a switch on them (their instruction streams stay as they are); the
-// per-observation terms are their own obs() (and tau_const()), called on members of which only the family flag is set,
-// the family a wave-uniform runtime branch as in GlmHierModel.  One evaluation walks the observations in chunks of 64, one
+// (DL = 2: D <= 128, DL = 4: D <= 256); x = (b_1..b_Dc [, tau]), tau on lane Dc % 64, slot Dc / 64.  Not a shape of
+// GlmModel: the walk differs in substance (slots, two passes).  The per-observation terms are the flat GLM's
+// (smcn_glm_family.hpp), the family a wave-uniform runtime branch as in GlmHierModel.  One evaluation walks the observations in chunks of 64, one
 // row per lane, in two passes over the chunk:
 //   eta: slot by slot, the coefficient of column 64 k + j read out of lane j as a scalar operand, the lane's own row read
 //        with 16-byte loads, two accumulators;
@@ -1106,8 +928,7 @@ struct GlmWideModel {
     static constexpr int G = G_, DL = DL_, SHARED = 0, MIN_WAVES = DL_ == 2 ? 2 : 1, LDS_LEVELS = 2;
     static constexpr bool DIST = true;
     using d2 = double __attribute__((ext_vector_type(2)));
-    GlmModel<64, 1> glm;          // families 0 / 1: obs() (only `poisson` is set)
-    GlmDispModel<64, 1> disp;     // families 2 / 3: tau_const() and obs() (only `nb` is set)
+    bool poisson, nb;             // family 1 among the canonical pair 0 / 1, family 3 among the dispersion pair 2 / 3
     int lg, D, Dc, DP, RS, n;
     bool hasd;
     const double* T;              // the repacked table
@@ -1123,8 +944,8 @@ struct GlmWideModel {
         lg = lg_;
         const double fam = md[0];
         hasd = fam >= 2.0;
-        glm.poisson = fam == 1.0;
-        disp.nb = fam == 3.0;
+        poisson = fam == 1.0;
+        nb = fam == 3.0;
         n = (int)md[1];
         const int p = (int)md[2];
         Dc = p + (int)md[3];
@@ -1157,7 +978,7 @@ struct GlmWideModel {
         double xt = x[0];
 #pragma unroll
         for (int k = 1; k < DL; ++k) xt = (Dc >> 6) == k ? x[k] : xt;
-        const auto tc = disp.tau_const(hasd ? group_read<64>(xt, Dc & 63) : 0.0);
+        const auto tc = glm_tau_const(nb, hasd ? group_read<64>(xt, Dc & 63) : 0.0);
         double acc[DL][2];
 #pragma unroll
         for (int k = 0; k < DL; ++k) acc[k][0] = acc[k][1] = 0.0;
@@ -1179,8 +1000,13 @@ struct GlmWideModel {
             const double e = e0 + e1;
             const d2 yl = row[dp >> 1];
             double term, d, g = 0.0;
-            if (hasd) disp.obs(tc, e, yl.x, yl.y, term, d, g);
-            else glm.obs(e, yl.x, yl.y, term, d);
+            if (hasd) {
+                glm_disp_obs(nb, tc, e, yl.x, yl.y, term, d, g);
+            } else {
+                double mean;
+                glm_canon_obs(poisson, e, yl.x, yl.y, term, mean);
+                d = yl.x - mean;
+            }
             const bool live = k0 + lg < n;
             ll += live ? term : 0.0;
             gt += live ? g : 0.0;
@@ -1471,25 +1297,6 @@ struct GlmOrdModel {
         lc = lg < D ? -log(s) - 0.5 * kLog2Pi : 0.0;
         cnt = mc >= 2 ? md[ord_counts_offset(D, n, p) + mc - 1] : 0.0;
     }
-    // one observation with label y, lo = c_y (y >= 1) and hi = c_{y+1} (y <= K - 2): log-likelihood term, d / d eta, and
-    // the partials of the lower and the upper cutpoint
-    __device__ __forceinline__ void obs(double eta, int y, double lo, double hi, double& term, double& de, double& glo,
-                                        double& ghi) const {
-        const bool hl = y >= 1, hh = y < Km1;
-        const double a1 = lo - eta, a2 = eta - hi;
-        // (exp_fast flushes below -800; a NaN stays NaN)
-        auto ex = [](double a) { return exp_fast(a < -800.0 ? -800.0 : a); };
-        const double t1 = ex(-fabs(a1)), t2 = ex(-fabs(a2));
-        double i1, i2;
-        const double sp1 = fmax(a1, 0.0) + log1p_pos(t1, i1);   // softplus(a1); i1 = sigmoid(|a1|)
-        const double sp2 = fmax(a2, 0.0) + log1p_pos(t2, i2);
-        const double s1 = a1 >= 0.0 ? i1 : t1 * i1, s2 = a2 >= 0.0 ? i2 : t2 * i2;
-        term = -((hl ? sp1 : 0.0) + (hh ? sp2 : 0.0));
-        term = finite_d(eta) ? term : -kInf;
-        glo = hl ? -s1 : 0.0;
-        ghi = hh ? s2 : 0.0;
-        de = -(glo + ghi);
-    }
     __device__ void eval(const double (&x)[DL], double& lpri, double& llik, double (&gp)[DL], double (&gl)[DL]) const {
         const double u = x[0];
         const bool isc = mc >= 1;
@@ -1519,7 +1326,7 @@ struct GlmOrdModel {
                 const double lo = __shfl(cut, p + (y >= 1 ? y - 1 : 0), 64);
                 const double hi = __shfl(cut, p + (y < Km1 ? y : Km1 - 1), 64);
                 double term, de, glo, ghi;
-                obs(e0 + e1, y, lo, hi, term, de, glo, ghi);
+                glm_ord_obs(Km1, e0 + e1, y, lo, hi, term, de, glo, ghi);
                 const bool live = k0 + lg < n;
                 ll += live ? term : 0.0;
                 de = live ? de : 0.0;
@@ -1569,7 +1376,7 @@ struct GlmOrdModel {
                     hi = j == p + y ? cs[j] : hi;
                 }
                 double term, de, glo, ghi;
-                obs(e, y, lo, hi, term, de, glo, ghi);
+                glm_ord_obs(Km1, e, y, lo, hi, term, de, glo, ghi);
                 const bool live = i < n;
                 ll += live ? term : 0.0;
                 de = live ? de : 0.0;

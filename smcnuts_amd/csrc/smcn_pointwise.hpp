@@ -12,10 +12,8 @@
 // slice order (groups of 16 first, then the groups), so a result depends on its inputs alone (the slice count follows
 // from M and n: pointwise_slices).
 //
-// The per-observation terms are the functors' own arithmetic: GlmDispModel<64, 1>::tau_const / obs are called on an
-// instance of which only `nb` is set (as GlmHierModel does); GlmModel's two terms are restated in pw_glm_obs because
-// the fitted value wants mu / the sigmoid itself, not the residual y - mu (exp_fast, log1p_pos: the same calls in the
-// same order, so the term has the bits of GlmModel::obs).
+// The per-observation terms are the density functors' own (smcn_glm_family.hpp: glm_canon_obs, which returns the fitted
+// value mu / the sigmoid itself, and glm_tau_const / glm_disp_obs), so a term has the bits the density's sum took.
 //
 // Partials (column layout: include/smcnuts_hip.h, smcn_pointwise_partials).  lw' = lw - mw with mw the largest finite
 // log-weight of the call; "contributing" particles are those with finite lw.  Per observation, over the contributing
@@ -42,22 +40,6 @@ __host__ __device__ inline int64_t pointwise_slices(int64_t M, int64_t n, int64_
     const int64_t cps = (chunks + want - 1) / want;
     *chunks_per_slice = cps;
     return (chunks + cps - 1) / cps;
-}
-
-// GlmModel::obs with E[y | eta] in place of the residual
-__device__ __forceinline__ void pw_glm_obs(bool poisson, double eta, double y, double lgy, double& term, double& mean) {
-    if (poisson) {
-        const double mu = exp_fast(eta);
-        term = ((y == 0.0 ? 0.0 : y * eta) - mu) - lgy;
-        term = mu < kInf ? term : -kInf;
-        mean = mu;
-    } else {
-        const double t = exp_fast(-fabs(eta));
-        double inv;
-        const double l1 = log1p_pos(t, inv);
-        term = (y != 0.0 ? fmin(eta, 0.0) : -fmax(eta, 0.0)) - l1;
-        mean = eta >= 0.0 ? inv : t * inv;
-    }
 }
 
 // e^-|d| for the running log-sum-exp updates; 0 below e^-800 (exp_fast wants a finite argument)
@@ -97,9 +79,7 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
     // (the weight slot is not read: a term is log p(y_i | x); weights belong to the training likelihood's sum)
     double off = 0.0;
     if constexpr (OW) off = rowp[(DP >> 1) + 1].x;
-    GlmDispModel<64, 1> dm;       // (tau_const() and obs() read `nb` only)
-    dm.nb = a.fam == 3;
-    const bool poisson = a.fam == 1;
+    const bool poisson = a.fam == 1, nb = a.fam == 3;
 
     const int64_t p_end = a.M < (slice + 1) * a.cps * 64 ? a.M : (slice + 1) * a.cps * 64;
     for (int64_t p0 = slice * a.cps * 64; p0 < p_end; p0 += 64) {
@@ -111,8 +91,8 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
         for (int j = 0; j < DPMAX; ++j) xc[j] = (j < Dc && have) ? xp[j * a.cs] : 0.0;
         const double lwv = chunk(t, have);
         const double wv = finite_d(lwv) ? exp_fast(fmax(lwv, -800.0)) : 0.0;
-        typename GlmDispModel<64, 1>::TauConst kc{};
-        if constexpr (DISP) kc = dm.tau_const(have ? xp[Dc * a.cs] : 0.0);
+        TauConst kc{};
+        if constexpr (DISP) kc = glm_tau_const(nb, have ? xp[Dc * a.cs] : 0.0);
         const int cnt = p_end - p0 < 64 ? (int)(p_end - p0) : 64;
 #pragma unroll 1
         for (int q = 0; q < cnt; ++q) {
@@ -130,7 +110,7 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
             if constexpr (OW) eta += off;
             double term, mean;
             if constexpr (DISP) {
-                typename GlmDispModel<64, 1>::TauConst k;
+                TauConst k;
                 k.tau = group_read<64>(kc.tau, q);
                 k.phi = group_read<64>(kc.phi, q);
                 k.iphi = group_read<64>(kc.iphi, q);
@@ -140,11 +120,11 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
                 k.big = (fl & 1) != 0;
                 k.bad = (fl & 2) != 0;
                 double d, gt;
-                dm.obs(k, eta, y, lgy, term, d, gt);
+                glm_disp_obs(nb, k, eta, y, lgy, term, d, gt);
                 term = k.bad ? -kInf : term;               // the dispersion coordinate is out of range: every term
-                mean = dm.nb ? exp_fast(fmin(eta, kLogDblMax)) : eta;
+                mean = nb ? exp_fast(fmin(eta, kLogDblMax)) : eta;
             } else {
-                pw_glm_obs(poisson, eta, y, lgy, term, mean);
+                glm_canon_obs(poisson, eta, y, lgy, term, mean);
             }
             f(p0 + q, lwq, group_read<64>(wv, q), term, mean);
         }

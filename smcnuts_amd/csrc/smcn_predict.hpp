@@ -176,9 +176,7 @@ __device__ __forceinline__ void pr_walk_hier_alpha(const PrArgs& a, int64_t tile
     const d2 yl = rowp[DP >> 1];
     const double y = yl.x, lgy = yl.y;
     const int gi = (int)rowp[(DP >> 1) + 1].x;     // (0 on the pad rows)
-    GlmDispModel<64, 1> dm;                        // (tau_const() and obs() read `nb` only)
-    dm.nb = a.fam == 3;
-    const bool poisson = a.fam == 1;
+    const bool poisson = a.fam == 1, nb = a.fam == 3;
 
     const int64_t p_end = a.M < (slice + 1) * a.cps * 64 ? a.M : (slice + 1) * a.cps * 64;
     for (int64_t p0 = slice * a.cps * 64; p0 < p_end; p0 += 64) {
@@ -192,8 +190,8 @@ __device__ __forceinline__ void pr_walk_hier_alpha(const PrArgs& a, int64_t tile
         for (int j = 0; j < J; ++j) zb[pr_slot(j, lane)] = have ? xp[(Dc + j) * a.cs] : 0.0;
         const double tauv = exp_fast(have ? xp[(Dc + J) * a.cs] : 0.0);      // GlmHierModel: tau = e^lt
         const double ld = (DISP && have) ? xp[(Dc + J + 1) * a.cs] : 0.0;
-        typename GlmDispModel<64, 1>::TauConst kc{};
-        if constexpr (DISP) kc = dm.tau_const(ld);
+        TauConst kc{};
+        if constexpr (DISP) kc = glm_tau_const(nb, ld);
         const double vcv = pr_var_const(a.fam, ld);
         const int flv = (kc.big ? 1 : 0) | (kc.bad ? 2 : 0) | (tauv * tauv < kInf ? 0 : 4);   // (4: e^(2 lt) overflows)
         const double lwv = chunk(t, have);
@@ -219,7 +217,7 @@ __device__ __forceinline__ void pr_walk_hier_alpha(const PrArgs& a, int64_t tile
             const int fl = group_read_i<64>(flv, q);
             double term, mean;
             if constexpr (DISP) {
-                typename GlmDispModel<64, 1>::TauConst k;
+                TauConst k;
                 k.tau = group_read<64>(kc.tau, q);
                 k.phi = group_read<64>(kc.phi, q);
                 k.iphi = group_read<64>(kc.iphi, q);
@@ -228,10 +226,10 @@ __device__ __forceinline__ void pr_walk_hier_alpha(const PrArgs& a, int64_t tile
                 k.big = (fl & 1) != 0;
                 k.bad = (fl & 2) != 0;
                 double d, gt;
-                dm.obs(k, eta, y, lgy, term, d, gt);
-                mean = dm.nb ? (eta <= kLogDblMax ? exp_fast(eta) : kInf) : eta;
+                glm_disp_obs(nb, k, eta, y, lgy, term, d, gt);
+                mean = nb ? (eta <= kLogDblMax ? exp_fast(eta) : kInf) : eta;
             } else {
-                pw_glm_obs(poisson, eta, y, lgy, term, mean);
+                glm_canon_obs(poisson, eta, y, lgy, term, mean);
             }
             term = (fl & 6) ? -kInf : term;                // the particle's llik is -inf: every term
             f(p0 + q, lwq, group_read<64>(wv, q), term, mean, pr_var(a.fam, mean, group_read<64>(vcv, q)));
@@ -300,8 +298,6 @@ __device__ __forceinline__ void pr_walk_ord(const PrArgs& a, int64_t tile, int64
     }
     const int y = (int)rowp[DP >> 1].x;
     const bool mid = y >= 1 && y < Km1;
-    GlmOrdModel<64, 1> om;                         // (obs() reads Km1 only)
-    om.Km1 = Km1;
 
     const int64_t p_end = a.M < (slice + 1) * a.cps * 64 ? a.M : (slice + 1) * a.cps * 64;
     for (int64_t p0 = slice * a.cps * 64; p0 < p_end; p0 += 64) {
@@ -348,7 +344,7 @@ __device__ __forceinline__ void pr_walk_ord(const PrArgs& a, int64_t tile, int64
             const double lo = cut[pr_slot(y >= 1 ? y - 1 : 0, q)];
             const double hi = cut[pr_slot(y < Km1 ? y : Km1 - 1, q)];
             double term, de, glo, ghi;
-            om.obs(eta, y, lo, hi, term, de, glo, ghi);
+            glm_ord_obs(Km1, eta, y, lo, hi, term, de, glo, ghi);
             term += mid ? lmid[pr_slot(mid ? y : 1, q)] : 0.0;
             term = group_read_i<64>(badv, q) ? -kInf : term;
             double em = 0.0, P[KP];

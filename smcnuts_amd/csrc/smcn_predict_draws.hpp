@@ -114,7 +114,7 @@ __device__ __forceinline__ double draw_gamma(double phi, const DrawKey& key) {
 }
 
 // What the sampler takes from the dispersion coordinate: sigma = e^tau (normal), phi = e^tau (NB2); `bad` under the
-// density's own range rules (GlmDispModel::tau_const) or once e^tau is not finite
+// density's own range rules (glm_tau_const) or once e^tau is not finite
 __device__ __forceinline__ double draw_disp(int fam, double tau, int& bad) {
     const bool ok = fam == 2 ? (-2.0 * tau <= kLogDblMax && tau <= kLogDblMax)
                              : (fam == 3 ? (tau <= kLogDblMax && tau >= kLogDblMinNormal) : true);

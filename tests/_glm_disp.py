@@ -9,7 +9,7 @@ Non-finite (-inf): e^-2tau overflows (normal); e^eta or e^tau overflows, or e^ta
 
 `GLMDispNumpy` is the model as a plain Python object with the reference's StanModel surface (.dim, .logpdf(x, phi),
 .logpdfgrad(x, phi), .constrain(x)): it runs through HostTarget and oracle/pynuts.PyNUTS.  Its NB terms take the
-device's algorithm (smcn_models.hpp GlmDispModel): for phi >= 10 lgamma(y + phi) - lgamma(phi) - y tau and
+device's algorithm (smcn_glm_family.hpp glm_disp_obs): for phi >= 10 lgamma(y + phi) - lgamma(phi) - y tau and
 psi(y + phi) - psi(phi) from Stirling's series and log1p(y / phi), below from a shift up to >= 10 and the same series.
 `mp_obs` is the 40-digit mpmath value of one observation's term and derivatives; `exact_parts` / `device_bounds`
 are the fsum reference and the worst-case error bound of the device's evaluation, as tests/_glm.py has them.

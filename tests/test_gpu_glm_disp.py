@@ -1,5 +1,5 @@
 """The GLM target's dispersion families on the device (GLMTarget family "normal" / "neg_binomial_2_log";
-GlmDispModel) against exact references and against the same model evaluated on the host (tests/_glm_disp.py's numpy
+GlmModel with DISP) against exact references and against the same model evaluated on the host (tests/_glm_disp.py's numpy
 density through HostTarget / oracle/pynuts.PyNUTS).
 
 Shapes: 8 lanes per particle for D <= 8, a whole wavefront for 9 <= D <= 64; observations in passes of 8 / chunks of
