@@ -15,8 +15,10 @@ import os
 import numpy as np
 
 from .. import _capi
+from .. import _checks
 from .. import covariance as _covariance
 from .. import summary as _summary
+from .._checks import GLM_DISPERSION, GLM_FAMILIES, GLM_MAX_DIM
 from ..predict import PredictMixin
 
 DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
@@ -91,9 +93,7 @@ class DeviceTarget:
         """summary.PosteriorSummary of the points x [M][D] (unconstrained) with log-weights logw (None: equal): weighted
         quantiles at `probs` (at most 16, each in (0, 1]) and, with `at` (a scalar, [T] or [Dc][T], T <= 16), the mass at
         or below each threshold, of every constrained coordinate -- constrained and selected on the device."""
-        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
-        if x2.ndim != 2 or x2.shape[1] != self.dim:
-            raise ValueError(f"{type(self).__name__}: x must be [{self.dim}] or [M, {self.dim}]")
+        x2 = _checks.points(type(self).__name__, x, self.dim)
         lw = _summary.check_logw(logw, x2.shape[0])
         probs, at = _summary.check_probs(probs), _summary.check_at(at, self.constrained_dim)
         return _summary.target_summary(self, self._context(x2.shape[0]), np.ascontiguousarray(x2), lw, probs, at)
@@ -102,9 +102,7 @@ class DeviceTarget:
         """covariance.PosteriorCovariance of the points x [M][D] (unconstrained) with log-weights logw (None: equal):
         weighted mean, covariance and correlation of the constrained coordinates -- constrained and summed on the device
         (one fp64 MFMA product) about the points' own weighted mean."""
-        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
-        if x2.ndim != 2 or x2.shape[1] != self.dim:
-            raise ValueError(f"{type(self).__name__}: x must be [{self.dim}] or [M, {self.dim}]")
+        x2 = _checks.points(type(self).__name__, x, self.dim)
         lw = _summary.check_logw(logw, x2.shape[0])
         return _covariance.target_covariance(self, self._context(x2.shape[0]), np.ascontiguousarray(x2), lw)
 
@@ -179,9 +177,7 @@ class HostTarget:
 
     def summary(self, x, logw=None, probs=_summary.DEFAULT_PROBS, at=None):
         """DeviceTarget.summary with the wrapped model's own constrain() on the host and the selection on the device."""
-        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
-        if x2.ndim != 2 or x2.shape[1] != self.dim:
-            raise ValueError(f"HostTarget: x must be [{self.dim}] or [M, {self.dim}]")
+        x2 = _checks.points("HostTarget", x, self.dim)
         lw = _summary.check_logw(logw, x2.shape[0])
         probs, at = _summary.check_probs(probs), _summary.check_at(at, self.constrained_dim)
         v = np.ascontiguousarray(np.atleast_2d(self.constrain(x2)), dtype=np.float64)
@@ -194,9 +190,7 @@ class HostTarget:
 
     def covariance(self, x, logw=None):
         """DeviceTarget.covariance with the wrapped model's own constrain() on the host and the sums on the device."""
-        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
-        if x2.ndim != 2 or x2.shape[1] != self.dim:
-            raise ValueError(f"HostTarget: x must be [{self.dim}] or [M, {self.dim}]")
+        x2 = _checks.points("HostTarget", x, self.dim)
         lw = _summary.check_logw(logw, x2.shape[0])
         v = np.ascontiguousarray(np.atleast_2d(self.constrain(x2)), dtype=np.float64)
         if v.shape != (x2.shape[0], self.constrained_dim):
@@ -282,22 +276,12 @@ class PRMwCDModel(DeviceTarget):
         self.two_phase_default = (9, True, 8) if (96 < int(d["N"]) <= 100 and int(d["Clength"]) == 11 and float(d["q"]) == 0.5) else None
 
 
-GLM_FAMILIES = ("bernoulli_logit", "poisson_log", "normal", "neg_binomial_2_log")
-GLM_DISPERSION = {"normal": "sigma", "neg_binomial_2_log": "phi"}    # the families with a sampled scale, and its name
-GLM_MAX_DIM = 64
 WGLM_MAX_DIM = 256                         # WideGLMTarget: GLM_MAX_DIM < D <= this
-_NO_PRIOR = object()
+_NO_PRIOR = _checks.NO_PRIOR
 
 
-def _row_vector(who, name, v, n, what):
-    """offset / weights / exposure as a float vector of the n observations."""
-    try:
-        a = np.asarray(v, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: {name} must be numeric") from None
-    if a.ndim != 1 or a.shape[0] != n:
-        raise ValueError(f"{who}: {name} must be a vector of {what}")
-    return a
+def _coefficient_names(ic, p):
+    return (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)]
 
 
 def _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior, offset=None, weights=None):
@@ -305,71 +289,33 @@ def _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior,
     attributes and the SMCN_MODEL_GLM data block -- with `offset` or `weights` (GLMTarget only), SMCN_MODEL_OGLM's.
     `limit(what, D)` raises where the class does not cover D."""
     who = type(self).__name__
-    if family not in GLM_FAMILIES:
-        raise ValueError(f"{who}: family must be one of {GLM_FAMILIES}, not {family!r}")
-    disp = family in GLM_DISPERSION
-    if not disp and dispersion_prior is not _NO_PRIOR:
-        raise ValueError(f"{who}: {family} has no dispersion parameter; dispersion_prior is for "
-                         f"{tuple(GLM_DISPERSION)}")
-    if disp:
-        m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
-        try:
-            m_tau, s_tau = (float(v) for v in m_s)
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: dispersion_prior must be a pair (m, s)") from None
-        if not math.isfinite(m_tau):
-            raise ValueError(f"{who}: dispersion_prior's m must be finite")
-        if not (math.isfinite(s_tau) and s_tau > 0.0):
-            raise ValueError(f"{who}: dispersion_prior's s must be finite and > 0")
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim == 1:
-        X = X.reshape(-1, 1)
-    if X.ndim != 2:
-        raise ValueError(f"{who}: X must be an (n, p) matrix")
+    _checks.family(who, family)
+    tau_prior = _checks.dispersion_prior(who, family, dispersion_prior)
+    disp = tau_prior is not None
+    X = _checks.design(who, X)
     n, p = X.shape
-    y = np.asarray(y, dtype=np.float64)
-    if y.ndim != 1 or y.shape[0] != n:
-        raise ValueError(f"{who}: y must be a vector of the n = {n} observations X has rows for")
-    if n < 1:
-        raise ValueError(f"{who}: at least one observation")
+    y = _checks.response(who, y, n)            # before the rows are counted: the other targets count first
+    _checks.some_rows(who, n)
     ic = 1 if intercept else 0
     Dc = p + ic
     D = Dc + (1 if disp else 0)
     if Dc < 1:
         raise ValueError(f"{who}: no coefficients (p = 0 without an intercept)")
     limit(f"D = {D} coefficients" if not disp else f"D = {D} coordinates ({Dc} coefficients and tau)", D)
-    if not np.all(np.isfinite(X)):
-        raise ValueError(f"{who}: X must be finite")
-    if family == "bernoulli_logit":
-        if not np.all((y == 0.0) | (y == 1.0)):
-            raise ValueError(f"{who}: bernoulli_logit needs y in {{0, 1}}")
-    elif family == "poisson_log":
-        if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
-            raise ValueError(f"{who}: poisson_log needs y in {{0, 1, 2, ...}}")
-    elif family == "normal":
-        if not np.all(np.isfinite(y)):
-            raise ValueError(f"{who}: normal needs finite y")
-    elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
-        raise ValueError(f"{who}: neg_binomial_2_log needs y in {{0, 1, 2, ..., 2^53}}")
-    s = np.asarray(prior_sd, dtype=np.float64)
-    if s.ndim == 0:
-        s = np.full(Dc, float(s))
-    if s.shape != (Dc,):
-        raise ValueError(f"{who}: prior_sd must be a scalar or one value per coefficient ({Dc})"
-                         if disp else f"{who}: prior_sd must be a scalar or one value per coefficient (D = {D})")
-    if not np.all(np.isfinite(s) & (s > 0.0)):
-        raise ValueError(f"{who}: prior_sd must be finite and > 0")
+    _checks.finite(who, "X", X)
+    _checks.family_response(who, family, y)
+    s = _checks.prior_sds(who, "prior_sd", prior_sd, (Dc,),
+                          f"a scalar or one value per coefficient ({Dc})" if disp
+                          else f"a scalar or one value per coefficient (D = {D})")
     self.family, self.intercept = family, bool(intercept)
     self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
-    self.dispersion_prior = (m_tau, s_tau) if disp else None
+    self.dispersion_prior = tau_prior
     self.offset = self.weights = None
     if offset is not None:
-        o = _row_vector(who, "offset", offset, n, f"the n = {n} observations' offsets")
-        if not np.all(np.isfinite(o)):
-            raise ValueError(f"{who}: offset must be finite")
-        self.offset = o.copy()
+        o = _checks.row_vector(who, "offset", offset, n, f"the n = {n} observations' offsets")
+        self.offset = _checks.finite(who, "offset", o).copy()
     if weights is not None:
-        w = _row_vector(who, "weights", weights, n, f"the n = {n} observations' weights")
+        w = _checks.row_vector(who, "weights", weights, n, f"the n = {n} observations' weights")
         if not np.all(np.isfinite(w) & (w >= 0.0)):
             raise ValueError(f"{who}: weights must be finite and >= 0")
         if not np.any(w > 0.0):
@@ -380,9 +326,9 @@ def _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior,
     if flags:
         self.model_id = _capi.MODEL_OGLM
         head.append(float(flags))
-    data = np.concatenate([head, s, [m_tau, s_tau] if disp else [], y,
+    data = np.concatenate([head, s, tau_prior or [], y,
                            self.offset if flags & 1 else [], self.weights if flags & 2 else [], X.reshape(-1)])
-    names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)]
+    names = _coefficient_names(ic, p)
     if disp:
         names.append(GLM_DISPERSION[family])
     DeviceTarget.__init__(self, data, D, names)
@@ -434,10 +380,7 @@ class GLMTarget(PredictMixin, DeviceTarget):
 
     def _points(self, x):
         self._refuse_weighted()
-        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
-        if x2.ndim != 2 or x2.shape[1] != self.dim:
-            raise ValueError(f"GLMTarget: x must be [{self.dim}] or [M, {self.dim}]")
-        return x2
+        return _checks.points("GLMTarget", x, self.dim)      # the literal name, for a subclass as well
 
     def pointwise_loglik(self, x):
         """ll[p, i] = log p(y_i | x_p): [n] for a 1-D x, [M, n] for 2-D (sum over i: logpdf_parts(x)[1]).  The matrix is
@@ -487,9 +430,7 @@ class WideGLMTarget(DeviceTarget):
             if D <= GLM_MAX_DIM:
                 raise ValueError(f"WideGLMTarget: {what}; the wide functor covers {GLM_MAX_DIM} < D <= {WGLM_MAX_DIM}. "
                                  f"D <= {GLM_MAX_DIM} is GLMTarget's.")
-            if D > WGLM_MAX_DIM:
-                raise ValueError(f"WideGLMTarget: {what}; the device functor covers D <= {WGLM_MAX_DIM}. "
-                                 "Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
+            _checks.dim_limit("WideGLMTarget", D, what, WGLM_MAX_DIM)
         _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior)
 
 
@@ -509,91 +450,37 @@ class HierarchicalGLM(PredictMixin, DeviceTarget):
 
     def __init__(self, X, y, groups, family="bernoulli_logit", prior_sd=2.5, group_sd_prior=1.0, intercept=True,
                  dispersion_prior=_NO_PRIOR, n_groups=None):
-        if family not in GLM_FAMILIES:
-            raise ValueError(f"HierarchicalGLM: family must be one of {GLM_FAMILIES}, not {family!r}")
-        disp = family in GLM_DISPERSION
-        if not disp and dispersion_prior is not _NO_PRIOR:
-            raise ValueError(f"HierarchicalGLM: {family} has no dispersion parameter; dispersion_prior is for "
-                             f"{tuple(GLM_DISPERSION)}")
-        if disp:
-            m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
-            try:
-                m_d, s_d = (float(v) for v in m_s)
-            except (TypeError, ValueError):
-                raise ValueError("HierarchicalGLM: dispersion_prior must be a pair (m, s)") from None
-            if not math.isfinite(m_d):
-                raise ValueError("HierarchicalGLM: dispersion_prior's m must be finite")
-            if not (math.isfinite(s_d) and s_d > 0.0):
-                raise ValueError("HierarchicalGLM: dispersion_prior's s must be finite and > 0")
-        try:
+        who = "HierarchicalGLM"
+        _checks.family(who, family)
+        ld_prior = _checks.dispersion_prior(who, family, dispersion_prior)
+        disp = ld_prior is not None
+        try:                                   # one number here; MultilevelGLM's is a vector, one per term
             s_tau = float(group_sd_prior)
         except (TypeError, ValueError):
-            raise ValueError("HierarchicalGLM: group_sd_prior must be a number") from None
+            raise ValueError(f"{who}: group_sd_prior must be a number") from None
         if not (math.isfinite(s_tau) and s_tau > 0.0):
-            raise ValueError("HierarchicalGLM: group_sd_prior must be finite and > 0")
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X.reshape(-1, 1)
-        if X.ndim != 2:
-            raise ValueError("HierarchicalGLM: X must be an (n, p) matrix")
+            raise ValueError(f"{who}: group_sd_prior must be finite and > 0")
+        X = _checks.design(who, X)
         n, p = X.shape
-        if n < 1:
-            raise ValueError("HierarchicalGLM: at least one observation")
-        y = np.asarray(y, dtype=np.float64)
-        if y.ndim != 1 or y.shape[0] != n:
-            raise ValueError(f"HierarchicalGLM: y must be a vector of the n = {n} observations X has rows for")
-        g = np.asarray(groups)
-        if g.ndim != 1 or g.shape[0] != n:
-            raise ValueError(f"HierarchicalGLM: groups must be a vector of the n = {n} observations X has rows for")
-        if g.dtype == bool or not (np.issubdtype(g.dtype, np.integer) or np.issubdtype(g.dtype, np.floating)):
-            raise ValueError("HierarchicalGLM: groups must be integers")
-        gf = g.astype(np.float64)
-        if not np.all(np.isfinite(gf) & (gf == np.floor(gf))):
-            raise ValueError("HierarchicalGLM: groups must be integers")
-        if np.any(gf < 0):
-            raise ValueError("HierarchicalGLM: groups must be >= 0")
-        J = int(gf.max()) + 1 if n_groups is None else n_groups
-        if isinstance(J, bool) or not isinstance(J, (int, np.integer)) or J < 1:
-            raise ValueError("HierarchicalGLM: n_groups must be an integer >= 1")
-        J = int(J)
-        if gf.max() >= J:
-            raise ValueError(f"HierarchicalGLM: groups must be in 0..n_groups - 1 = {J - 1}")
+        _checks.some_rows(who, n)
+        y = _checks.response(who, y, n)
+        gf = _checks.index_vector(who, groups, n, "groups")
+        J = _checks.n_groups(who, gf, n_groups)
         ic = 1 if intercept else 0
         Dc = p + ic
         D = Dc + J + 1 + (1 if disp else 0)
-        if D > GLM_MAX_DIM:
-            raise ValueError(f"HierarchicalGLM: D = {D} coordinates ({Dc} coefficients, {J} groups, tau"
-                             f"{', ' + GLM_DISPERSION[family] if disp else ''}); the device functor covers "
-                             f"D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget "
-                             "instead.")
-        if not np.all(np.isfinite(X)):
-            raise ValueError("HierarchicalGLM: X must be finite")
-        if family == "bernoulli_logit":
-            if not np.all((y == 0.0) | (y == 1.0)):
-                raise ValueError("HierarchicalGLM: bernoulli_logit needs y in {0, 1}")
-        elif family == "poisson_log":
-            if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
-                raise ValueError("HierarchicalGLM: poisson_log needs y in {0, 1, 2, ...}")
-        elif family == "normal":
-            if not np.all(np.isfinite(y)):
-                raise ValueError("HierarchicalGLM: normal needs finite y")
-        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
-            raise ValueError("HierarchicalGLM: neg_binomial_2_log needs y in {0, 1, 2, ..., 2^53}")
-        s = np.asarray(prior_sd, dtype=np.float64)
-        if s.ndim == 0:
-            s = np.full(Dc, float(s))
-        if s.shape != (Dc,):
-            raise ValueError(f"HierarchicalGLM: prior_sd must be a scalar or one value per coefficient ({Dc})")
-        if not np.all(np.isfinite(s) & (s > 0.0)):
-            raise ValueError("HierarchicalGLM: prior_sd must be finite and > 0")
+        _checks.dim_limit(who, D, f"D = {D} coordinates ({Dc} coefficients, {J} groups, tau"
+                                  f"{', ' + GLM_DISPERSION[family] if disp else ''})")
+        _checks.finite(who, "X", X)
+        _checks.family_response(who, family, y)
+        s = _checks.prior_sds(who, "prior_sd", prior_sd, (Dc,), f"a scalar or one value per coefficient ({Dc})")
         self.family, self.intercept, self.n_groups = family, bool(intercept), J
         self.X, self.y, self.groups, self.prior_sd = X.copy(), y.copy(), gf.astype(np.int64), s.copy()
         self.group_sd_prior = s_tau
-        self.dispersion_prior = (m_d, s_d) if disp else None
+        self.dispersion_prior = ld_prior
         head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic), float(J)]
-        data = np.concatenate([head, s, [s_tau], [m_d, s_d] if disp else [], y, gf, X.reshape(-1)])
-        names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)] \
-            + [f"alpha.{j + 1}" for j in range(J)] + ["tau"]
+        data = np.concatenate([head, s, [s_tau], ld_prior or [], y, gf, X.reshape(-1)])
+        names = _coefficient_names(ic, p) + [f"alpha.{j + 1}" for j in range(J)] + ["tau"]
         if disp:
             names.append(GLM_DISPERSION[family])
         super().__init__(data, D, names)
@@ -622,123 +509,61 @@ class MultilevelGLM(DeviceTarget):
 
     def __init__(self, X, y, terms, family="bernoulli_logit", prior_sd=2.5, group_sd_prior=1.0, intercept=True,
                  dispersion_prior=_NO_PRIOR):
-        if family not in GLM_FAMILIES:
-            raise ValueError(f"MultilevelGLM: family must be one of {GLM_FAMILIES}, not {family!r}")
-        disp = family in GLM_DISPERSION
-        if not disp and dispersion_prior is not _NO_PRIOR:
-            raise ValueError(f"MultilevelGLM: {family} has no dispersion parameter; dispersion_prior is for "
-                             f"{tuple(GLM_DISPERSION)}")
-        if disp:
-            m_s = (0.0, 2.5) if dispersion_prior is _NO_PRIOR else dispersion_prior
-            try:
-                m_d, s_d = (float(v) for v in m_s)
-            except (TypeError, ValueError):
-                raise ValueError("MultilevelGLM: dispersion_prior must be a pair (m, s)") from None
-            if not math.isfinite(m_d):
-                raise ValueError("MultilevelGLM: dispersion_prior's m must be finite")
-            if not (math.isfinite(s_d) and s_d > 0.0):
-                raise ValueError("MultilevelGLM: dispersion_prior's s must be finite and > 0")
+        who = "MultilevelGLM"
+        _checks.family(who, family)
+        ld_prior = _checks.dispersion_prior(who, family, dispersion_prior)
+        disp = ld_prior is not None
         try:
             terms = [tuple(t) for t in terms]
         except TypeError:
-            raise ValueError("MultilevelGLM: terms must be a sequence of (groups,), (groups, z) or (groups, z, n_groups)") \
+            raise ValueError(f"{who}: terms must be a sequence of (groups,), (groups, z) or (groups, z, n_groups)") \
                 from None
         R = len(terms)
         if not 1 <= R <= ML_MAX_TERMS:
-            raise ValueError(f"MultilevelGLM: terms must hold 1 to {ML_MAX_TERMS} varying terms, not {R}")
+            raise ValueError(f"{who}: terms must hold 1 to {ML_MAX_TERMS} varying terms, not {R}")
         if any(not 1 <= len(t) <= 3 for t in terms):
-            raise ValueError("MultilevelGLM: every term must be (groups,), (groups, z) or (groups, z, n_groups)")
-        try:
+            raise ValueError(f"{who}: every term must be (groups,), (groups, z) or (groups, z, n_groups)")
+        try:                                   # one per term here; HierarchicalGLM's is one number
             s_tau = np.asarray(group_sd_prior, dtype=np.float64)
         except (TypeError, ValueError):
-            raise ValueError("MultilevelGLM: group_sd_prior must be a number or one per term") from None
-        if s_tau.ndim == 0:
-            s_tau = np.full(R, float(s_tau))
-        if s_tau.shape != (R,):
-            raise ValueError(f"MultilevelGLM: group_sd_prior must be a scalar or one value per term ({R})")
-        if not np.all(np.isfinite(s_tau) & (s_tau > 0.0)):
-            raise ValueError("MultilevelGLM: group_sd_prior must be finite and > 0")
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X.reshape(-1, 1)
-        if X.ndim != 2:
-            raise ValueError("MultilevelGLM: X must be an (n, p) matrix")
+            raise ValueError(f"{who}: group_sd_prior must be a number or one per term") from None
+        s_tau = _checks.prior_sds(who, "group_sd_prior", s_tau, (R,), f"a scalar or one value per term ({R})")
+        X = _checks.design(who, X)
         n, p = X.shape
-        if n < 1:
-            raise ValueError("MultilevelGLM: at least one observation")
-        y = np.asarray(y, dtype=np.float64)
-        if y.ndim != 1 or y.shape[0] != n:
-            raise ValueError(f"MultilevelGLM: y must be a vector of the n = {n} observations X has rows for")
+        _checks.some_rows(who, n)
+        y = _checks.response(who, y, n)
         gs, zs, Js = [], [], []
         for r, t in enumerate(terms):
-            g = np.asarray(t[0])
-            if g.ndim != 1 or g.shape[0] != n:
-                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be a vector of the n = {n} observations X has "
-                                 "rows for")
-            if g.dtype == bool or not (np.issubdtype(g.dtype, np.integer) or np.issubdtype(g.dtype, np.floating)):
-                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be integers")
-            gf = g.astype(np.float64)
-            if not np.all(np.isfinite(gf) & (gf == np.floor(gf))):
-                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be integers")
-            if np.any(gf < 0):
-                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be >= 0")
+            pre = f"term {r + 1}: "
+            gf = _checks.index_vector(who, t[0], n, pre + "groups")
             if len(t) < 2 or t[1] is None:
                 z = np.ones(n)
             else:
                 try:
                     z = np.asarray(t[1], dtype=np.float64)
                 except (TypeError, ValueError):
-                    raise ValueError(f"MultilevelGLM: term {r + 1}: z must be numbers") from None
-                if z.ndim != 1 or z.shape[0] != n:
-                    raise ValueError(f"MultilevelGLM: term {r + 1}: z must be a vector of the n = {n} observations X has "
-                                     "rows for")
-                if not np.all(np.isfinite(z)):
-                    raise ValueError(f"MultilevelGLM: term {r + 1}: z must be finite")
-            J = int(gf.max()) + 1 if len(t) < 3 or t[2] is None else t[2]
-            if isinstance(J, bool) or not isinstance(J, (int, np.integer)) or J < 1:
-                raise ValueError(f"MultilevelGLM: term {r + 1}: n_groups must be an integer >= 1")
-            J = int(J)
-            if gf.max() >= J:
-                raise ValueError(f"MultilevelGLM: term {r + 1}: groups must be in 0..n_groups - 1 = {J - 1}")
+                    raise ValueError(f"{who}: {pre}z must be numbers") from None
+                _checks.finite(who, pre + "z", _checks.per_row(who, pre + "z", z, n))
+            J = _checks.n_groups(who, gf, t[2] if len(t) == 3 else None, pre)
             gs.append(gf), zs.append(z.copy()), Js.append(J)
         ic = 1 if intercept else 0
         Dc = p + ic
         D = Dc + sum(Js) + R + (1 if disp else 0)
-        if D > GLM_MAX_DIM:
-            raise ValueError(f"MultilevelGLM: D = {D} coordinates ({Dc} coefficients, {' + '.join(map(str, Js))} levels, "
-                             f"{R} tau{', ' + GLM_DISPERSION[family] if disp else ''}); the device functor covers "
-                             f"D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget "
-                             "instead.")
-        if not np.all(np.isfinite(X)):
-            raise ValueError("MultilevelGLM: X must be finite")
-        if family == "bernoulli_logit":
-            if not np.all((y == 0.0) | (y == 1.0)):
-                raise ValueError("MultilevelGLM: bernoulli_logit needs y in {0, 1}")
-        elif family == "poisson_log":
-            if not np.all(np.isfinite(y) & (y >= 0.0) & (y == np.floor(y))):
-                raise ValueError("MultilevelGLM: poisson_log needs y in {0, 1, 2, ...}")
-        elif family == "normal":
-            if not np.all(np.isfinite(y)):
-                raise ValueError("MultilevelGLM: normal needs finite y")
-        elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
-            raise ValueError("MultilevelGLM: neg_binomial_2_log needs y in {0, 1, 2, ..., 2^53}")
-        s = np.asarray(prior_sd, dtype=np.float64)
-        if s.ndim == 0:
-            s = np.full(Dc, float(s))
-        if s.shape != (Dc,):
-            raise ValueError(f"MultilevelGLM: prior_sd must be a scalar or one value per coefficient ({Dc})")
-        if not np.all(np.isfinite(s) & (s > 0.0)):
-            raise ValueError("MultilevelGLM: prior_sd must be finite and > 0")
+        _checks.dim_limit(who, D, f"D = {D} coordinates ({Dc} coefficients, {' + '.join(map(str, Js))} levels, "
+                                  f"{R} tau{', ' + GLM_DISPERSION[family] if disp else ''})")
+        _checks.finite(who, "X", X)
+        _checks.family_response(who, family, y)
+        s = _checks.prior_sds(who, "prior_sd", prior_sd, (Dc,), f"a scalar or one value per coefficient ({Dc})")
         self.family, self.intercept, self.n_groups = family, bool(intercept), tuple(Js)
         self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
         self.term_groups, self.term_z = [g.astype(np.int64) for g in gs], zs
         self.group_sd_prior = s_tau.copy()
-        self.dispersion_prior = (m_d, s_d) if disp else None
+        self.dispersion_prior = ld_prior
         head = [float(GLM_FAMILIES.index(family)), float(n), float(p), float(ic), float(R)] \
             + [float(J) for J in Js] + [0.0] * (ML_MAX_TERMS - R)
         gz = [v for r in range(R) for v in (gs[r], zs[r])]
-        data = np.concatenate([head, s, s_tau, [m_d, s_d] if disp else [], y] + gz + [X.reshape(-1)])
-        names = (["Intercept"] if ic else []) + [f"beta.{j + 1}" for j in range(p)] \
+        data = np.concatenate([head, s, s_tau, ld_prior or [], y] + gz + [X.reshape(-1)])
+        names = _coefficient_names(ic, p) \
             + [f"alpha.{r + 1}.{j + 1}" for r in range(R) for j in range(Js[r])] + [f"tau.{r + 1}" for r in range(R)]
         if disp:
             names.append(GLM_DISPERSION[family])
@@ -763,56 +588,28 @@ class CategoricalRegression(PredictMixin, DeviceTarget):
     model_id = _capi.MODEL_CATEGORICAL
 
     def __init__(self, X, y, n_classes=None, prior_sd=2.5, intercept=True):
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X.reshape(-1, 1)
-        if X.ndim != 2:
-            raise ValueError("CategoricalRegression: X must be an (n, p) matrix")
+        who = "CategoricalRegression"
+        X = _checks.design(who, X)
         n, p = X.shape
-        if n < 1:
-            raise ValueError("CategoricalRegression: at least one observation")
-        y = np.asarray(y)
-        if y.ndim != 1 or y.shape[0] != n:
-            raise ValueError(f"CategoricalRegression: y must be a vector of the n = {n} observations X has rows for")
-        if y.dtype == bool or not (np.issubdtype(y.dtype, np.integer) or np.issubdtype(y.dtype, np.floating)):
-            raise ValueError("CategoricalRegression: the labels y must be integers")
-        yf = y.astype(np.float64)
-        if not np.all(np.isfinite(yf) & (yf == np.floor(yf))):
-            raise ValueError("CategoricalRegression: the labels y must be integers")
-        if np.any(yf < 0):
-            raise ValueError("CategoricalRegression: the labels y must be >= 0")
-        K = int(yf.max()) + 1 if n_classes is None else n_classes
-        if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
-            raise ValueError("CategoricalRegression: n_classes must be an integer")
-        K = int(K)
-        if K < 2:
-            raise ValueError("CategoricalRegression: K = n_classes must be >= 2 (one class has no likelihood)")
+        _checks.some_rows(who, n)
+        yf = _checks.index_vector(who, y, n, "y", "the labels y")
+        K = _checks.n_classes(who, yf, n_classes)
         if K > CAT_MAX_CLASSES:
-            raise ValueError(f"CategoricalRegression: K = {K} classes; the device functor holds K <= {CAT_MAX_CLASSES}. "
+            raise ValueError(f"{who}: K = {K} classes; the device functor holds K <= {CAT_MAX_CLASSES}. "
                              "Wrap a model object with .dim / .logpdf / .logpdfgrad in HostTarget instead.")
-        if yf.max() >= K:
-            raise ValueError(f"CategoricalRegression: the labels y must be in 0..n_classes - 1 = {K - 1}")
+        _checks.below(who, "the labels y", yf, K, "n_classes")
         ic = 1 if intercept else 0
         Dc = p + ic
         if Dc < 1:
-            raise ValueError("CategoricalRegression: no coefficients (p = 0 without an intercept)")
+            raise ValueError(f"{who}: no coefficients (p = 0 without an intercept)")
         D = (K - 1) * Dc
-        if D > GLM_MAX_DIM:
-            raise ValueError(f"CategoricalRegression: D = (K - 1) Dc = {K - 1} x {Dc} = {D} coefficients; the device "
-                             f"functor covers D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad "
-                             "in HostTarget instead.")
-        if not np.all(np.isfinite(X)):
-            raise ValueError("CategoricalRegression: X must be finite")
+        _checks.dim_limit(who, D, f"D = (K - 1) Dc = {K - 1} x {Dc} = {D} coefficients")
+        _checks.finite(who, "X", X)
         s = np.asarray(prior_sd, dtype=np.float64)
-        if s.ndim == 0:
-            s = np.full((K - 1, Dc), float(s))
-        elif s.shape == (Dc,):
+        if s.shape == (Dc,):                   # one value per column, shared by the classes
             s = np.tile(s, (K - 1, 1))
-        if s.shape != (K - 1, Dc):
-            raise ValueError(f"CategoricalRegression: prior_sd must be a scalar, one value per column ({Dc}) or a "
-                             f"(K - 1, Dc) = ({K - 1}, {Dc}) array")
-        if not np.all(np.isfinite(s) & (s > 0.0)):
-            raise ValueError("CategoricalRegression: prior_sd must be finite and > 0")
+        s = _checks.prior_sds(who, "prior_sd", s, (K - 1, Dc), f"a scalar, one value per column ({Dc}) or a "
+                                                               f"(K - 1, Dc) = ({K - 1}, {Dc}) array")
         self.intercept, self.n_classes = bool(intercept), K
         self.X, self.y, self.prior_sd = X.copy(), yf.astype(np.int64), s.copy()
         data = np.concatenate([[float(K), float(n), float(p), float(ic)], s.reshape(-1), yf, X.reshape(-1)])
@@ -836,54 +633,19 @@ class OrdinalRegression(PredictMixin, DeviceTarget):
     model_id = _capi.MODEL_ORDINAL
 
     def __init__(self, X, y, n_classes=None, prior_sd=2.5, cutpoint_prior_sd=5.0):
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X.reshape(-1, 1)
-        if X.ndim != 2:
-            raise ValueError("OrdinalRegression: X must be an (n, p) matrix")
+        who = "OrdinalRegression"
+        X = _checks.design(who, X)
         n, p = X.shape
-        if n < 1:
-            raise ValueError("OrdinalRegression: at least one observation")
-        y = np.asarray(y)
-        if y.ndim != 1 or y.shape[0] != n:
-            raise ValueError(f"OrdinalRegression: y must be a vector of the n = {n} observations X has rows for")
-        if y.dtype == bool or not (np.issubdtype(y.dtype, np.integer) or np.issubdtype(y.dtype, np.floating)):
-            raise ValueError("OrdinalRegression: the labels y must be integers")
-        yf = y.astype(np.float64)
-        if not np.all(np.isfinite(yf) & (yf == np.floor(yf))):
-            raise ValueError("OrdinalRegression: the labels y must be integers")
-        if np.any(yf < 0):
-            raise ValueError("OrdinalRegression: the labels y must be >= 0")
-        K = int(yf.max()) + 1 if n_classes is None else n_classes
-        if isinstance(K, bool) or not isinstance(K, (int, np.integer)):
-            raise ValueError("OrdinalRegression: n_classes must be an integer")
-        K = int(K)
-        if K < 2:
-            raise ValueError("OrdinalRegression: K = n_classes must be >= 2 (one class has no likelihood)")
-        if yf.max() >= K:
-            raise ValueError(f"OrdinalRegression: the labels y must be in 0..n_classes - 1 = {K - 1}")
+        _checks.some_rows(who, n)
+        yf = _checks.index_vector(who, y, n, "y", "the labels y")
+        K = _checks.n_classes(who, yf, n_classes)
+        _checks.below(who, "the labels y", yf, K, "n_classes")
         D = p + K - 1
-        if D > GLM_MAX_DIM:
-            raise ValueError(f"OrdinalRegression: D = p + K - 1 = {p} + {K - 1} = {D} coordinates; the device functor "
-                             f"covers D <= {GLM_MAX_DIM}. Wrap a model object with .dim / .logpdf / .logpdfgrad in "
-                             "HostTarget instead.")
-        if not np.all(np.isfinite(X)):
-            raise ValueError("OrdinalRegression: X must be finite")
-        s = np.asarray(prior_sd, dtype=np.float64)
-        if s.ndim == 0:
-            s = np.full(p, float(s))
-        if s.shape != (p,):
-            raise ValueError(f"OrdinalRegression: prior_sd must be a scalar or one value per column ({p})")
-        if not np.all(np.isfinite(s) & (s > 0.0)):
-            raise ValueError("OrdinalRegression: prior_sd must be finite and > 0")
-        t = np.asarray(cutpoint_prior_sd, dtype=np.float64)
-        if t.ndim == 0:
-            t = np.full(K - 1, float(t))
-        if t.shape != (K - 1,):
-            raise ValueError(f"OrdinalRegression: cutpoint_prior_sd must be a scalar or one value per cutpoint "
-                             f"(K - 1 = {K - 1})")
-        if not np.all(np.isfinite(t) & (t > 0.0)):
-            raise ValueError("OrdinalRegression: cutpoint_prior_sd must be finite and > 0")
+        _checks.dim_limit(who, D, f"D = p + K - 1 = {p} + {K - 1} = {D} coordinates")
+        _checks.finite(who, "X", X)
+        s = _checks.prior_sds(who, "prior_sd", prior_sd, (p,), f"a scalar or one value per column ({p})")
+        t = _checks.prior_sds(who, "cutpoint_prior_sd", cutpoint_prior_sd, (K - 1,),
+                              f"a scalar or one value per cutpoint (K - 1 = {K - 1})")
         self.n_classes = K
         self.X, self.y, self.prior_sd, self.cutpoint_prior_sd = X.copy(), yf.astype(np.int64), s.copy(), t.copy()
         data = np.concatenate([[float(K), float(n), float(p)], s, t, yf, X.reshape(-1)])

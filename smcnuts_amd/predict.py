@@ -28,6 +28,7 @@ cutpoint, mu > 2^53, an attempt cap of a rejection sampler reached) is NaN and c
 import numpy as np
 
 from . import _capi
+from . import _checks
 from .criteria import _merge_lse, _se
 
 # columns of a partials block (row 0: header [mw, sw, sw2, cnt, 0 ..]; row 1 + i: new row i)
@@ -267,27 +268,29 @@ class PredictMixin:
         labels >= J name new groups; such rows carry group 0 in the block and (block, has_y, labels) is returned.
         A GLMTarget with offsets takes offset_new, one per new row; after a fit with weights the new rows carry weight 1."""
         name = type(self).__name__
+        who = f"{name}.predict"
         hier = self.model_id == _capi.MODEL_HGLM
         oglm = self.model_id == _capi.MODEL_OGLM
+        # not _checks.design: a vector is ONE ROW of a design with p > 1 columns, and m >= 1 belongs to the shape check
         X = np.asarray(X_new, dtype=np.float64)
         p = self.X.shape[1]
         if X.ndim == 1:
             X = X.reshape(-1, 1) if p == 1 else X.reshape(1, -1)
         if X.ndim != 2 or X.shape[0] < 1:
-            raise ValueError(f"{name}.predict: X_new must be an (m, p) matrix with m >= 1")
+            raise ValueError(f"{who}: X_new must be an (m, p) matrix with m >= 1")
         m = X.shape[0]
         if X.shape[1] != p:
-            raise ValueError(f"{name}.predict: X_new has {X.shape[1]} columns, the training design has {p}")
-        if not np.all(np.isfinite(X)):
-            raise ValueError(f"{name}.predict: X_new must be finite")
+            raise ValueError(f"{who}: X_new has {X.shape[1]} columns, the training design has {p}")
+        _checks.finite(who, "X_new", X)
         if hier:
             if groups_new is None:
-                raise ValueError(f"{name}.predict: groups_new is required (each new row's group, an existing group "
+                raise ValueError(f"{who}: groups_new is required (each new row's group, an existing group "
                                  f"0..{self.n_groups - 1}; predictions for new, unseen groups are not implemented)")
+            # not _checks.index_vector: shape and dtype are ONE check with one text here, and so are the value checks
             g = np.asarray(groups_new)
             if g.ndim != 1 or g.shape[0] != m or g.dtype == bool or \
                     not (np.issubdtype(g.dtype, np.integer) or np.issubdtype(g.dtype, np.floating)):
-                raise ValueError(f"{name}.predict: groups_new must be a vector of m = {m} integers")
+                raise ValueError(f"{who}: groups_new must be a vector of m = {m} integers")
             gf = g.astype(np.float64)
             if new_groups:
                 if not np.all(np.isfinite(gf) & (gf == np.floor(gf)) & (gf >= 0) & (gf < 2.0 ** 32)):
@@ -296,49 +299,40 @@ class PredictMixin:
                 labels = gf.astype(np.int64)
                 gf = np.where(gf < self.n_groups, gf, 0.0)
             elif not np.all(np.isfinite(gf) & (gf == np.floor(gf)) & (gf >= 0) & (gf < self.n_groups)):
-                raise ValueError(f"{name}.predict: groups_new must be existing groups 0..{self.n_groups - 1} "
+                raise ValueError(f"{who}: groups_new must be existing groups 0..{self.n_groups - 1} "
                                  "(predictions for new, unseen groups are not implemented)")
         elif groups_new is not None:
-            raise ValueError(f"{name}.predict: groups_new is for HierarchicalGLM only")
+            raise ValueError(f"{who}: groups_new is for HierarchicalGLM only")
         ow = []
         if oglm and self.offset is not None:
             if offset_new is None:
-                raise ValueError(f"{name}.predict: offset_new is required (each new row's offset: the model was fitted "
+                raise ValueError(f"{who}: offset_new is required (each new row's offset: the model was fitted "
                                  "with offsets)")
-            try:
-                o = np.asarray(offset_new, dtype=np.float64)
-            except (TypeError, ValueError):
-                raise ValueError(f"{name}.predict: offset_new must be numeric") from None
-            if o.ndim != 1 or o.shape[0] != m:
-                raise ValueError(f"{name}.predict: offset_new must be a vector of the m = {m} rows X_new has")
-            if not np.all(np.isfinite(o)):
-                raise ValueError(f"{name}.predict: offset_new must be finite")
-            ow.append(o)
+            o = _checks.row_vector(who, "offset_new", offset_new, m, f"the m = {m} rows X_new has")
+            ow.append(_checks.finite(who, "offset_new", o))
         elif offset_new is not None:
-            raise ValueError(f"{name}.predict: offset_new is for a GLMTarget fitted with offsets only")
+            raise ValueError(f"{who}: offset_new is for a GLMTarget fitted with offsets only")
         if oglm and self.weights is not None:
             ow.append(np.ones(m))
         has_y = y_new is not None
         if has_y:
+            # not _checks.row_vector: the shape is checked before the conversion to numbers
             y = np.asarray(y_new)
             if y.ndim != 1 or y.shape[0] != m:
-                raise ValueError(f"{name}.predict: y_new must be a vector of the m = {m} rows X_new has")
+                raise ValueError(f"{who}: y_new must be a vector of the m = {m} rows X_new has")
             try:
                 y = y.astype(np.float64)
             except (TypeError, ValueError):
-                raise ValueError(f"{name}.predict: y_new must be numeric") from None
+                raise ValueError(f"{who}: y_new must be numeric") from None
             kind, K = self._predict_kind()
-            if kind != "glm":
+            if kind != "glm":           # whole, >= 0 and < K in ONE check with one text, unlike the constructors' labels
                 if not np.all(np.isfinite(y) & (y == np.floor(y)) & (y >= 0) & (y < K)):
-                    raise ValueError(f"{name}.predict: the labels y_new must be integers in 0..{K - 1}")
-            elif self.family == "bernoulli_logit":
-                if not np.all((y == 0.0) | (y == 1.0)):
-                    raise ValueError(f"{name}.predict: bernoulli_logit needs y_new in {{0, 1}}")
-            elif self.family == "normal":
-                if not np.all(np.isfinite(y)):
-                    raise ValueError(f"{name}.predict: normal needs finite y_new")
+                    raise ValueError(f"{who}: the labels y_new must be integers in 0..{K - 1}")
+            elif self.family in ("bernoulli_logit", "normal"):
+                _checks.family_response(who, self.family, y, "y_new")
+            # the count families: unlike the constructors', poisson_log's y_new is bounded by 2^53 too, under one text
             elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
-                raise ValueError(f"{name}.predict: {self.family} needs y_new in {{0, 1, 2, ...}}")
+                raise ValueError(f"{who}: {self.family} needs y_new in {{0, 1, 2, ...}}")
         else:
             y = np.zeros(m)
         nh = 3 if self.model_id == _capi.MODEL_ORDINAL else (5 if hier or oglm else 4)
@@ -350,10 +344,7 @@ class PredictMixin:
         return block, has_y
 
     def _predict_points(self, x):
-        x2 = np.atleast_2d(np.asarray(x, dtype=np.float64))
-        if x2.ndim != 2 or x2.shape[1] != self.dim:
-            raise ValueError(f"{type(self).__name__}: x must be [{self.dim}] or [M, {self.dim}]")
-        return x2
+        return _checks.points(type(self).__name__, x, self.dim)
 
     _PR_CHUNK = 1 << 25          # doubles of the matrix the device holds at once (256 MB)
 
