@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/smcnuts_hip.h"
+#include "smcn_devbuf.hpp"
 #include "smcn_nuts.hpp"
 #include "smcn_nuts_wave.hpp"
 #include "smcn_nuts_fin.hpp"
@@ -64,6 +65,25 @@ constexpr int kTimerRing = 512;   // NUTS launches timed between two smcn_timers
 constexpr int64_t kDlChunk = 8;   // generations per staging pass of the history download
 }  // namespace
 
+// What a context owns on the device (smcn_devbuf.hpp): buffers from the per-device cache below, pinned host memory, events
+struct CacheMem { static int alloc(void** p, size_t bytes); static void free(void* p, bool synced); };
+struct PinnedMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes); }
+    static void free(void* p, bool) { (void)hipHostFree(p); }
+};
+struct HipEv {
+    using event = hipEvent_t;
+    using stream = hipStream_t;
+    static int create(event* e, bool timing) { return (int)(timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming)); }
+    static int record(event e, stream s) { return (int)hipEventRecord(e, s); }
+    static int wait(event e) { return (int)hipEventSynchronize(e); }
+    static int elapsed(float* ms, event from, event to) { return (int)hipEventElapsedTime(ms, from, to); }
+    static void destroy(event e) { (void)hipEventDestroy(e); }
+};
+template <class T>
+using Buf = DevBuf<T, CacheMem>;
+using Event = DevEvent<HipEv>;
+
 struct smcn_ctx {
     int device = 0;
     int64_t N = 0, base = 0;
@@ -78,51 +98,46 @@ struct smcn_ctx {
     RegLayout reg;              // the regression models: where things sit in mdata_h and in its image mdata (smcn_regdata.hpp)
 
     // device state, all fp64; vectors are [D][N]
-    double *mdata = nullptr, *x = nullptr, *x_new = nullptr, *x_tmp = nullptr, *r = nullptr, *r_new = nullptr;
-    double *logw = nullptr, *logw_new = nullptr, *wn = nullptr, *work = nullptr;
-    double *lpri0 = nullptr, *llik0 = nullptr, *lpri1 = nullptr, *llik1 = nullptr, *Lg = nullptr, *qv = nullptr;
-    double *scan_local = nullptr, *ttot = nullptr, *toff = nullptr, *part = nullptr, *scal = nullptr;
-    double* glk_buf = nullptr;          // device-side Gaussian L-kernel: mean, both moment sums, parameters (lazy)
-    double* glk_xchg = nullptr;         // ... over shards: [local row | world gathered rows] of moment sums
+    Buf<double> mdata, x, x_new, x_tmp, r, r_new;
+    Buf<double> logw, logw_new, wn, work;
+    Buf<double> lpri0, llik0, lpri1, llik1, Lg, qv;
+    Buf<double> scan_local, ttot, toff, part, scal;
+    Buf<double> glk_buf;          // device-side Gaussian L-kernel: mean, both moment sums, parameters (lazy)
+    Buf<double> glk_xchg;         // ... over shards: [local row | world gathered rows] of moment sums
     int glk_world = 0;
     // two-phase NUTS launches (smcn_set_nuts_cap): doublings of the first launch, records and list of the parked trees
     int nuts_jcap = 0, nuts_wide2 = 1;
-    double* nuts_resume = nullptr;
-    unsigned int* nuts_pend = nullptr;
-    unsigned int* nuts_mq = nullptr;    // list of the trees parked at the inner level of a launch (smcn_set_nuts_requeue)
-    double* nuts_mq_rec = nullptr;      // ... and their records ([N][128])
+    Buf<double> nuts_resume;
+    Buf<unsigned int> nuts_pend;
+    Buf<unsigned int> nuts_mq;    // list of the trees parked at the inner level of a launch (smcn_set_nuts_requeue)
+    Buf<double> nuts_mq_rec;      // ... and their records ([N][128])
     int nuts_mq_b = 0;                  // ... after this many doublings (0: no inner level)
     bool nuts_mq_used = false;          // the last proposal had an inner level (its hand-over count is checked behind the wait)
     bool nuts_mq_ok = false;            // set by the entry points that wait for the proposal and check that count (smcn_propose_nuts)
     int64_t nuts_parked = 0;            // trees the last launch parked
-    double* stage = nullptr;  // [N*D] host<->device staging, also [M*D] for target_eval
-    int64_t stage_len = 0;
-    double* stage2 = nullptr;
-    int64_t stage2_len = 0;
-    double* cstage = nullptr;   // SMCN_MODEL_HGLM / ORDINAL / MLGLM: the constrained population the moment kernels read ([ngen][D][N])
-    int64_t cstage_len = 0;
-    int32_t *nleap = nullptr, *depth = nullptr, *ndraws = nullptr, *flags = nullptr;
-    int64_t* idx = nullptr;
-    unsigned int* queue = nullptr;
-    double* kin0 = nullptr;     // wave-per-particle NUTS kernels: |r|^2, |r'|^2 and the all-coordinates-moved flag per particle
-    double* kin1 = nullptr;
-    int32_t* moved_i = nullptr;
+    Buf<double> stage;  // [N*D] host<->device staging, also [M*D] for target_eval
+    Buf<double> stage2;
+    Buf<double> cstage;   // SMCN_MODEL_HGLM / ORDINAL / MLGLM: the constrained population the moment kernels read ([ngen][D][N])
+    Buf<int32_t> nleap, depth, ndraws, flags;
+    Buf<int64_t> idx;
+    Buf<unsigned int> queue;
+    Buf<double> kin0;     // wave-per-particle NUTS kernels: |r|^2, |r'|^2 and the all-coordinates-moved flag per particle
+    Buf<double> kin1;
+    Buf<int32_t> moved_i;
     bool kin_valid = false;     // written by the last NUTS launch (consumed by the device-resident re-weighting)
     // Momentum layout.  Targets whose particle fills a wavefront (nuts_wave_kernel: coordinate c on lane c % 64) read and
     // write a particle's momentum as ONE contiguous row: r / r_new then hold [N][D] ("particle-major": 512-byte coalesced
     // rows) instead of the [D][N] every other kernel uses -- converted in place (momentum_dn) before any of those reads them
     bool r_pm = false, r_new_pm = false;
-    unsigned long long* prof = nullptr;
-    double* tape_d = nullptr;
-    int64_t* tape_off_d = nullptr;
-    int64_t tape_cap = 0;
+    Buf<unsigned long long> prof;
+    Buf<double> tape_d;
+    Buf<int64_t> tape_off_d;
     bool momentum_set = false, lg_set = false, q_set = false, u_set = false;
     // device-resident loop (smcn_fast_*)
-    double *hist = nullptr, *ss = nullptr, *lp = nullptr, *gath = nullptr, *hist_x = nullptr, *hist_logw = nullptr;
-    double* u_res = nullptr;
-    double *in_rec = nullptr, *out_rec = nullptr;   // nuts2 per-particle records
-    double* nuts_scratch = nullptr;                  // HBM tree stacks (large D)
-    int64_t nuts_scratch_len = 0;
+    Buf<double> hist, ss, lp, gath, hist_x, hist_logw;
+    Buf<double> u_res;
+    Buf<double> in_rec, out_rec;   // nuts2 per-particle records
+    Buf<double> nuts_scratch;                  // HBM tree stacks (large D)
     int64_t fast_K = -1;
     bool fast_hist = false;
     // fused transitions (smcn_super_*)
@@ -132,86 +147,75 @@ struct smcn_ctx {
     bool fused_ok = false;     // the model's NUTS kernel takes B > 1 transitions per launch
     bool lane_kernel = false;  // NUTS by nuts3_kernel (one lane per particle)
     int64_t arma_T = 0;        // series length of an arma context
-    double *tb_state = nullptr, *tb_part = nullptr, *tb_local = nullptr, *tb_gath = nullptr;   // device-side ESS bisection
+    Buf<double> tb_state, tb_part, tb_local, tb_gath;   // device-side ESS bisection
     int tb_world = 0, tb_blocks = 0;
     int wide_eval = 1;         // nuts3_kernel: lane groups evaluate a wavefront's last stragglers (smcn_set_wide_eval)
     int64_t lane_grid_cap = 0; // nuts3_kernel: wavefronts launched at most (0: one per SIMD; < 0: no cap, a wavefront per 64 particles)
     int lane_segments = 0;     // nuts3_kernel, fewer lanes than particles: segments a block is worked off in (0: auto, 1: whole blocks)
-    unsigned long long* handover = nullptr;  // [N][segments - 1][VH + 1 pairs] (lane queue: x', running log-weight between segments)
-    int64_t handover_len = 0;
+    Buf<unsigned long long> handover;  // [N][segments - 1][VH + 1 pairs] (lane queue: x', running log-weight between segments)
     bool plain_block = false;  // the last smcn_fuse_run ran ONE transition of a model without fused transitions
     // in-library shard exchange (RCCL) and the routed global resampling (smcn_gres_*)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 1;
-    double *g_ttot_all = nullptr, *g_toff_all = nullptr, *g_keys = nullptr, *g_keys_send = nullptr, *g_keys_recv = nullptr,
-           *g_rows_send = nullptr, *g_rows_recv = nullptr;
-    int32_t *g_dest = nullptr, *g_order = nullptr;
+    Buf<double> g_ttot_all, g_toff_all, g_keys, g_keys_send, g_keys_recv, g_rows_send, g_rows_recv;
+    Buf<int32_t> g_dest, g_order;
     int64_t g_serve_cap = 0;
     int g_world = 0;
     smcn_host_target_fn host_fn = nullptr;   // SMCN_MODEL_HOST: the caller's density
     void* host_user = nullptr;
-    double *hc_vec = nullptr, *hc_sc = nullptr, *hc_gp = nullptr, *hc_gl = nullptr;   // host-target NUTS state
-    int32_t* hc_st = nullptr;
+    Buf<double> hc_vec, hc_sc, hc_gp, hc_gl;   // host-target NUTS state
+    Buf<int32_t> hc_st;
     std::vector<double> hx, hlp, hll, hgp, hgl;   // host staging of the callback
-    double* n2_ovf = nullptr;           // v2 kernel: overflow tree-stack levels
-    int64_t n2_ovf_len = 0;
-    double* ss_scratch = nullptr;       // pipelined blocks: step scalars of the inner generations
-    double* rows_h = nullptr;           // pinned: history rows of the block being validated
-    double* hist_h = nullptr;           // pinned: the whole scalar history, downloaded behind a run's last block
+    Buf<double> n2_ovf;           // v2 kernel: overflow tree-stack levels
+    Buf<double> ss_scratch;       // pipelined blocks: step scalars of the inner generations
+    DevBuf<double, PinnedMem> rows_h;   // pinned: history rows of the block being validated
+    DevBuf<double, PinnedMem> hist_h;   // pinned: the whole scalar history, downloaded behind a run's last block
     bool hist_h_valid = false;
-    hipEvent_t ev_rows = nullptr;
+    DevEvent<HipEv, false> ev_rows;     // (no timing: only waited for)
     hipStream_t dl_stream = nullptr;    // history download beside the loop (smcn_history_download)
-    double* dl_stage = nullptr;
-    int64_t dl_stage_len = 0;
-    double *lpB = nullptr, *gathB = nullptr, *gen_x = nullptr, *gen_logw = nullptr, *cnt = nullptr, *shiftB = nullptr;
+    Buf<double> dl_stage;
+    Buf<double> lpB, gathB, gen_x, gen_logw, cnt, shiftB;
 
     // NUTS kernel timing (HIP events on the launch stream)
-    hipEvent_t ev0[kTimerRing], ev1[kTimerRing];
+    Event ev0[kTimerRing], ev1[kTimerRing];
     int ev_n = 0;
     double nuts_ms = 0.0;
     int64_t nuts_launches = 0;
 
     // pointwise criteria (smcn_pointwise_*): log-weights, slice partials and the result of a call; its kernels' time
-    double* pw_buf = nullptr;
-    int64_t pw_len = 0;
-    hipEvent_t pw_ev0 = nullptr, pw_ev1 = nullptr;
+    Buf<double> pw_buf;
+    Event pw_ev0, pw_ev1;     // (around the kernels of smcn_predict_partials and smcn_predict_draws too)
     double pw_ms = 0.0;
 
     // Pareto-smoothed LOO (smcn_psis_*): header, log-weights, the staged slab of ll, candidates, cutoffs, body partials and
     // the result of a call; device time of the stages of the last calls (candidates, body, fit, whole smcn_psis_loo)
-    double* ps_buf = nullptr;
-    int64_t ps_len = 0;
-    hipEvent_t ps_ev[4] = {};
+    Buf<double> ps_buf;
+    Event ps_ev[4];
     double ps_ms[4] = {};
 
     // held-out prediction (smcn_predict_*): the new rows' image [block | padding | table] as smcn_ctx_create lays out the
     // training data, its layout (pr.n new rows, 0: none set) and whether they came with y
-    double* pr_md = nullptr;
-    int64_t pr_md_len = 0;
+    Buf<double> pr_md;
     RegLayout pr;
     int pr_has_y = 0;
     double pr_ms = 0.0;
 
     // posterior predictive draws (smcn_predict_draws): weights, scan, ancestors, gathered particles and the draws of a call
-    double* dr_buf = nullptr;
-    int64_t dr_len = 0;
+    Buf<double> dr_buf;
     double dr_ms = 0.0;
 
     // posterior summaries (smcn_summary_*): the staged population of a call (constrained values, fixed-point weights,
     // selection state), its histograms, and the device time of its kernels
-    double* sm_buf = nullptr;
-    int64_t sm_len = 0;
-    unsigned long long* sm_hist = nullptr;
-    int64_t sm_hist_len = 0;
+    Buf<double> sm_buf;
+    Buf<unsigned long long> sm_hist;
     int64_t sm_M = 0;
     int sm_Dc = 0, sm_cur = 0, sm_stage_state = 0;    // (state: 0 nothing staged, 1 values, 2 values and weights)
     std::vector<unsigned long long> sm_pfx_h, sm_thr_h;
-    hipEvent_t sm_ev[10] = {};
+    Event sm_ev[10];
     double sm_ms = 0.0, sm_pass_ms[8] = {};
     // posterior covariance (smcn_cov_*): weights, centre, slice and group partials, result
-    double* cov_buf = nullptr;
-    int64_t cov_len = 0;
-    hipEvent_t cov_ev[2] = {};
+    Buf<double> cov_buf;
+    Event cov_ev[2];
     double cov_ms = 0.0;
 };
 
@@ -220,7 +224,7 @@ struct smcn_ctx {
     (void)hipSetDevice((c)->device)
 #define HIPC(c, call)                                                                         \
     do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
+        const hipError_t e_ = (hipError_t)(call);                                                            \
         if (e_ != hipSuccess) {                                                               \
             (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                     \
             return -2;                                                                        \
@@ -350,10 +354,17 @@ hipError_t cached_free(void* p, bool synced = false, bool keep = true) {
     return hipFree(p);
 }
 }  // namespace
-
-template <class T>
-static hipError_t dalloc(T** p, int64_t n) {
-    return cached_malloc((void**)p, sizeof(T) * (size_t)(n > 0 ? n : 1));
+int CacheMem::alloc(void** p, size_t bytes) { return (int)cached_malloc(p, bytes); }
+void CacheMem::free(void* p, bool synced) { (void)cached_free(p, synced); }
+// A buffer that may still be in use grows behind a wait for the context's stream.  (Buffers made lazily as a SET are asked
+// for by the set's LAST member -- `if (!c->moved_i)` for kin0, kin1, moved_i -- so that a set a failed allocation left
+// incomplete is made again; a capacity that is no length -- rec_cap, g_world -- is 0 while its buffers are being made.)
+template <class B>
+static int grow(smcn_ctx* c, B& buf, int64_t need) {
+    if (need <= buf.len()) return 0;
+    HIPC(c, stream_wait(c->stream));
+    HIPC(c, buf.grow(need));
+    return 0;
 }
 
 #ifdef SMCN_TRACE_SETUP   // (diagnostic build: where a context's set-up time goes, on stderr)
@@ -535,41 +546,16 @@ int smcn_device_cache_trim(int device, int64_t* released_bytes, int64_t* idle_by
 
 const char* smcn_last_error(const smcn_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
+// What teardown has to do in ORDER: ONE wait for everything this context has in flight (its own stream, the history
+// stream -- its buffers were used by these only), then the streams go back to the pool.  The buffers and events are members
+// and release themselves, synced, when the context is deleted behind this.
 static void free_all(smcn_ctx* c) {
-    void* ptrs[] = {c->mdata, c->x, c->x_new, c->x_tmp, c->r, c->r_new, c->logw, c->logw_new, c->wn, c->work,
-                    c->lpri0, c->llik0, c->lpri1, c->llik1, c->Lg, c->qv, c->scan_local, c->ttot, c->toff, c->part,
-                    c->scal, c->stage, c->stage2, c->nleap, c->depth, c->ndraws, c->flags, c->idx, c->queue,
-                    c->tape_d, c->tape_off_d, c->prof, c->hist, c->ss, c->lp, c->gath, c->hist_x, c->hist_logw, c->u_res, c->in_rec, c->out_rec, c->nuts_scratch, c->lpB, c->gathB, c->gen_x, c->gen_logw, c->cnt, c->shiftB, c->ss_scratch, c->n2_ovf, c->hc_vec, c->hc_sc, c->hc_gp, c->hc_gl, c->hc_st, c->kin0, c->kin1, c->moved_i, c->tb_state, c->tb_part, c->tb_local,
-                    c->tb_gath, c->glk_buf, c->glk_xchg, c->nuts_resume, c->nuts_pend, c->nuts_mq, c->nuts_mq_rec, c->handover, c->cstage, c->pw_buf, c->ps_buf, c->pr_md, c->dr_buf, c->sm_buf, c->sm_hist, c->cov_buf};
-    if (c->rows_h) (void)hipHostFree(c->rows_h);
-    if (c->hist_h) (void)hipHostFree(c->hist_h);
-    if (c->ev_rows) (void)hipEventDestroy(c->ev_rows);
-    if (c->pw_ev0) (void)hipEventDestroy(c->pw_ev0);
-    if (c->pw_ev1) (void)hipEventDestroy(c->pw_ev1);
-    for (hipEvent_t e : c->ps_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->sm_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->cov_ev)
-        if (e) (void)hipEventDestroy(e);
-    // ONE wait for everything this context has in flight (its own stream, the history stream); the buffers below were
-    // used by these streams only
     if (c->stream) (void)stream_wait(c->stream);
     if (c->dl_stream) (void)hipStreamSynchronize(c->dl_stream);
     if (c->dl_stream) pool_give(c->device, c->dl_stream);
     c->dl_stream = nullptr;
-    if (c->dl_stage) (void)cached_free(c->dl_stage, true);
     if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
     c->comm = nullptr;
-    for (void* q : {(void*)c->g_ttot_all, (void*)c->g_toff_all, (void*)c->g_keys, (void*)c->g_keys_send, (void*)c->g_keys_recv,
-                    (void*)c->g_rows_send, (void*)c->g_rows_recv, (void*)c->g_dest, (void*)c->g_order})
-        if (q) (void)cached_free(q, true);
-    for (void* p : ptrs)
-        if (p) (void)cached_free(p, true);
-    for (int i = 0; i < kTimerRing; ++i) {
-        if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
-        if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
-    }
     if (c->own_stream && c->stream) pool_give(c->device, c->stream);
     c->stream = nullptr;
 }
@@ -591,8 +577,6 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
         return -1;
     }
     smcn_ctx* c = new smcn_ctx();
-    memset(c->ev0, 0, sizeof c->ev0);
-    memset(c->ev1, 0, sizeof c->ev1);
     c->device = device_id;
     c->N = n_particles;
     c->base = particle_base;
@@ -651,7 +635,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     const int64_t N = c->N, ND = N * c->D;
     const int nt = grid_for(N, kScanTile);
 #define A_(p, n) \
-    if ((e = dalloc(&c->p, (n))) != hipSuccess) return fail(#p, e)
+    if ((e = (hipError_t)c->p.reset(n)) != hipSuccess) return fail(#p, e)
     // PRMwCD: behind the caller's data a table the one-lane-per-particle functor reads by scalar loads -- a row per observation,
     // [X_i1 .. X_iC, y_i] padded to an even count, at a 128-byte boundary, two zero rows behind it for the look-ahead
     std::vector<double> mup(model_data, model_data + model_data_len);
@@ -676,7 +660,6 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     A_(stage, ND); A_(nleap, N); A_(depth, N); A_(ndraws, N); A_(flags, N); A_(idx, N); A_(queue, 16); A_(prof, 16);
 #undef A_
     SETUP_TRACE("35 x hipMalloc");
-    c->stage_len = ND;
     // (everything below goes through the context's OWN stream: it is non-blocking, so a hipMemset on the null stream is not
     //  ordered against it and could land AFTER the first kernels the caller enqueues -- seen with eight 1.6 GB contexts
     //  created at once: part of a shard's initial particles zeroed behind smcn_init_particles_std_normal)
@@ -694,8 +677,8 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     if ((e = stream_wait(c->stream)) != hipSuccess) return fail("initial memsets", e);   // (model_data is the caller's)
     SETUP_TRACE("memsets + wait");
     for (int i = 0; i < kTimerRing; ++i) {
-        if ((e = hipEventCreate(&c->ev0[i])) != hipSuccess) return fail("event", e);
-        if ((e = hipEventCreate(&c->ev1[i])) != hipSuccess) return fail("event", e);
+        if ((e = (hipError_t)c->ev0[i].create()) != hipSuccess) return fail("event", e);
+        if ((e = (hipError_t)c->ev1[i].create()) != hipSuccess) return fail("event", e);
     }
     SETUP_TRACE("events");
     // refuse models this build has no device functor for, at creation time
@@ -799,22 +782,8 @@ int smcn_set_seed(smcn_ctx* c, uint64_t seed) {
 }
 
 // ---- staging helpers --------------------------------------------------------------
-static int ensure_stage(smcn_ctx* c, int64_t n) {
-    if (n <= c->stage_len) return 0;
-    if (c->stage) (void)cached_free(c->stage);
-    c->stage = nullptr;
-    HIPC(c, dalloc(&c->stage, n));
-    c->stage_len = n;
-    return 0;
-}
-static int ensure_stage2(smcn_ctx* c, int64_t n) {
-    if (n <= c->stage2_len) return 0;
-    if (c->stage2) (void)cached_free(c->stage2);
-    c->stage2 = nullptr;
-    HIPC(c, dalloc(&c->stage2, n));
-    c->stage2_len = n;
-    return 0;
-}
+static int ensure_stage(smcn_ctx* c, int64_t n) { return grow(c, c->stage, n); }
+static int ensure_stage2(smcn_ctx* c, int64_t n) { return grow(c, c->stage2, n); }
 // models whose constrained space is not coordinate-wise: the moment kernels read a constrained copy of the population
 static bool has_constrain_pass(const smcn_ctx* c) {
     return c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_ORDINAL || c->model == SMCN_MODEL_MLGLM;
@@ -838,12 +807,7 @@ static void launch_constrain_pass(smcn_ctx* c, const double* x, double* out, int
 // into c->cstage, on the context's stream; *out is what the moment kernels then read with the identity (c->cmodel)
 static int model_constrained(smcn_ctx* c, const double* x, int ngen, const double** out) {
     const int64_t M = (int64_t)ngen * c->N, n = M * c->D;
-    if (n > c->cstage_len) {
-        if (c->cstage) (void)cached_free(c->cstage);
-        c->cstage = nullptr;
-        HIPC(c, dalloc(&c->cstage, n));
-        c->cstage_len = n;
-    }
+    if (int rc = grow(c, c->cstage, n)) return rc;
     launch_constrain_pass(c, x, c->cstage, M, c->N, 1, c->N);
     HIPC(c, hipGetLastError());
     *out = c->cstage;
@@ -1176,18 +1140,17 @@ int smcn_temper_partials(smcn_ctx* c, double phi_old, double phi_new, double out
 // ---- ESSTempering.calculate_phi on the device (smcn_temper.hpp) ------------------------------------------------
 static int tb_ensure(smcn_ctx* c, int world) {
     if (world < 1 || world > 64) FAIL(c, "smcn_temper_bisect: 1..64 shards");
-    if (!c->tb_state) {
+    if (!c->tb_local) {
         c->tb_blocks = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->N + 511) / 512));
-        HIPC(c, dalloc(&c->tb_state, TB_STATE));
-        HIPC(c, dalloc(&c->tb_part, (int64_t)c->tb_blocks * kTbNodes * 4));
-        HIPC(c, dalloc(&c->tb_local, kTbNodes * 4));
+        HIPC(c, c->tb_state.reset(TB_STATE));
+        HIPC(c, c->tb_part.reset((int64_t)c->tb_blocks * kTbNodes * 4));
+        HIPC(c, c->tb_local.reset(kTbNodes * 4));
         HIPC(c, hipMemsetAsync(c->tb_state, 0, sizeof(double) * TB_STATE, c->stream));
     }
     if (c->tb_world < world) {
+        c->tb_world = 0;
         HIPC(c, stream_wait(c->stream));
-        if (c->tb_gath) (void)cached_free(c->tb_gath);
-        c->tb_gath = nullptr;
-        HIPC(c, dalloc(&c->tb_gath, (int64_t)world * kTbNodes * 4));
+        HIPC(c, c->tb_gath.reset((int64_t)world * kTbNodes * 4));
         c->tb_world = world;
     }
     return 0;
@@ -1395,15 +1358,12 @@ int smcn_bench_resample(smcn_ctx* c, int reps, int64_t iteration, double* ms_tot
     // the particles are permuted on a COPY (x_tmp <-> stage): the resident state is the same before and after
     int rc = ensure_stage(c, N * c->D);
     if (rc) return rc;
-    struct Events {     // destroyed on every exit path
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    HIPC(c, hipEventCreate(&ev.e0));
-    HIPC(c, hipEventCreate(&ev.e1));
+    Event e0, e1;
+    HIPC(c, e0.create());
+    HIPC(c, e1.create());
     HIPC(c, hipMemcpyAsync(c->x_tmp, c->x, sizeof(double) * N * c->D, hipMemcpyDeviceToDevice, c->stream));
     double *src = c->x_tmp, *dst = c->stage;
-    HIPC(c, hipEventRecord(ev.e0, c->stream));
+    HIPC(c, e0.record(c->stream));
     for (int r = 0; r < reps; ++r) {
         scan_tile_kernel<<<nt, 256, 0, c->stream>>>(c->wn, N, c->scan_local, c->ttot);
         if (!fused) scan_offsets_kernel<<<1, 64, 0, c->stream>>>(c->ttot, nt, c->toff);
@@ -1416,11 +1376,9 @@ int smcn_bench_resample(smcn_ctx* c, int reps, int64_t iteration, double* ms_tot
         std::swap(src, dst);
     }
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(ev.e1, c->stream));
-    HIPC(c, hipEventSynchronize(ev.e1));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    *ms_total = ms;
+    HIPC(c, e1.record(c->stream));
+    HIPC(c, e1.wait());
+    HIPC(c, e1.since(e0, ms_total));
     return 0;
 }
 
@@ -1432,27 +1390,15 @@ struct resume_model;
 template <int NOBS, int C_, int RED, int LEVELS, bool FAST>
 struct resume_model<PrmwcdDistModel<8, NOBS, C_, RED, LEVELS, FAST>> { using type = PrmwcdDistModel<64, NOBS, C_, 2, 5, FAST>; };
 
-// Grows one of the context's scratch buffers (nuts_scratch, n2_ovf, pw_buf, pr_md, dr_buf) to at least `need` doubles;
-// holds nothing (len = 0) if the allocation fails.
-static int grow_scratch(smcn_ctx* c, double*& buf, int64_t& len, int64_t need) {
-    if (need <= len) return 0;
-    HIPC(c, stream_wait(c->stream));     // (the old buffer may still be in use)
-    if (buf) (void)cached_free(buf);
-    buf = nullptr;
-    len = 0;
-    HIPC(c, dalloc(&buf, need));
-    len = need;
-    return 0;
-}
 // Enqueues a kernel launch between the timer events of the context's next ring slot (smcn_nuts_times).
 template <class L>
 static int timed_launch(smcn_ctx* c, L&& launch) {
     const int k = c->ev_n < kTimerRing ? c->ev_n : -1;
-    if (k >= 0) HIPC(c, hipEventRecord(c->ev0[k], c->stream));
+    if (k >= 0) HIPC(c, c->ev0[k].record(c->stream));
     launch();
     HIPC(c, hipGetLastError());
     if (k >= 0) {
-        HIPC(c, hipEventRecord(c->ev1[k], c->stream));
+        HIPC(c, c->ev1[k].record(c->stream));
         c->ev_n++;
     }
     return 0;
@@ -1478,10 +1424,10 @@ static int launch_nuts_fin(smcn_ctx* c, NutsArgs a, int64_t items) {
     if (a.resume_in) {
         a.kin0 = nullptr; a.kin1 = nullptr; a.moved = nullptr;   // (a resumed tree's start statistics were not kept)
     } else {
-        if (!c->kin0) {
-            HIPC(c, dalloc(&c->kin0, c->N));
-            HIPC(c, dalloc(&c->kin1, c->N));
-            HIPC(c, cached_malloc((void**)&c->moved_i, sizeof(int32_t) * c->N));
+        if (!c->moved_i) {
+            HIPC(c, c->kin0.reset(c->N));
+            HIPC(c, c->kin1.reset(c->N));
+            HIPC(c, c->moved_i.reset(c->N));
         }
         a.kin0 = c->kin0; a.kin1 = c->kin1; a.moved = c->moved_i;
         c->kin_valid = true;
@@ -1504,13 +1450,13 @@ static int launch_nuts_wave_t(smcn_ctx* c, NutsArgs a) {
     const int64_t cap = (int64_t)c->num_cu * per_cu;
     if (blocks > cap) blocks = cap;
     // first leaves of the sub-trees above the LDS slots: one area per resident wavefront
-    if (int rc = grow_scratch(c, c->nuts_scratch, c->nuts_scratch_len, blocks * wpb * (int64_t)kMaxLevels * wave_slot_doubles(Model::DL)))
+    if (int rc = grow(c, c->nuts_scratch, blocks * wpb * (int64_t)kMaxLevels * wave_slot_doubles(Model::DL)))
         return rc;
     a.scratch = c->nuts_scratch;
-    if (!c->kin0) {
-        HIPC(c, dalloc(&c->kin0, c->N));
-        HIPC(c, dalloc(&c->kin1, c->N));
-        HIPC(c, cached_malloc((void**)&c->moved_i, sizeof(int32_t) * c->N));
+    if (!c->moved_i) {
+        HIPC(c, c->kin0.reset(c->N));
+        HIPC(c, c->kin1.reset(c->N));
+        HIPC(c, c->moved_i.reset(c->N));
     }
     a.kin0 = c->kin0; a.kin1 = c->kin1; a.moved = c->moved_i;
     c->kin_valid = true;
@@ -1561,9 +1507,9 @@ static int launch_nuts(smcn_ctx* c, Model, NutsArgs a) {
             if (c->nuts_jcap <= 0 || c->nuts_jcap >= a.max_depth + 1) return launch_nuts_phase<Model, false>(c, Model{}, a, a.N);
             // ---- two phases: trees that want more than jcap doublings are parked and finished by a second launch ------
             const int64_t rsz = 8 * (int64_t)c->D + 8;
-            if (!c->nuts_resume) {
-                HIPC(c, dalloc(&c->nuts_resume, c->N * rsz));
-                HIPC(c, cached_malloc((void**)&c->nuts_pend, sizeof(unsigned int) * (c->N + 1)));
+            if (!c->nuts_pend) {
+                HIPC(c, c->nuts_resume.reset(c->N * rsz));
+                HIPC(c, c->nuts_pend.reset(c->N + 1));
             }
             HIPC(c, hipMemsetAsync(c->nuts_pend, 0, sizeof(unsigned int), c->stream));
             a.jcap = c->nuts_jcap; a.resume = c->nuts_resume; a.pend = c->nuts_pend; a.resume_in = 0;
@@ -1572,9 +1518,9 @@ static int launch_nuts(smcn_ctx* c, Model, NutsArgs a) {
             c->nuts_mq_used = false;
             if (mq_b > 0 && mq_b < c->nuts_jcap && c->nuts_mq_ok) {
                 if (8 * c->D + 8 > 128) FAIL(c, "nuts: the inner park level holds records of up to 128 doubles (D <= 15)");
-                if (!c->nuts_mq) {
-                    HIPC(c, cached_malloc((void**)&c->nuts_mq, sizeof(unsigned int) * (c->N + 16)));
-                    HIPC(c, dalloc(&c->nuts_mq_rec, c->N * 128));
+                if (!c->nuts_mq_rec) {
+                    HIPC(c, c->nuts_mq.reset(c->N + 16));
+                    HIPC(c, c->nuts_mq_rec.reset(c->N * 128));
                 }
                 HIPC(c, hipMemsetAsync(c->nuts_mq, 0, sizeof(unsigned int) * (c->N + 16), c->stream));
                 a.mq = c->nuts_mq; a.mq_rec = c->nuts_mq_rec; a.mq_b = mq_b;
@@ -1618,7 +1564,7 @@ static int launch_nuts_phase(smcn_ctx* c, Model, NutsArgs a, int64_t items) {
     const int64_t cap = (int64_t)c->num_cu * per_cu;
     if (blocks > cap) blocks = cap;
     if (HBM) {
-        if (int rc = grow_scratch(c, c->nuts_scratch, c->nuts_scratch_len, blocks * gpb * (int64_t)nuts_slot_doubles(VS)))
+        if (int rc = grow(c, c->nuts_scratch, blocks * gpb * (int64_t)nuts_slot_doubles(VS)))
             return rc;
         a.scratch = c->nuts_scratch;
     }
@@ -1632,6 +1578,17 @@ static int launch_nuts_phase(smcn_ctx* c, Model, NutsArgs a, int64_t items) {
 
 // One lane per particle (smcn_nuts3.hpp): one wavefront per block, no work queue; input and output records, a prep
 // kernel (momentum draw, slice exponential) and the post kernel of smcn_nuts2.hpp (unpack + forward-L re-weight).
+// the lane kernels' per-transition records for blocks of up to `cap` transitions
+static int reset_records(smcn_ctx* c, int64_t cap, int D) {
+    c->rec_cap = 0;
+    HIPC(c, stream_wait(c->stream));
+    c->in_rec.release();
+    c->out_rec.release();
+    HIPC(c, c->in_rec.reset(c->N * cap * n2_in_doubles(D)));
+    HIPC(c, c->out_rec.reset(c->N * cap * n2_out_doubles(D)));
+    c->rec_cap = cap;
+    return 0;
+}
 template <class Model, bool TAPE, int LC, int LF>
 static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const int64_t* tape_off_d, bool fuse_reweight,
                         int B, double* gen_x, double* gen_logw, double* cnt, int phase) {
@@ -1641,13 +1598,7 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
     if (phase == 2 && B > c->rec_cap) FAIL(c, "nuts3: post without a launch");
     if (B > c->rec_cap) {   // once: sized for the longest block the caller announced (smcn_fuse_begin)
         const int cap = c->fuse_max > B ? c->fuse_max : B;
-        HIPC(c, stream_wait(c->stream));
-        if (c->in_rec) (void)cached_free(c->in_rec);
-        if (c->out_rec) (void)cached_free(c->out_rec);
-        c->in_rec = c->out_rec = nullptr;
-        HIPC(c, dalloc(&c->in_rec, N * cap * n2_in_doubles(D)));
-        HIPC(c, dalloc(&c->out_rec, N * cap * n2_out_doubles(D)));
-        c->rec_cap = cap;
+        if (int rc = reset_records(c, cap, D)) return rc;
     }
     const size_t lds = (size_t)n3_lds_bytes<Model>(LC, LF);
     // one wavefront per SIMD is all the chip holds of this kernel: larger populations are NOT more wavefronts (a second
@@ -1660,7 +1611,7 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
     // (the ready bits of a wavefront's particles are one 64-bit word per lane: beyond 4 096 particles a wavefront the
     //  launch is the plain one -- a wavefront per 64 particles, in rounds)
     if (((N + blocks - 1) / blocks + 63) / 64 > kN3ReadyWords) blocks = (N + kN3Block - 1) / kN3Block;
-    if (int rc = grow_scratch(c, c->n2_ovf, c->n2_ovf_len, blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, LC, LF))) return rc;
+    if (int rc = grow(c, c->n2_ovf, blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, LC, LF))) return rc;
     a.ovf = c->n2_ovf;
     if (phase != 2) {
         if (c->momentum_set && B != 1) FAIL(c, "nuts3: caller-supplied momenta go with single transitions");
@@ -1698,13 +1649,7 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
                 ++segs;
             }
             const int64_t hw = N * (segs - 1) * 2 * (n2_vp(D) / 2 + 1);     // 8-byte words: [N][segments - 1][VH + 1 pairs]
-            if (hw > c->handover_len) {
-                HIPC(c, stream_wait(c->stream));
-                if (c->handover) (void)cached_free(c->handover);
-                c->handover = nullptr;
-                HIPC(c, cached_malloc((void**)&c->handover, sizeof(unsigned long long) * (size_t)hw));
-                c->handover_len = hw;
-            }
+            if (int rc = grow(c, c->handover, hw)) return rc;
             a.handover = c->handover;
         }
         const void* const kfn = queued ? (const void*)nuts3_kernel<Model, TAPE, LC, LF, true, 1>
@@ -1731,12 +1676,12 @@ static int propose_host(smcn_ctx* c, double step_size, double phi, int max_depth
                         const double* tape_d, const int64_t* tape_off_d) {
     const int64_t N = c->N;
     const int D = c->D;
-    if (!c->hc_vec) {
-        HIPC(c, dalloc(&c->hc_vec, (int64_t)HV_COUNT * D * N));
-        HIPC(c, dalloc(&c->hc_sc, (int64_t)HS_COUNT * N));
-        HIPC(c, dalloc(&c->hc_st, (int64_t)HI_COUNT * N));
-        HIPC(c, dalloc(&c->hc_gp, (int64_t)D * N));
-        HIPC(c, dalloc(&c->hc_gl, (int64_t)D * N));
+    if (!c->hc_gl) {
+        HIPC(c, c->hc_vec.reset((int64_t)HV_COUNT * D * N));
+        HIPC(c, c->hc_sc.reset((int64_t)HS_COUNT * N));
+        HIPC(c, c->hc_st.reset((int64_t)HI_COUNT * N));
+        HIPC(c, c->hc_gp.reset((int64_t)D * N));
+        HIPC(c, c->hc_gl.reset((int64_t)D * N));
     }
     if (!c->momentum_set) {  // samples.py:155 with the N(0, I) momentum proposal
         const int64_t n = N * ((D + 1) / 2);
@@ -1788,14 +1733,8 @@ static int propose_async(smcn_ctx* c, double step_size, double phi, int max_dept
     if (tape) {
         const int64_t len = tape_off[N];
         if (len < 0) FAIL(c, "smcn_propose_nuts: bad tape offsets");
-        if (len + 1 > c->tape_cap) {
-            HIPC(c, stream_wait(c->stream));
-            if (c->tape_d) (void)cached_free(c->tape_d);
-            c->tape_d = nullptr;
-            HIPC(c, dalloc(&c->tape_d, len + 1));
-            c->tape_cap = len + 1;
-        }
-        if (!c->tape_off_d) HIPC(c, dalloc(&c->tape_off_d, N + 1));
+        if (int rc = grow(c, c->tape_d, len + 1)) return rc;
+        if (!c->tape_off_d) HIPC(c, c->tape_off_d.reset(N + 1));
         HIPC(c, hipMemcpyAsync(c->tape_d, tape, sizeof(double) * len, hipMemcpyHostToDevice, c->stream));
         HIPC(c, hipMemcpyAsync(c->tape_off_d, tape_off, sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, c->stream));
         tape_d = c->tape_d;
@@ -2037,7 +1976,7 @@ int smcn_gauss_lkernel_device(smcn_ctx* c, double info[4]) {
     if (D > kGlkMaxD) FAIL(c, "smcn_gauss_lkernel_device: D > 32 not supported (use the host algebra)");
     if (c->N < 2) FAIL(c, "smcn_gauss_lkernel_device: needs at least two particles");
     const size_t npar = (size_t)2 * D + 2 * D * D + 4;
-    if (!c->glk_buf) HIPC(c, cached_malloc((void**)&c->glk_buf, sizeof(double) * (E + 2 * (size_t)nq + npar)));
+    if (!c->glk_buf) HIPC(c, c->glk_buf.reset((int64_t)(E + 2 * (size_t)nq + npar)));
     double *dmu = c->glk_buf, *ds1 = dmu + E, *ds2 = ds1 + nq, *par = ds2 + nq;
     const int TP = D <= 16 ? 256 : 64;
     const size_t lds = sizeof(double) * ((size_t)E * TP + nq) + sizeof(unsigned short) * (size_t)((nq + 3) & ~3);
@@ -2079,10 +2018,9 @@ int smcn_gauss_lkernel_buffers(smcn_ctx* c, int world, void** local, void** gath
     const int D = c->D, E = 2 * D, nq = E + E * (E + 1) / 2;
     if (D > kGlkMaxD) FAIL(c, "smcn_gauss_lkernel_buffers: D > 32 not supported (use the host algebra)");
     if (c->glk_world < world) {
+        c->glk_world = 0;
         HIPC(c, stream_wait(c->stream));
-        if (c->glk_xchg) (void)cached_free(c->glk_xchg);
-        c->glk_xchg = nullptr;
-        HIPC(c, dalloc(&c->glk_xchg, (int64_t)(world + 1) * nq));
+        HIPC(c, c->glk_xchg.reset((int64_t)(world + 1) * nq));
         c->glk_world = world;
     }
     *local = c->glk_xchg;
@@ -2099,7 +2037,7 @@ int smcn_gauss_lkernel_stage(smcn_ctx* c, int stage, int world, double n_total, 
         FAIL(c, "smcn_gauss_lkernel_stage: call smcn_gauss_lkernel_buffers(world) first; stages 0, 1, 2");
     if (!(n_total >= 2.0)) FAIL(c, "smcn_gauss_lkernel_stage: needs at least two particles");
     const size_t npar = (size_t)2 * D + 2 * D * D + 4;
-    if (!c->glk_buf) HIPC(c, cached_malloc((void**)&c->glk_buf, sizeof(double) * (E + 2 * (size_t)nq + npar)));
+    if (!c->glk_buf) HIPC(c, c->glk_buf.reset((int64_t)(E + 2 * (size_t)nq + npar)));
     double *dmu = c->glk_buf, *ds1 = dmu + E, *ds2 = ds1 + nq, *par = ds2 + nq;
     double *loc = c->glk_xchg, *gat = loc + nq;
     const double* rows = world > 1 ? gat : loc;
@@ -2214,25 +2152,22 @@ int smcn_fast_begin(smcn_ctx* c, int64_t K, int save_history, int world) {
     HIPC(c, stream_wait(c->stream));
     SETUP_TRACE("fast_begin: wait");
     const int HS = hist_stride(c->Dc), NQ = 4 + 2 * c->Dc;
-    for (double** p : {&c->hist, &c->ss, &c->lp, &c->gath, &c->hist_x, &c->hist_logw, &c->u_res}) {
-        if (*p) (void)cached_free(*p);
-        *p = nullptr;
-    }
-    HIPC(c, dalloc(&c->hist, (K + 1) * HS));
-    HIPC(c, dalloc(&c->ss, SS_SHIFT + c->Dc + 8));
-    HIPC(c, dalloc(&c->lp, NQ));
-    HIPC(c, dalloc(&c->gath, (int64_t)world * NQ));
-    HIPC(c, dalloc(&c->u_res, c->N));
+    for (Buf<double>* b : {&c->hist, &c->ss, &c->lp, &c->gath, &c->hist_x, &c->hist_logw, &c->u_res}) b->release();
+    HIPC(c, c->hist.reset((K + 1) * HS));
+    HIPC(c, c->ss.reset(SS_SHIFT + c->Dc + 8));
+    HIPC(c, c->lp.reset(NQ));
+    HIPC(c, c->gath.reset((int64_t)world * NQ));
+    HIPC(c, c->u_res.reset(c->N));
     HIPC(c, hipMemsetAsync(c->hist, 0, sizeof(double) * (K + 1) * HS, c->stream));   // (the context's stream: see smcn_ctx_create)
     HIPC(c, hipMemsetAsync(c->ss, 0, sizeof(double) * (SS_SHIFT + c->Dc + 8), c->stream));
     SETUP_TRACE("fast_begin: small buffers");
     c->fast_K = K;
     c->fast_hist = save_history != 0;
-    if (c->hist_h) { (void)hipHostFree(c->hist_h); c->hist_h = nullptr; }
+    c->hist_h.release();
     c->hist_h_valid = false;
     if (c->fast_hist) {
-        HIPC(c, dalloc(&c->hist_x, (K + 1) * c->N * c->D));
-        HIPC(c, dalloc(&c->hist_logw, (K + 1) * c->N));
+        HIPC(c, c->hist_x.reset((K + 1) * c->N * c->D));
+        HIPC(c, c->hist_logw.reset((K + 1) * c->N));
         HIPC(c, hipMemcpyAsync(c->hist_x, c->x, sizeof(double) * c->N * c->D, hipMemcpyDeviceToDevice, c->stream));
         HIPC(c, hipMemcpyAsync(c->hist_logw, c->logw, sizeof(double) * c->N, hipMemcpyDeviceToDevice, c->stream));
         SETUP_TRACE("fast_begin: history buffers");
@@ -2374,24 +2309,17 @@ int smcn_fuse_begin(smcn_ctx* c, int Bmax, int world) {
     if (Bmax < 1 || Bmax > 64 || world < 1 || world > 64) FAIL(c, "smcn_fuse_begin: bad arguments");
     HIPC(c, stream_wait(c->stream));
     const int NQ = 4 + 2 * c->Dc;
-    for (double** p : {&c->lpB, &c->gathB, &c->gen_x, &c->gen_logw, &c->cnt, &c->shiftB}) {
-        if (*p) (void)cached_free(*p);
-        *p = nullptr;
-    }
-    HIPC(c, dalloc(&c->lpB, (int64_t)Bmax * NQ));
-    HIPC(c, dalloc(&c->gathB, (int64_t)Bmax * world * NQ));
-    HIPC(c, dalloc(&c->cnt, 2 * Bmax));
-    HIPC(c, dalloc(&c->shiftB, c->Dc));
-    if (c->ss_scratch) (void)cached_free(c->ss_scratch);
-    c->ss_scratch = nullptr;
-    HIPC(c, dalloc(&c->ss_scratch, (int64_t)Bmax * (SS_SHIFT + c->Dc + 8)));
-    if (c->rows_h) (void)hipHostFree(c->rows_h);
-    c->rows_h = nullptr;
-    HIPC(c, hipHostMalloc((void**)&c->rows_h, sizeof(double) * (size_t)Bmax * hist_stride(c->Dc)));
-    if (!c->ev_rows) HIPC(c, hipEventCreateWithFlags(&c->ev_rows, hipEventDisableTiming));
+    for (Buf<double>* b : {&c->lpB, &c->gathB, &c->gen_x, &c->gen_logw, &c->cnt, &c->shiftB}) b->release();
+    HIPC(c, c->lpB.reset((int64_t)Bmax * NQ));
+    HIPC(c, c->gathB.reset((int64_t)Bmax * world * NQ));
+    HIPC(c, c->cnt.reset(2 * Bmax));
+    HIPC(c, c->shiftB.reset(c->Dc));
+    HIPC(c, c->ss_scratch.reset((int64_t)Bmax * (SS_SHIFT + c->Dc + 8)));
+    HIPC(c, c->rows_h.reset((int64_t)Bmax * hist_stride(c->Dc)));
+    HIPC(c, c->ev_rows.create());
     if (!c->fast_hist) {
-        HIPC(c, dalloc(&c->gen_x, (int64_t)Bmax * c->N * c->D));
-        HIPC(c, dalloc(&c->gen_logw, (int64_t)Bmax * c->N));
+        HIPC(c, c->gen_x.reset((int64_t)Bmax * c->N * c->D));
+        HIPC(c, c->gen_logw.reset((int64_t)Bmax * c->N));
     }
     c->fuse_max = Bmax;
     // lane kernel: the per-transition record buffers and the overflow tree-stack area for blocks of up to Bmax
@@ -2399,20 +2327,9 @@ int smcn_fuse_begin(smcn_ctx* c, int Bmax, int world) {
     // milliseconds in hipMalloc)
     if (c->lane_kernel && Bmax > c->rec_cap) {
         constexpr int D = ArmaLaneModel::D;
-        if (c->in_rec) (void)cached_free(c->in_rec);
-        if (c->out_rec) (void)cached_free(c->out_rec);
-        c->in_rec = c->out_rec = nullptr;
-        HIPC(c, dalloc(&c->in_rec, c->N * Bmax * n2_in_doubles(D)));
-        HIPC(c, dalloc(&c->out_rec, c->N * Bmax * n2_out_doubles(D)));
-        c->rec_cap = Bmax;
+        if (int rc = reset_records(c, Bmax, D)) return rc;
         const int64_t blocks = (c->N + kN3Block - 1) / kN3Block;
-        const int64_t need = blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, 3, 3);
-        if (need > c->n2_ovf_len) {
-            if (c->n2_ovf) (void)cached_free(c->n2_ovf);
-            c->n2_ovf = nullptr;
-            HIPC(c, dalloc(&c->n2_ovf, need));
-            c->n2_ovf_len = need;
-        }
+        if (int rc = grow(c, c->n2_ovf, blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, 3, 3))) return rc;
     }
     return 0;
 }
@@ -2643,11 +2560,11 @@ int smcn_block_stats(smcn_ctx* c, int64_t k0, int B, int world, int rank, double
     c->hist_h_valid = false;
     if (final_block) {   // the run ends with this block: the whole scalar history comes along behind the same event,
                          // so that smcn_fast_read needs no further round trip if the block turns out valid
-        if (!c->hist_h) HIPC(c, hipHostMalloc((void**)&c->hist_h, sizeof(double) * (size_t)(c->fast_K + 1) * HS));
+        if (!c->hist_h) HIPC(c, c->hist_h.reset((c->fast_K + 1) * HS));
         HIPC(c, hipMemcpyAsync(c->hist_h, c->hist, sizeof(double) * (c->fast_K + 1) * HS, hipMemcpyDeviceToHost, c->stream));
         c->hist_h_valid = true;
     }
-    HIPC(c, hipEventRecord(c->ev_rows, c->stream));
+    HIPC(c, c->ev_rows.record(c->stream));
     return 0;
 }
 // *n_ok in 1..B: transitions valid before a generation that has to resample; *resample_next: whether
@@ -2656,7 +2573,7 @@ int smcn_block_wait(smcn_ctx* c, int B, int* n_ok, int* resample_next) {
     CHECK_CTX(c);
     if (c->fuse_max < 1 || B < 1 || B > c->fuse_max || !n_ok || !resample_next)
         FAIL(c, "smcn_block_wait: bad arguments");
-    HIPC(c, hipEventSynchronize(c->ev_rows));
+    HIPC(c, c->ev_rows.wait());
     const int HS = hist_stride(c->Dc);
     int ok = B;
     for (int g = 1; g < B; ++g)
@@ -2688,12 +2605,7 @@ int smcn_block_commit(smcn_ctx* c, int64_t k0, int ok) {   // the committed stat
 static int dl_prepare(smcn_ctx* c) {  // the download stream and its staging buffer (smcn_fast_begin with a history: up front)
     const int64_t ND = c->N * c->D;
     if (!c->dl_stream) HIPC(c, pool_take(c->device, &c->dl_stream));
-    if (c->dl_stage_len < kDlChunk * ND) {
-        if (c->dl_stage) (void)cached_free(c->dl_stage);
-        c->dl_stage = nullptr;
-        HIPC(c, dalloc(&c->dl_stage, kDlChunk * ND));
-        c->dl_stage_len = kDlChunk * ND;
-    }
+    HIPC(c, c->dl_stage.grow(kDlChunk * ND));   // (no wait for c->stream: the loop runs on beside this download)
     return 0;
 }
 
@@ -2738,7 +2650,7 @@ int smcn_fast_read_from(smcn_ctx* c, double* hist, double* x_saved, double* logw
     const int HS = hist_stride(c->Dc);
     const bool cached = hist && c->hist_h_valid && !x_saved && !logw_saved;
     if (cached) {        // downloaded behind the last block's statistics (smcn_block_stats, final_block) and waited for
-        HIPC(c, hipEventSynchronize(c->ev_rows));
+        HIPC(c, c->ev_rows.wait());
         memcpy(hist, c->hist_h, sizeof(double) * K1 * HS);
         return 0;
     }
@@ -2920,19 +2832,18 @@ int smcn_gres_begin(smcn_ctx* c, int world, double* ttot_host) {
     if (world < 1 || world > 64) FAIL(c, "smcn_gres_begin: 1..64 shards");
     const int nt = grid_for(n, kScanTile);
     if (c->g_world != world) {
+        c->g_world = 0;
         HIPC(c, stream_wait(c->stream));
-        for (void** q : {(void**)&c->g_ttot_all, (void**)&c->g_toff_all, (void**)&c->g_keys, (void**)&c->g_keys_send,
-                         (void**)&c->g_rows_recv, (void**)&c->g_dest, (void**)&c->g_order}) {
-            if (*q) (void)cached_free(*q);
-            *q = nullptr;
-        }
-        HIPC(c, dalloc(&c->g_ttot_all, (int64_t)world * nt));
-        HIPC(c, dalloc(&c->g_toff_all, (int64_t)world * nt + 1));
-        HIPC(c, dalloc(&c->g_keys, n));
-        HIPC(c, dalloc(&c->g_keys_send, n));
-        HIPC(c, dalloc(&c->g_rows_recv, n * c->D));
-        HIPC(c, dalloc(&c->g_dest, n));
-        HIPC(c, dalloc(&c->g_order, n));
+        for (Buf<double>* b : {&c->g_ttot_all, &c->g_toff_all, &c->g_keys, &c->g_keys_send, &c->g_rows_recv}) b->release();
+        c->g_dest.release();
+        c->g_order.release();
+        HIPC(c, c->g_ttot_all.reset((int64_t)world * nt));
+        HIPC(c, c->g_toff_all.reset((int64_t)world * nt + 1));
+        HIPC(c, c->g_keys.reset(n));
+        HIPC(c, c->g_keys_send.reset(n));
+        HIPC(c, c->g_rows_recv.reset(n * c->D));
+        HIPC(c, c->g_dest.reset(n));
+        HIPC(c, c->g_order.reset(n));
         c->g_world = world;
     }
     scan_tile_kernel<<<nt, 256, 0, c->stream>>>(c->wn, n, c->scan_local, c->ttot);
@@ -2964,12 +2875,12 @@ int smcn_gres_reserve(smcn_ctx* c, int64_t m) {   // room to serve m requests
     if (m < 0) FAIL(c, "smcn_gres_reserve: negative request count");
     if (m < 1) m = 1;     // a rank that serves nothing still owns (tiny) buffers: communicators alias them by address
     if (m > c->g_serve_cap) {
+        c->g_serve_cap = 0;
         HIPC(c, stream_wait(c->stream));
-        if (c->g_keys_recv) (void)cached_free(c->g_keys_recv);
-        if (c->g_rows_send) (void)cached_free(c->g_rows_send);
-        c->g_keys_recv = c->g_rows_send = nullptr;
-        HIPC(c, dalloc(&c->g_keys_recv, m));
-        HIPC(c, dalloc(&c->g_rows_send, m * c->D));
+        c->g_keys_recv.release();
+        c->g_rows_send.release();
+        HIPC(c, c->g_keys_recv.reset(m));
+        HIPC(c, c->g_rows_send.reset(m * c->D));
         c->g_serve_cap = m;
     }
     return 0;
@@ -3171,7 +3082,6 @@ static PwArgs pw_args(const RegLayout& L, const double* md, const double* x, int
     a.Dc = L.Dc;
     return a;
 }
-static int pw_ensure(smcn_ctx* c, int64_t n) { return grow_scratch(c, c->pw_buf, c->pw_len, n); }
 // f(row capacity) for table rows of Dc columns: DP <= 16 / 32 / 64 doubles
 template <class F>
 static void row_cap(int Dc, F&& f) {
@@ -3244,7 +3154,7 @@ int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) 
     if (tiles * slices > 2147483647LL) FAIL(c, "smcn_pointwise_loglik: too many observations");
     int rc = ensure_stage(c, M * c->D);
     if (rc) return rc;
-    if ((rc = pw_ensure(c, M * n))) return rc;
+    if ((rc = grow(c, c->pw_buf, M * n))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
     const PwArgs a = pw_args(c->reg, c->mdata, c->stage, c->D, 1, M, cps);
     row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
@@ -3270,7 +3180,7 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
     const int64_t groups = (slices + kPwGroup - 1) / kPwGroup;
     const int64_t o_lw = 16, o_part = o_lw + (M + 15) / 16 * 16, o_grp = o_part + slices * kPwCols * npad;
     const int64_t o_out = o_grp + groups * kPwCols * npad;
-    int rc = pw_ensure(c, o_out + (1 + n) * kPwCols);
+    int rc = grow(c, c->pw_buf, o_out + (1 + n) * kPwCols);
     if (rc) return rc;
     double* const head = c->pw_buf;
     double* const part = c->pw_buf + o_part;
@@ -3279,12 +3189,8 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
     Particles P;
     if ((rc = stage_particles(c, x, logw, M, c->pw_buf + o_lw, &P))) return rc;
     const double* const lw = P.lw;
-    if (!c->pw_ev0) {
-        HIPC(c, hipEventCreate(&c->pw_ev0));
-        HIPC(c, hipEventCreate(&c->pw_ev1));
-    }
     const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, cps);
-    HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
+    HIPC(c, c->pw_ev0.record(c->stream));
     pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
     row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
         pointwise_stats_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
@@ -3294,12 +3200,10 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
     pointwise_combine_kernel<false><<<dim3((unsigned)grid_for(n, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, n, npad, grp);
     pointwise_combine_kernel<true><<<grid_for(n, 64), 64, 0, c->stream>>>(grp, head, groups, n, npad, res);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->pw_ev1, c->stream));
+    HIPC(c, c->pw_ev1.record(c->stream));
     HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * (1 + n) * kPwCols, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
-    c->pw_ms = (double)ms;
+    HIPC(c, c->pw_ev1.since(c->pw_ev0, &c->pw_ms));
     return 0;
 }
 
@@ -3351,12 +3255,7 @@ static int ps_layout(smcn_ctx* c, const char* who, int64_t M, int64_t S_bound, P
     L->o_body = L->o_grp + L->groups * kPsBodyCols * L->npad;
     L->o_out = L->o_body + L->n * kPsBodyCols;
     L->total = L->o_out + L->n * kPsOutCols;
-    return grow_scratch(c, c->ps_buf, c->ps_len, L->total);
-}
-static int ps_events(smcn_ctx* c) {
-    for (hipEvent_t& e : c->ps_ev)
-        if (!e) HIPC(c, hipEventCreate(&e));
-    return 0;
+    return grow(c, c->ps_buf, L->total);
 }
 // header of a staged call from the caller's (mw, S)
 static int ps_put_head(smcn_ctx* c, double mw, int64_t S) {
@@ -3388,9 +3287,7 @@ static void ps_run_body(smcn_ctx* c, const PsLayout& L, const PwArgs& a, const d
     psis_body_combine_kernel<true><<<grid_for(L.n, 64), 64, 0, c->stream>>>(B + L.o_grp, L.groups, L.n, L.npad, B + L.o_body);
 }
 static int ps_elapsed(smcn_ctx* c, int slot, int e0, int e1) {
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->ps_ev[e0], c->ps_ev[e1]));
-    c->ps_ms[slot] = (double)ms;
+    HIPC(c, c->ps_ev[e1].since(c->ps_ev[e0], &c->ps_ms[slot]));
     return 0;
 }
 
@@ -3402,14 +3299,14 @@ int smcn_psis_candidates(smcn_ctx* c, const double* x, const double* logw, int64
     if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_candidates: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
     PsLayout L;
     int rc = ps_layout(c, "smcn_psis_candidates", M, S, &L);
-    if (rc || (rc = ps_events(c)) || (rc = ps_put_head(c, mw, S))) return rc;
+    if (rc || (rc = ps_put_head(c, mw, S))) return rc;
     Particles P;
     if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
     const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
-    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    HIPC(c, c->ps_ev[0].record(c->stream));
     ps_run_candidates(c, L, a, P.lw);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    HIPC(c, c->ps_ev[1].record(c->stream));
     HIPC(c, hipMemcpyAsync(cand, c->ps_buf + L.o_clr, sizeof(double) * 2 * L.n * L.stride, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
     return ps_elapsed(c, 0, 0, 1);
@@ -3422,15 +3319,15 @@ int smcn_psis_body(smcn_ctx* c, const double* x, const double* logw, int64_t M, 
     if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_body: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
     PsLayout L;
     int rc = ps_layout(c, "smcn_psis_body", M, S, &L);
-    if (rc || (rc = ps_events(c)) || (rc = ps_put_head(c, mw, S))) return rc;
+    if (rc || (rc = ps_put_head(c, mw, S))) return rc;
     Particles P;
     if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
     HIPC(c, hipMemcpyAsync(c->ps_buf + L.o_cut, cutoff, sizeof(double) * L.n, hipMemcpyHostToDevice, c->stream));
     const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
-    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    HIPC(c, c->ps_ev[0].record(c->stream));
     ps_run_body(c, L, a, P.lw);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    HIPC(c, c->ps_ev[1].record(c->stream));
     HIPC(c, hipMemcpyAsync(body, c->ps_buf + L.o_body, sizeof(double) * L.n * kPsBodyCols, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
     return ps_elapsed(c, 1, 0, 1);
@@ -3446,15 +3343,15 @@ int smcn_psis_fit(smcn_ctx* c, const double* cand, const double* body, int64_t n
                     std::to_string(kPsMaxTail));
     // ps_buf: [header 16 | candidates lr, ll [n][stride] | body [n][4] | out [n][6]]
     const int64_t o_c = 16, o_b = o_c + 2 * n_obs * stride, o_o = o_b + n_obs * kPsBodyCols;
-    int rc = grow_scratch(c, c->ps_buf, c->ps_len, o_o + n_obs * kPsOutCols);
-    if (rc || (rc = ps_events(c)) || (rc = ps_put_head(c, mw, S))) return rc;
+    int rc = grow(c, c->ps_buf, o_o + n_obs * kPsOutCols);
+    if (rc || (rc = ps_put_head(c, mw, S))) return rc;
     double* const B = c->ps_buf;
     HIPC(c, hipMemcpyAsync(B + o_c, cand, sizeof(double) * 2 * n_obs * stride, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(B + o_b, body, sizeof(double) * n_obs * kPsBodyCols, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    HIPC(c, c->ps_ev[0].record(c->stream));
     psis_fit_kernel<<<(int)n_obs, kPsBlock, 0, c->stream>>>(B + o_c, B + o_c + n_obs * stride, B + o_b, B, (int)stride, B + o_o);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    HIPC(c, c->ps_ev[1].record(c->stream));
     HIPC(c, hipMemcpyAsync(out, B + o_o, sizeof(double) * n_obs * kPsOutCols, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
     return ps_elapsed(c, 2, 0, 1);
@@ -3467,20 +3364,20 @@ int smcn_psis_loo(smcn_ctx* c, const double* x, const double* logw, int64_t M, d
     // S <= M is known on the device only: the candidate rows are laid out for S = M, the kernels read S from the header
     PsLayout L;
     int rc = ps_layout(c, "smcn_psis_loo", M, M, &L);
-    if (rc || (rc = ps_events(c))) return rc;
+    if (rc) return rc;
     Particles P;
     if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
     const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
     double* const B = c->ps_buf;
-    HIPC(c, hipEventRecord(c->ps_ev[0], c->stream));
+    HIPC(c, c->ps_ev[0].record(c->stream));
     pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(P.lw, M, B);
     ps_run_candidates(c, L, a, P.lw);
-    HIPC(c, hipEventRecord(c->ps_ev[1], c->stream));
+    HIPC(c, c->ps_ev[1].record(c->stream));
     ps_run_body(c, L, a, P.lw);
-    HIPC(c, hipEventRecord(c->ps_ev[2], c->stream));
+    HIPC(c, c->ps_ev[2].record(c->stream));
     psis_fit_kernel<<<(int)L.n, kPsBlock, 0, c->stream>>>(B + L.o_clr, B + L.o_cll, B + L.o_body, B, (int)L.stride, B + L.o_out);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->ps_ev[3], c->stream));
+    HIPC(c, c->ps_ev[3].record(c->stream));
     HIPC(c, hipMemcpyAsync(out, B + L.o_out, sizeof(double) * L.n * kPsOutCols, hipMemcpyDeviceToHost, c->stream));
     if (head_out) HIPC(c, hipMemcpyAsync(head_out, B, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
@@ -3525,29 +3422,15 @@ SmLayout sm_layout(const smcn_ctx* c) {
     return L;
 }
 }  // namespace
-static int sm_events(smcn_ctx* c) {
-    for (hipEvent_t& e : c->sm_ev)
-        if (!e) HIPC(c, hipEventCreate(&e));
-    return 0;
-}
 // waits for the stream and adds the time between sm_ev[0] and sm_ev[last] to the call's device time
 static int sm_finish(smcn_ctx* c, int last) {
     HIPC(c, stream_wait(c->stream));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->sm_ev[0], c->sm_ev[last]));
-    c->sm_ms += (double)ms;
+    double ms = 0.0;
+    HIPC(c, c->sm_ev[last].since(c->sm_ev[0], &ms));
+    c->sm_ms += ms;
     return 0;
 }
-static int sm_hist_ensure(smcn_ctx* c) {
-    const int64_t n = (int64_t)c->sm_Dc * kSmMaxQ * 256 * 2 + c->sm_Dc;
-    if (n <= c->sm_hist_len) return 0;
-    if (c->sm_hist) (void)cached_free(c->sm_hist);
-    c->sm_hist = nullptr;
-    c->sm_hist_len = 0;
-    HIPC(c, dalloc(&c->sm_hist, n));
-    c->sm_hist_len = n;
-    return 0;
-}
+static int sm_hist_ensure(smcn_ctx* c) { return grow(c, c->sm_hist, (int64_t)c->sm_Dc * kSmMaxQ * 256 * 2 + c->sm_Dc); }
 static dim3 sm_grid(const smcn_ctx* c) {
     return dim3((unsigned)grid_for(c->sm_M, kSmBlock * kSmElems), (unsigned)c->sm_Dc);
 }
@@ -3573,17 +3456,10 @@ int smcn_summary_begin(smcn_ctx* c, const double* x, const double* logw, const d
     if (M > (int64_t)1 << 40) FAIL(c, "smcn_summary_begin: too many particles");
     const int Dc = v ? Dv : c->Dc;
     c->sm_stage_state = 0;
-    if (sm_words(M, Dc) > c->sm_len) {
-        if (c->sm_buf) (void)cached_free(c->sm_buf);
-        c->sm_buf = nullptr;
-        c->sm_len = 0;
-        HIPC(c, dalloc(&c->sm_buf, sm_words(M, Dc)));
-        c->sm_len = sm_words(M, Dc);
-    }
+    if (int rc = grow(c, c->sm_buf, sm_words(M, Dc))) return rc;
     c->sm_M = M;
     c->sm_Dc = Dc;
-    int rc = sm_events(c);
-    if (rc) return rc;
+    int rc = 0;
     const SmLayout L = sm_layout(c);
     const int64_t n = M * Dc;
     if (x || v) {
@@ -3593,7 +3469,7 @@ int smcn_summary_begin(smcn_ctx* c, const double* x, const double* logw, const d
         if (logw) HIPC(c, hipMemcpyAsync(L.lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
         else HIPC(c, hipMemsetAsync(L.lw, 0, sizeof(double) * M, c->stream));
     }
-    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    HIPC(c, c->sm_ev[0].record(c->stream));
     if (x) {                    // [M][D] through the model's constrain path, then coordinate-major
         if (has_constrain_pass(c))
             launch_constrain_pass(c, c->stage, c->stage2, M, M, c->D, 1);
@@ -3615,7 +3491,7 @@ int smcn_summary_begin(smcn_ctx* c, const double* x, const double* logw, const d
     sm_total_kernel<<<grid_for(M, kSmBlock), kSmBlock, 0, c->stream>>>(L.lw, M, L.head, L.tot + 2);
     sm_total_final_kernel<<<1, 64, 0, c->stream>>>(L.tot + 2, L.head);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    HIPC(c, c->sm_ev[1].record(c->stream));
     HIPC(c, hipMemcpyAsync(head, L.head, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
     c->sm_ms = 0.0;
     for (double& p : c->sm_pass_ms) p = 0.0;
@@ -3631,10 +3507,10 @@ int smcn_summary_weights(smcn_ctx* c, double lw_max, double lw_sum, double* mass
         FAIL(c, "smcn_summary_weights: bad arguments (no particle with positive weight?)");
     const SmLayout L = sm_layout(c);
     HIPC(c, hipMemsetAsync(L.tot, 0, sizeof(u64) * 2, c->stream));
-    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    HIPC(c, c->sm_ev[0].record(c->stream));
     sm_fixed_kernel<<<grid_for(c->sm_M, kSmBlock), kSmBlock, 0, c->stream>>>(L.lw, c->sm_M, lw_max, lw_sum, L.fw, L.tot);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    HIPC(c, c->sm_ev[1].record(c->stream));
     u64 tot = 0;
     HIPC(c, hipMemcpyAsync(&tot, L.tot, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     int rc = sm_finish(c, 1);
@@ -3665,21 +3541,17 @@ int smcn_summary_select(smcn_ctx* c, int nq, const double* thr) {
     HIPC(c, hipMemcpyAsync(L.thr0, c->sm_thr_h.data(), sizeof(u64) * kSmMaxQ, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemsetAsync(L.nan, 0, sizeof(int) * c->sm_Dc, c->stream));
     c->sm_cur = 0;
-    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    HIPC(c, c->sm_ev[0].record(c->stream));
     for (int pass = 0; pass < 8; ++pass) {
         if ((rc = sm_launch_hist(c, L, nq, pass))) return rc;
         sm_pick_kernel<<<c->sm_Dc * nq, 256, 0, c->stream>>>(c->sm_hist, L.pfx[c->sm_cur], L.thr[c->sm_cur], L.thr0,
                                                              L.pfx[c->sm_cur ^ 1], L.thr[c->sm_cur ^ 1], nq, pass);
         HIPC(c, hipGetLastError());
         c->sm_cur ^= 1;
-        HIPC(c, hipEventRecord(c->sm_ev[pass + 1], c->stream));
+        HIPC(c, c->sm_ev[pass + 1].record(c->stream));
     }
     if ((rc = sm_finish(c, 8))) return rc;
-    for (int pass = 0; pass < 8; ++pass) {
-        float ms = 0.f;
-        HIPC(c, hipEventElapsedTime(&ms, c->sm_ev[pass], c->sm_ev[pass + 1]));
-        c->sm_pass_ms[pass] = (double)ms;
-    }
+    for (int pass = 0; pass < 8; ++pass) HIPC(c, c->sm_ev[pass + 1].since(c->sm_ev[pass], &c->sm_pass_ms[pass]));
     return 0;
 }
 
@@ -3698,16 +3570,14 @@ int smcn_summary_hist(smcn_ctx* c, int pass, int nq, double* out) {
     }
     const int64_t n = (int64_t)c->sm_Dc * (pass == 0 ? 1 : nq) * 256 + c->sm_Dc;
     double* const dout = (double*)(c->sm_hist + (int64_t)c->sm_Dc * kSmMaxQ * 256);
-    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    HIPC(c, c->sm_ev[0].record(c->stream));
     if ((rc = sm_launch_hist(c, L, nq, pass))) return rc;
     sm_export_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->sm_hist, L.pfx[c->sm_cur], L.nan, c->sm_Dc, nq, pass, dout);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    HIPC(c, c->sm_ev[1].record(c->stream));
     HIPC(c, hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     if ((rc = sm_finish(c, 1))) return rc;
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->sm_ev[0], c->sm_ev[1]));
-    c->sm_pass_ms[pass] = (double)ms;
+    HIPC(c, c->sm_ev[1].since(c->sm_ev[0], &c->sm_pass_ms[pass]));
     return 0;
 }
 
@@ -3758,12 +3628,12 @@ int smcn_summary_cdf(smcn_ctx* c, int T, const double* at, double* out) {
     HIPC(c, hipMemcpyAsync(L.thr_at, at, sizeof(double) * S, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemsetAsync(L.cnt, 0, sizeof(u64) * S, c->stream));
     HIPC(c, hipMemsetAsync(nan, 0, sizeof(int) * c->sm_Dc, c->stream));
-    HIPC(c, hipEventRecord(c->sm_ev[0], c->stream));
+    HIPC(c, c->sm_ev[0].record(c->stream));
     sm_cdf_kernel<<<sm_grid(c), kSmBlock, 0, c->stream>>>(L.vals, c->sm_M, L.fw, L.thr_at, T, L.cnt, nan);
     double* const dout = L.cdf_out;
     sm_counts_kernel<<<grid_for(S + c->sm_Dc, 256), 256, 0, c->stream>>>(L.cnt, nan, S, c->sm_Dc, dout);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->sm_ev[1], c->stream));
+    HIPC(c, c->sm_ev[1].record(c->stream));
     HIPC(c, hipMemcpyAsync(out, dout, sizeof(double) * (S + c->sm_Dc), hipMemcpyDeviceToHost, c->stream));
     return sm_finish(c, 1);
 }
@@ -3812,20 +3682,12 @@ int smcn_cov_partials(smcn_ctx* c, double lw_max, const double* centre, int64_t 
     const int64_t nch = (M + kCovCentreChunk - 1) / kCovCentreChunk;
     const int64_t o_c = (M + 15) / 16 * 16, o_part = o_c + 16 * T, o_grp = o_part + slices * entries;
     const int64_t o_out = o_grp + groups * entries, o_cp = o_out + (int64_t)Da * Da, words = o_cp + 2 * Dc * nch;
-    if (words > c->cov_len) {
-        if (c->cov_buf) (void)cached_free(c->cov_buf);
-        c->cov_buf = nullptr;
-        c->cov_len = 0;
-        HIPC(c, dalloc(&c->cov_buf, words));
-        c->cov_len = words;
-    }
-    for (hipEvent_t& e : c->cov_ev)
-        if (!e) HIPC(c, hipEventCreate(&e));
+    if (int rc = grow(c, c->cov_buf, words)) return rc;
     const SmLayout L = sm_layout(c);
     double *const w = c->cov_buf, *const cen = c->cov_buf + o_c, *const part = c->cov_buf + o_part;
     double *const grp = c->cov_buf + o_grp, *const res = c->cov_buf + o_out;
     if (centre) HIPC(c, hipMemcpyAsync(cen, centre, sizeof(double) * Dc, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipEventRecord(c->cov_ev[0], c->stream));
+    HIPC(c, c->cov_ev[0].record(c->stream));
     cov_weight_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(L.lw, M, lw_max, w);
     if (!centre) {
         double* const cp = c->cov_buf + o_cp;
@@ -3840,13 +3702,11 @@ int smcn_cov_partials(smcn_ctx* c, double lw_max, const double* centre, int64_t 
         cov_combine_kernel<true><<<grid_for(entries, 256), 256, 0, c->stream>>>(grp, groups, entries, T, Da, res);
     }
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->cov_ev[1], c->stream));
+    HIPC(c, c->cov_ev[1].record(c->stream));
     if (out) HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * Da * Da, hipMemcpyDeviceToHost, c->stream));
     if (centre_out) HIPC(c, hipMemcpyAsync(centre_out, cen, sizeof(double) * Dc, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->cov_ev[0], c->cov_ev[1]));
-    c->cov_ms = (double)ms;
+    HIPC(c, c->cov_ev[1].since(c->cov_ev[0], &c->cov_ms));
     return 0;
 }
 
@@ -3965,7 +3825,7 @@ int smcn_predict_set_data(smcn_ctx* c, const double* block, int64_t len, int has
     if (L.D != c->D) FAIL(c, "smcn_predict_set_data: the new rows give another dimension than the training data");
     reg_repack(L, full.data(), mup);
     c->pr.n = 0;
-    const int rc = grow_scratch(c, c->pr_md, c->pr_md_len, L.rlen);
+    const int rc = grow(c, c->pr_md, L.rlen);
     if (rc) return rc;
     HIPC(c, hipMemcpyAsync(c->pr_md, mup.data(), sizeof(double) * L.rlen, hipMemcpyHostToDevice, c->stream));
     HIPC(c, stream_wait(c->stream));                             // (mup is a local)
@@ -3997,7 +3857,7 @@ int smcn_predict_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
     if (tiles * slices > 2147483647LL) FAIL(c, "smcn_predict_loglik: too many rows");
     int rc = ensure_stage(c, M * c->D);
     if (rc) return rc;
-    if ((rc = pw_ensure(c, M * m))) return rc;
+    if ((rc = grow(c, c->pw_buf, M * m))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
     pr_launch<false>(c, c->stage, c->D, 1, M, cps, tiles, tiles * slices, nullptr, nullptr, c->pw_buf);
     HIPC(c, hipGetLastError());
@@ -4022,7 +3882,7 @@ int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int6
     const int64_t groups = (slices + kPwGroup - 1) / kPwGroup;
     const int64_t o_lw = 16, o_part = o_lw + (M + 15) / 16 * 16, o_grp = o_part + slices * Q * mpad;
     const int64_t o_out = o_grp + groups * Q * mpad;
-    int rc = pw_ensure(c, o_out + (1 + m) * Q);
+    int rc = grow(c, c->pw_buf, o_out + (1 + m) * Q);
     if (rc) return rc;
     double* const head = c->pw_buf;
     double* const part = c->pw_buf + o_part;
@@ -4031,22 +3891,16 @@ int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int6
     Particles P;
     if ((rc = stage_particles(c, x, logw, M, c->pw_buf + o_lw, &P))) return rc;
     const double* const lw = P.lw;
-    if (!c->pw_ev0) {
-        HIPC(c, hipEventCreate(&c->pw_ev0));
-        HIPC(c, hipEventCreate(&c->pw_ev1));
-    }
-    HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
+    HIPC(c, c->pw_ev0.record(c->stream));
     pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
     pr_launch<true>(c, P.xd, P.rs, P.cs, M, cps, tiles, tiles * slices, lw, head, part);
     predict_combine_kernel<false><<<dim3((unsigned)grid_for(m, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, m, mpad, Q, mom, grp);
     predict_combine_kernel<true><<<grid_for(m, 64), 64, 0, c->stream>>>(grp, head, groups, m, mpad, Q, mom, res);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->pw_ev1, c->stream));
+    HIPC(c, c->pw_ev1.record(c->stream));
     HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * (1 + m) * Q, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
-    c->pr_ms = (double)ms;
+    HIPC(c, c->pw_ev1.since(c->pw_ev0, &c->pr_ms));
     return 0;
 }
 
@@ -4138,7 +3992,7 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
     const int64_t o_lw = 16, o_w = o_lw + pad(M), o_loc = o_w + pad(M), o_tt = o_loc + pad(M), o_to = o_tt + pad(nt);
     const int64_t o_anc = o_to + pad(nt + 1), o_ng = o_anc + pad(n), o_xg = o_ng + pad(m), o_y = o_xg + pad(n * c->D);
     const int64_t need = o_y + n * m;
-    int rc = grow_scratch(c, c->dr_buf, c->dr_len, need);
+    int rc = grow(c, c->dr_buf, need);
     if (rc) return rc;
     double* const B = c->dr_buf;
     double* const head = B;
@@ -4149,11 +4003,7 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
     const double* const lw = P.lw;
     if (new_group) HIPC(c, hipMemcpyAsync(ng, new_group, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
     if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
-    if (!c->pw_ev0) {
-        HIPC(c, hipEventCreate(&c->pw_ev0));
-        HIPC(c, hipEventCreate(&c->pw_ev1));
-    }
-    HIPC(c, hipEventRecord(c->pw_ev0, c->stream));
+    HIPC(c, c->pw_ev0.record(c->stream));
     if (!ancestors) {
         pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
         draws_weights_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(lw, head, M, B + o_w);
@@ -4165,15 +4015,13 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
     const DrawArgs d{seed, s_first, new_group ? ng : nullptr};
     dr_launch(c, B + o_xg, n, d, B + o_y);
     HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(c->pw_ev1, c->stream));
+    HIPC(c, c->pw_ev1.record(c->stream));
     double cnt = 1.0;
     if (!ancestors) HIPC(c, hipMemcpyAsync(&cnt, head + 3, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (ancestors_out) HIPC(c, hipMemcpyAsync(ancestors_out, anc, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(y_out, B + o_y, sizeof(double) * n * m, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
-    float ms = 0.f;
-    HIPC(c, hipEventElapsedTime(&ms, c->pw_ev0, c->pw_ev1));
-    c->dr_ms = (double)ms;
+    HIPC(c, c->pw_ev1.since(c->pw_ev0, &c->dr_ms));
     if (cnt == 0.0) FAIL(c, "smcn_predict_draws: no particle has a finite log-weight");
     if (n_bad_out) {
         int64_t nb = 0;
@@ -4217,25 +4065,22 @@ extern "C" {
 int smcn_measure_peaks(smcn_ctx* c, double out[3]) {
     CHECK_CTX(c);
     if (!out) FAIL(c, "smcn_measure_peaks: null");
-    struct Events {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    HIPC(c, hipEventCreate(&ev.e0));
-    HIPC(c, hipEventCreate(&ev.e1));
+    Event e0, e1;
+    HIPC(c, e0.create());
+    HIPC(c, e1.create());
     const size_t bytes = (size_t)1 << 30, n = bytes / sizeof(double2);
-    struct Buf { void* p = nullptr; ~Buf() { if (p) (void)cached_free(p, false, /*keep=*/false); } } a, b;   // 2 x 1 GiB of scratch: back to the driver
+    struct Scratch { void* p = nullptr; ~Scratch() { if (p) (void)cached_free(p, false, /*keep=*/false); } } a, b;   // 2 x 1 GiB of scratch: back to the driver
     HIPC(c, cached_malloc((void**)&a.p, bytes));
     HIPC(c, cached_malloc((void**)&b.p, bytes));
     HIPC(c, hipMemsetAsync(a.p, 0, bytes, c->stream));
-    float best = 1e30f;
+    double best = 1e30;
     for (int rep = 0; rep < 8; ++rep) {
-        HIPC(c, hipEventRecord(ev.e0, c->stream));
+        HIPC(c, e0.record(c->stream));
         peak_copy_kernel<<<c->num_cu * 8, 256, 0, c->stream>>>((const double2*)a.p, (double2*)b.p, n);
-        HIPC(c, hipEventRecord(ev.e1, c->stream));
-        HIPC(c, hipEventSynchronize(ev.e1));
-        float ms = 0.f;
-        HIPC(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+        HIPC(c, e1.record(c->stream));
+        HIPC(c, e1.wait());
+        double ms = 0.0;
+        HIPC(c, e1.since(e0, &ms));
         if (rep > 1 && ms < best) best = ms;
     }
     out[0] = 2.0 * (double)bytes / best / 1e6;
@@ -4244,14 +4089,14 @@ int smcn_measure_peaks(smcn_ctx* c, double out[3]) {
         const size_t lds = waves == 1 ? 36 * 1024 : 8 * 1024;     // 4 / 16 one-wavefront blocks per CU
         HIPC(c, hipFuncSetAttribute((const void*)peak_fma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const int grid = c->num_cu * 4 * waves;
-        best = 1e30f;
+        best = 1e30;
         for (int rep = 0; rep < 6; ++rep) {
-            HIPC(c, hipEventRecord(ev.e0, c->stream));
+            HIPC(c, e0.record(c->stream));
             peak_fma_kernel<<<grid, 64, lds, c->stream>>>((double*)b.p, iters, 1.0000001, 1e-9);
-            HIPC(c, hipEventRecord(ev.e1, c->stream));
-            HIPC(c, hipEventSynchronize(ev.e1));
-            float ms = 0.f;
-            HIPC(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+            HIPC(c, e1.record(c->stream));
+            HIPC(c, e1.wait());
+            double ms = 0.0;
+            HIPC(c, e1.since(e0, &ms));
             if (rep > 1 && ms < best) best = ms;
         }
         out[1 + wv] = (double)grid * iters * 16.0 * 64.0 * 2.0 / best / 1e9;
@@ -4277,8 +4122,8 @@ int smcn_timers(smcn_ctx* c, double out[6], int reset) {
     CHECK_CTX(c);
     HIPC(c, stream_wait(c->stream));
     for (int i = 0; i < c->ev_n; ++i) {
-        float ms = 0.f;
-        HIPC(c, hipEventElapsedTime(&ms, c->ev0[i], c->ev1[i]));
+        double ms = 0.0;
+        HIPC(c, c->ev1[i].since(c->ev0[i], &ms));
         c->nuts_ms += ms;
         c->nuts_launches++;
     }
