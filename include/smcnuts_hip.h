@@ -397,6 +397,14 @@ int smcn_block_stats(smcn_ctx* ctx, int64_t k0, int B, int world, int rank, doub
                      int final_block /* the run ends with this block: the scalar history is downloaded behind it */);
 int smcn_block_wait(smcn_ctx* ctx, int B, int* n_ok, int* resample_next);
 int smcn_block_commit(smcn_ctx* ctx, int64_t k0, int n_ok);
+/* What smcn_block_post / smcn_block_stats enqueue behind the NUTS launch of an arma block.  1 (default): one streaming
+ * kernel (unpack + re-weight + the generations + their block partials, from registers) and one tail kernel (shard
+ * partials, counts and, one shard, the combine of smcn_block_stats, which then launches nothing when it brings the
+ * launch's phi and n_total = N).  0: the separate launches these replace (post, counts, partials, reduce, copy, combine
+ * behind counters cleared in front of the NUTS launch).  Every output has the same bits either way; 0 is the reference of
+ * tests/test_gpu_block_post.py.  Blocks of 4 and more transitions over more than 131 072 particles a shard run the
+ * separate launches under both. */
+int smcn_set_block_post(smcn_ctx* ctx, int mode);
 /* ESS (samples.py:113) of the B generations of the block smcn_block_wait returned for. */
 int smcn_block_ess(smcn_ctx* ctx, int B, double* out);
 int smcn_fuse_finish(smcn_ctx* ctx, int64_t k0, int B, int world, int rank, double n_total, double phi,

@@ -28,6 +28,7 @@
 #include "smcn_weights.hpp"
 #include "smcn_glk.hpp"
 #include "smcn_step.hpp"
+#include "smcn_block_post.hpp"
 #include "smcn_comm.hpp"
 #include "smcn_pointwise.hpp"
 #include "smcn_predict.hpp"
@@ -154,6 +155,20 @@ struct smcn_ctx {
     int lane_segments = 0;     // nuts3_kernel, fewer lanes than particles: segments a block is worked off in (0: auto, 1: whole blocks)
     Buf<unsigned long long> handover;  // [N][segments - 1][VH + 1 pairs] (lane queue: x', running log-weight between segments)
     bool plain_block = false;  // the last smcn_fuse_run ran ONE transition of a model without fused transitions
+    // pipelined blocks (smcn_block_*): what follows the NUTS launch (smcn_set_block_post)
+    int block_post_mode = 1;   // 1: block_stream_kernel + block_tail_kernel (smcn_block_post.hpp); 0: the separate launches
+    bool cnt_zeroed = false;   // smcn_block_launch cleared the block's counters (mode 0 accumulates into them)
+    int streamed_g = 0;        // > 0: the post pass of the block was block_stream_kernel on this many cells per generation
+    double block_phi = 1.0;    // the block's temperature as smcn_block_launch got it
+    // the tail kernel of a one-shard block combines as well, with the arguments smcn_block_stats is expected to bring;
+    // smcn_block_stats launches nothing when it brings exactly these (and nobody has rewritten gathB in between)
+    struct { int64_t k0 = -1; int B = 0; double n_total = 0.0, phi = 0.0; } tail_combined;
+    // ... and leaves the block's last generation in x_next / logw_next as well: smcn_block_commit of the WHOLE block swaps
+    // them in instead of copying the generation out of the history -- only while nothing but the block's own entry points
+    // (statistics, exchange, wait) has been called since that post pass; anything else falls back to the copies.
+    Buf<double> x_next, logw_next;
+    uint64_t api_seq = 0;      // entry points called on this context (CHECK_CTX)
+    struct { uint64_t seq = 0; int64_t k0 = -1; int B = 0; } next;
     // in-library shard exchange (RCCL) and the routed global resampling (smcn_gres_*)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -221,6 +236,7 @@ struct smcn_ctx {
 
 #define CHECK_CTX(c)             \
     if (!(c)) return -1;         \
+    ++(c)->api_seq;              \
     (void)hipSetDevice((c)->device)
 #define HIPC(c, call)                                                                         \
     do {                                                                                      \
@@ -258,6 +274,28 @@ static int final_grid(int nv) { return nv < 1 ? 1 : (nv < 1024 ? nv : 1024); }  
 static int red_grid(int64_t n) {
     int g = grid_for(n, kRedBlock);
     return g < 1 ? 1 : (g > kMaxPart ? kMaxPart : g);
+}
+constexpr int64_t part_doubles(int D) { return (int64_t)kMaxPart * (4 * D * D + 2 * D + 8); }   // smcn_ctx::part
+// blocks per generation of the generation statistics (gen_partials_kernel) over ngen generations at once
+static int partials_grid(const smcn_ctx* c, int ngen) {
+    int g = red_grid(c->N);
+    // many generations at once: fewer, fatter blocks (the kernel is a chain of block reductions; at one element per
+    // thread it was latency-bound: 46 us for 20 generations of 65 536 particles)
+    if (ngen >= 4 && g > 64) g = 64;
+    if (c->D >= 64 && g > 128) g = 128;   // wide particles: 2 block reductions per coordinate -- four particles per thread
+                                          // between them (measured at D = 256, N = 131 072: 155 us against 197 at 512 blocks)
+    const int NQB = gen_block_nq(c->Dc);   // block partials: [max, cnt, s1, s2, A.., B.., reference point..]
+    while ((int64_t)g * NQB * ngen > part_doubles(c->D) && g > 1) g /= 2;
+    return g;
+}
+// Particles a thread of block_stream_kernel holds (4 or 8: its instances) when a pipelined block of B transitions takes
+// the fused post pass (smcn_block_post.hpp); 0: the separate launches -- smcn_set_block_post(0), another model, or more
+// than 8 particles per thread (beyond 131 072 particles a shard in blocks of 4 and more).
+static int block_stream_slots(const smcn_ctx* c, int B) {
+    if (c->block_post_mode != 1 || !c->lane_kernel || c->D != ArmaLaneModel::D || c->Dc != c->D) return 0;
+    const int64_t threads = (int64_t)partials_grid(c, B) * kRedBlock;
+    const int64_t per_thread = (c->N + threads - 1) / threads;
+    return per_thread <= 4 ? 4 : per_thread <= 8 ? 8 : 0;
 }
 
 // ---- device memory ---------------------------------------------------------------------------------------------------
@@ -745,6 +783,14 @@ int smcn_set_wide_eval(smcn_ctx* c, int on) {
     CHECK_CTX(c);
     if (on != 0 && on != 1) FAIL(c, "smcn_set_wide_eval: 0 or 1");
     c->wide_eval = on;
+    return 0;
+}
+// pipelined fused blocks: what runs between the NUTS launch and the host's wait.  1 (default): one streaming kernel and
+// one tail kernel (smcn_block_post.hpp); 0: the separate launches they replace -- same bits, kept as the tests' reference.
+int smcn_set_block_post(smcn_ctx* c, int mode) {
+    CHECK_CTX(c);
+    if (mode != 0 && mode != 1) FAIL(c, "smcn_set_block_post: 0 (separate launches) or 1 (fused)");
+    c->block_post_mode = mode;
     return 0;
 }
 
@@ -1276,16 +1322,17 @@ int smcn_moment_sums_of(smcn_ctx* c, const double* v, int Dc, const double* shif
 // ---- resampling -------------------------------------------------------------------------------
 // forward-L re-weighting and the acceptance count of the device-resident loop: from the NUTS kernel's own per-particle
 // |r|^2, |r'|^2 and moved flags when it wrote them (wave-per-particle kernels), else by passes over r, r', x, x'
-static void enqueue_reweight_forward(smcn_ctx* c) {
+static int enqueue_reweight_forward(smcn_ctx* c) {
     const int64_t N = c->N;
     if (c->kin_valid)
         reweight_kin_kernel<<<grid_for(N, 256), 256, 0, c->stream>>>(c->logw, c->lpri0, c->llik0, c->lpri1, c->llik1, c->kin0,
                                                                      c->kin1, c->logw_new, N, c->D);
     else {
-        (void)momentum_dn(c);
+        if (int rc = momentum_dn(c)) return rc;
         reweight_kernel<<<grid_for(N, 256), 256, 0, c->stream>>>(c->logw, c->lpri0, c->llik0, c->lpri1, c->llik1, c->r,
                                                                  c->r_new, nullptr, nullptr, c->logw_new, N, c->D);
     }
+    return 0;
 }
 static void enqueue_moved_count(smcn_ctx* c, int g, double* part) {
     if (c->kin_valid) isum_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(c->moved_i, c->N, part);
@@ -1662,6 +1709,25 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
         if (rc) return rc;
     }
     if (phase == 1) return 0;
+    c->streamed_g = 0;
+    if (const int slots = (phase == 2 && fuse_reweight && gen_x && gen_logw && cnt) ? block_stream_slots(c, B) : 0) {
+        // a pipelined block's post pass and its generation statistics in one launch (smcn_block_post.hpp): the cells of
+        // gen_partials_kernel's grid, a thread's particles in registers
+        const int g = partials_grid(c, B);
+        if ((int64_t)g * B * (gen_block_nq(D) + 2) > part_doubles(c->D)) FAIL(c, "nuts3: block partials do not fit");
+        double* const cntpart = c->part + (int64_t)g * B * gen_block_nq(D);
+        auto stream = [&](auto kr) {
+            block_stream_kernel<D, decltype(kr)::value><<<dim3(g, B), kRedBlock, 0, c->stream>>>(
+                c->out_rec, c->in_rec, c->x, c->logw, c->x_new, c->r_new, c->lpri0, c->llik0, c->lpri1, c->llik1,
+                c->nleap, c->depth, c->ndraws, c->flags, c->logw_new, c->x_next, c->logw_next, gen_x, gen_logw, N, B,
+                c->cmodel, c->part, cntpart);
+        };
+        if (slots == 4) stream(std::integral_constant<int, 4>{});
+        else stream(std::integral_constant<int, 8>{});
+        HIPC(c, hipGetLastError());
+        c->streamed_g = g;
+        return 0;
+    }
     nuts2_post_kernel<D><<<grid_for(N, 256), 256, 0, c->stream>>>(
         c->out_rec, c->in_rec, c->x, fuse_reweight ? c->logw : nullptr, c->x_new, c->r_new, c->lpri0, c->llik0,
         c->lpri1, c->llik1, c->nleap, c->depth, c->ndraws, c->flags, fuse_reweight ? c->logw_new : nullptr, gen_x,
@@ -2219,14 +2285,7 @@ static int enqueue_partials(smcn_ctx* c, const double* logw, const double* x, do
                             const double* shift = nullptr, int ngen = 1) {
     // ngen consecutive generations ([ngen][N] weights, [ngen][D][N] particles) in two launches
     const int64_t N = c->N;
-    int g = red_grid(N);
-    // many generations at once: fewer, fatter blocks (the kernel is a chain of block reductions; at one element per
-    // thread it was latency-bound: 46 us for 20 generations of 65 536 particles)
-    if (ngen >= 4 && g > 64) g = 64;
-    if (c->D >= 64 && g > 128) g = 128;   // wide particles: 2 block reductions per coordinate -- four particles per thread
-                                          // between them (measured at D = 256, N = 131 072: 155 us against 197 at 512 blocks)
-    const int NQB = gen_block_nq(c->Dc);   // block partials: [max, cnt, s1, s2, A.., B.., reference point..]
-    while ((int64_t)g * NQB * ngen > (int64_t)kMaxPart * (4 * c->D * c->D + 2 * c->D + 8) && g > 1) g /= 2;
+    const int g = partials_grid(c, ngen);
     const int nz = c->D >= 64 ? 8 : 1;
     if (has_constrain_pass(c)) {
         const int rc = model_constrained(c, x, ngen, &x);
@@ -2276,7 +2335,7 @@ int smcn_step_finish(smcn_ctx* c, int64_t k, int world, int rank, double n_total
     bool reweighted = false;
     int rc = propose_async(c, step_size, phi, max_depth, delta_max, k, tape, tape_off, true, &reweighted);
     if (rc) return rc;
-    if (!reweighted) enqueue_reweight_forward(c);
+    if (!reweighted && (rc = enqueue_reweight_forward(c))) return rc;
     const int g = red_grid(N);
     isum_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(c->nleap, N, c->part);
     sum_to_kernel<<<1, kRedBlock, 0, c->stream>>>(c->part, g, hk + H_LEAPS);
@@ -2325,6 +2384,10 @@ int smcn_fuse_begin(smcn_ctx* c, int Bmax, int world) {
     // lane kernel: the per-transition record buffers and the overflow tree-stack area for blocks of up to Bmax
     // transitions -- here, once, rather than at the first launch that needs them (a cold sample() spent its first
     // milliseconds in hipMalloc)
+    if (c->lane_kernel && !c->x_next) {
+        HIPC(c, c->x_next.reset(c->N * c->D));
+        HIPC(c, c->logw_next.reset(c->N));
+    }
     if (c->lane_kernel && Bmax > c->rec_cap) {
         constexpr int D = ArmaLaneModel::D;
         if (int rc = reset_records(c, Bmax, D)) return rc;
@@ -2404,7 +2467,7 @@ int smcn_fuse_run(smcn_ctx* c, int64_t k0, int B, int world, int rank, double n_
     } else {
         // models without the fused-transition kernel: one transition, generation k0+1 written here
         if (B != 1) FAIL(c, "smcn_fuse_run: this model runs one iteration per launch");
-        enqueue_reweight_forward(c);
+        if ((rc = enqueue_reweight_forward(c))) return rc;
         const int g = red_grid(N);
         isum_partial_kernel<<<g, kRedBlock, 0, c->stream>>>(c->nleap, N, c->part);
         sum_to_kernel<<<1, kRedBlock, 0, c->stream>>>(c->part, g, hk + H_LEAPS);
@@ -2504,8 +2567,12 @@ int smcn_block_launch(smcn_ctx* c, int64_t k0, int B, double step_size, double p
     if (c->fuse_max < 1 || B < 1 || B > c->fuse_max || k0 < 0 || k0 + B > c->fast_K)
         FAIL(c, "smcn_block_launch: bad iteration range / no smcn_fuse_begin");
     // the leapfrog / moved counters of the block are cleared HERE, in front of the long NUTS launch, not between it and
-    // the post kernel (the previous block's counts were copied into the history by its own smcn_block_post)
-    HIPC(c, hipMemsetAsync(c->cnt, 0, sizeof(double) * 2 * B, c->stream));
+    // the post kernel (the previous block's counts were copied into the history by its own smcn_block_post).  The fused
+    // post pass (smcn_set_block_post 1) sums per-block counts and needs no cleared counters.
+    c->cnt_zeroed = block_stream_slots(c, B) == 0;
+    if (c->cnt_zeroed) HIPC(c, hipMemsetAsync(c->cnt, 0, sizeof(double) * 2 * B, c->stream));
+    c->block_phi = phi;
+    c->tail_combined.k0 = -1;
     bool reweighted = false;
     return propose_async(c, step_size, phi, max_depth, delta_max, k0, nullptr, nullptr, true, &reweighted, B,
                          gen_x_ptr(c, k0), gen_logw_ptr(c, k0), c->cnt, 1);
@@ -2518,9 +2585,30 @@ int smcn_block_post(smcn_ctx* c, int64_t k0, int B, int world) {
         FAIL(c, "smcn_block_post: bad iteration range");
     const int HS = hist_stride(c->Dc), NQ = 4 + 2 * c->Dc;
     bool reweighted = false;
+    c->tail_combined.k0 = -1;
+    if (block_stream_slots(c, B) == 0 && !c->cnt_zeroed)   // (the mode changed since the launch, or the pass is repeated)
+        HIPC(c, hipMemsetAsync(c->cnt, 0, sizeof(double) * 2 * B, c->stream));
+    c->cnt_zeroed = false;
     int rc = propose_async(c, 0.0, 1.0, 0, 0.0, k0, nullptr, nullptr, true, &reweighted, B, gen_x_ptr(c, k0),
                            gen_logw_ptr(c, k0), c->cnt, 2);
     if (rc) return rc;
+    if (c->streamed_g > 0) {
+        // one tail launch: shard partials, counts and, one shard, the combine that smcn_block_stats would launch -- with
+        // the arguments it is expected to bring (smcn_ctx::tail_combined)
+        const double n_total = (double)c->N;
+        static_assert(kMaxPart <= kTailPerThread * kRedBlock, "block_tail_kernel: a generation's block partials in registers");
+        block_tail_kernel<ArmaLaneModel::D><<<B, kRedBlock, 0, c->stream>>>(     // (streamed_g > 0: the lane kernel's model)
+            c->part, c->streamed_g, c->part + (int64_t)c->streamed_g * B * gen_block_nq(c->Dc), c->cnt,
+            c->hist + k0 * HS + H_MEAN, c->lpB, world == 1 ? (double*)c->gathB : nullptr, c->hist + k0 * HS, HS,
+            world == 1 ? 1 : 0, n_total, log((double)c->N), c->block_phi, c->ss, c->ss_scratch, SS_SHIFT + c->Dc + 8);
+        HIPC(c, hipGetLastError());
+        if (c->x_next && c->logw_next) { c->next.seq = c->api_seq; c->next.k0 = k0; c->next.B = B; }
+        if (world == 1) {
+            c->tail_combined.k0 = k0; c->tail_combined.B = B;
+            c->tail_combined.n_total = n_total; c->tail_combined.phi = c->block_phi;
+        }
+        return 0;
+    }
     store_counts_kernel<<<1, 64, 0, c->stream>>>(c->cnt, B, c->hist + k0 * HS, HS);
     // all B generations; the variance shift of the block is the mean of generation k0 (its history row)
     rc = enqueue_partials(c, gen_logw_ptr(c, k0), gen_x_ptr(c, k0), c->lpB, c->hist + k0 * HS + H_MEAN, B);
@@ -2531,6 +2619,7 @@ int smcn_block_post(smcn_ctx* c, int64_t k0, int B, int world) {
 }
 int smcn_block_partials_get(smcn_ctx* c, int B, double* out) {
     CHECK_CTX(c);
+    if (c->next.seq + 1 == c->api_seq) c->next.seq = c->api_seq;   // (x_next / logw_next stay the block's last generation)
     if (c->fuse_max < 1 || B < 1 || B > c->fuse_max || !out) FAIL(c, "smcn_block_partials_get: bad arguments");
     HIPC(c, hipMemcpyAsync(out, c->lpB, sizeof(double) * B * (4 + 2 * c->Dc), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
@@ -2538,7 +2627,9 @@ int smcn_block_partials_get(smcn_ctx* c, int B, double* out) {
 }
 int smcn_block_partials_set(smcn_ctx* c, int B, int world, const double* in) {
     CHECK_CTX(c);
+    if (c->next.seq + 1 == c->api_seq) c->next.seq = c->api_seq;   // (x_next / logw_next stay the block's last generation)
     if (c->fuse_max < 1 || B < 1 || B > c->fuse_max || !in) FAIL(c, "smcn_block_partials_set: bad arguments");
+    c->tail_combined.k0 = -1;   // the gathered partials are the caller's now: smcn_block_stats combines them
     HIPC(c, hipMemcpyAsync(c->gathB, in, sizeof(double) * world * B * (4 + 2 * c->Dc), hipMemcpyHostToDevice,
                            c->stream));
     HIPC(c, stream_wait(c->stream));
@@ -2546,14 +2637,20 @@ int smcn_block_partials_set(smcn_ctx* c, int B, int world, const double* in) {
 }
 int smcn_block_stats(smcn_ctx* c, int64_t k0, int B, int world, int rank, double n_total, double phi, int final_block) {
     CHECK_CTX(c);
+    if (c->next.seq + 1 == c->api_seq) c->next.seq = c->api_seq;   // (x_next / logw_next stay the block's last generation)
     Range roctx_range("smcn:normalise+ess");
     if (c->fuse_max < 1 || B < 1 || B > c->fuse_max || k0 < 0 || k0 + B > c->fast_K)
         FAIL(c, "smcn_block_stats: bad iteration range");
     if (world < 1 || rank < 0 || rank >= world) FAIL(c, "smcn_block_stats: bad world/rank");
     const int HS = hist_stride(c->Dc);
-    combine_ranks_gens_kernel<<<B, 64, 0, c->stream>>>(c->gathB, world, rank, c->Dc, n_total, log((double)c->N),
-                                                       c->hist + k0 * HS + H_MEAN, phi, c->hist + (k0 + 1) * HS, HS,
-                                                       c->ss, c->ss_scratch, SS_SHIFT + c->Dc + 8);
+    // (one shard, fused post pass: the tail kernel of smcn_block_post has combined already, from the same numbers)
+    const bool combined = world == 1 && c->tail_combined.k0 == k0 && c->tail_combined.B == B &&
+                          c->tail_combined.n_total == n_total && c->tail_combined.phi == phi;
+    c->tail_combined.k0 = -1;
+    if (!combined)
+        combine_ranks_gens_kernel<<<B, 64, 0, c->stream>>>(c->gathB, world, rank, c->Dc, n_total, log((double)c->N),
+                                                           c->hist + k0 * HS + H_MEAN, phi, c->hist + (k0 + 1) * HS, HS,
+                                                           c->ss, c->ss_scratch, SS_SHIFT + c->Dc + 8);
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(c->rows_h, c->hist + (k0 + 1) * HS, sizeof(double) * B * HS, hipMemcpyDeviceToHost,
                            c->stream));
@@ -2571,6 +2668,7 @@ int smcn_block_stats(smcn_ctx* c, int64_t k0, int B, int world, int rank, double
 // generation k0 + *n_ok has to (always 1 if *n_ok < B).
 int smcn_block_wait(smcn_ctx* c, int B, int* n_ok, int* resample_next) {
     CHECK_CTX(c);
+    if (c->next.seq + 1 == c->api_seq) c->next.seq = c->api_seq;   // (x_next / logw_next stay the block's last generation)
     if (c->fuse_max < 1 || B < 1 || B > c->fuse_max || !n_ok || !resample_next)
         FAIL(c, "smcn_block_wait: bad arguments");
     HIPC(c, c->ev_rows.wait());
@@ -2585,6 +2683,7 @@ int smcn_block_wait(smcn_ctx* c, int B, int* n_ok, int* resample_next) {
 // ESS of the B generations of the block just waited for (host copy; drives the block-size policy)
 int smcn_block_ess(smcn_ctx* c, int B, double* out) {
     CHECK_CTX(c);
+    if (c->next.seq + 1 == c->api_seq) c->next.seq = c->api_seq;   // (x_next / logw_next stay the block's last generation)
     if (c->fuse_max < 1 || B < 1 || B > c->fuse_max || !out) FAIL(c, "smcn_block_ess: bad arguments");
     const int HS = hist_stride(c->Dc);
     for (int g = 0; g < B; ++g) out[g] = c->rows_h[(size_t)g * HS + H_ESS];
@@ -2595,6 +2694,13 @@ int smcn_block_commit(smcn_ctx* c, int64_t k0, int ok) {   // the committed stat
     if (c->fuse_max < 1 || ok < 1 || ok > c->fuse_max || k0 < 0 || k0 + ok > c->fast_K)
         FAIL(c, "smcn_block_commit: bad arguments");
     const int64_t N = c->N;
+    const bool whole = c->next.seq + 1 == c->api_seq && c->next.k0 == k0 && c->next.B == ok;
+    c->next.k0 = -1;
+    if (whole) {     // the fused post pass left generation k0 + ok in x_next / logw_next
+        std::swap(c->x, c->x_next);
+        std::swap(c->logw, c->logw_next);
+        return 0;
+    }
     HIPC(c, hipMemcpyAsync(c->x, gen_x_ptr(c, k0) + (int64_t)(ok - 1) * N * c->D, sizeof(double) * N * c->D,
                            hipMemcpyDeviceToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->logw, gen_logw_ptr(c, k0) + (int64_t)(ok - 1) * N, sizeof(double) * N,

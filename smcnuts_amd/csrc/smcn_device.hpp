@@ -242,6 +242,38 @@ __device__ __forceinline__ double block_max(double v, double* sh) {
     __syncthreads();
     return fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
 }
+// NV of them behind ONE pair of barriers (a chain of block reductions is a chain of barrier round trips): every value goes
+// through block_sum's / block_max's own tree, so each result has the bits of a call of its own.
+template <int NV, int NS>
+__device__ __forceinline__ void block_sum_n(double (&v)[NV], double (&sh)[NS]) {
+    static_assert(NS >= 4 * NV, "one slot per wavefront and value");
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] = wave_sum(v[q]);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) sh[4 * q + w] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] = ((sh[4 * q] + sh[4 * q + 1]) + sh[4 * q + 2]) + sh[4 * q + 3];
+}
+template <int NV, int NS>
+__device__ __forceinline__ void block_max_n(double (&v)[NV], double (&sh)[NS]) {
+    static_assert(NS >= 4 * NV, "one slot per wavefront and value");
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] = wave_max(v[q]);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) sh[4 * q + w] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] = fmax(fmax(sh[4 * q], sh[4 * q + 1]), fmax(sh[4 * q + 2], sh[4 * q + 3]));
+}
 
 
 // ---- lean fp64 elementary functions for the per-leaf density evaluation ----------
