@@ -1,5 +1,7 @@
 // C ABI of libsmcnuts_hip.so (see include/smcnuts_hip.h for the contract and
-// the reference interfaces each entry point replaces).
+// the reference interfaces each entry point replaces).  This is the core unit: the context, the sampler and its loops,
+// the shard exchange, the self-tests and the timers.  The post-fit entry points are smcn_loo.hip, smcn_predict.hip and
+// smcn_summary.hip; smcn_ctx.hpp is what the units share.
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -16,8 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/smcnuts_hip.h"
-#include "smcn_devbuf.hpp"
+#include "smcn_ctx.hpp"
 #include "smcn_nuts.hpp"
 #include "smcn_nuts_wave.hpp"
 #include "smcn_nuts_fin.hpp"
@@ -29,13 +30,6 @@
 #include "smcn_glk.hpp"
 #include "smcn_step.hpp"
 #include "smcn_block_post.hpp"
-#include "smcn_comm.hpp"
-#include "smcn_pointwise.hpp"
-#include "smcn_predict.hpp"
-#include "smcn_predict_draws.hpp"
-#include "smcn_quantile.hpp"
-#include "smcn_psis.hpp"
-#include "smcn_cov.hpp"
 
 using namespace smcn;
 
@@ -62,214 +56,10 @@ struct Range {
 };
 thread_local std::string g_create_error;
 constexpr int kMaxPart = 1024;    // block partials per reduction
-constexpr int kTimerRing = 512;   // NUTS launches timed between two smcn_timers calls
 constexpr int64_t kDlChunk = 8;   // generations per staging pass of the history download
 }  // namespace
 
-// What a context owns on the device (smcn_devbuf.hpp): buffers from the per-device cache below, pinned host memory, events
-struct CacheMem { static int alloc(void** p, size_t bytes); static void free(void* p, bool synced); };
-struct PinnedMem {
-    static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes); }
-    static void free(void* p, bool) { (void)hipHostFree(p); }
-};
-struct HipEv {
-    using event = hipEvent_t;
-    using stream = hipStream_t;
-    static int create(event* e, bool timing) { return (int)(timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming)); }
-    static int record(event e, stream s) { return (int)hipEventRecord(e, s); }
-    static int wait(event e) { return (int)hipEventSynchronize(e); }
-    static int elapsed(float* ms, event from, event to) { return (int)hipEventElapsedTime(ms, from, to); }
-    static void destroy(event e) { (void)hipEventDestroy(e); }
-};
-template <class T>
-using Buf = DevBuf<T, CacheMem>;
-using Event = DevEvent<HipEv>;
-
-struct smcn_ctx {
-    int device = 0;
-    int64_t N = 0, base = 0;
-    int model = 0, D = 0, Dc = 0;
-    int cmodel = 0;   // the model id the constrained-space kernels get (constrain_coord: ids 1 and 2 exp the last coordinate)
-    int num_cu = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    uint64_t seed = 0;
-    std::string err;
-    std::vector<double> mdata_h;
-    RegLayout reg;              // the regression models: where things sit in mdata_h and in its image mdata (smcn_regdata.hpp)
-
-    // device state, all fp64; vectors are [D][N]
-    Buf<double> mdata, x, x_new, x_tmp, r, r_new;
-    Buf<double> logw, logw_new, wn, work;
-    Buf<double> lpri0, llik0, lpri1, llik1, Lg, qv;
-    Buf<double> scan_local, ttot, toff, part, scal;
-    Buf<double> glk_buf;          // device-side Gaussian L-kernel: mean, both moment sums, parameters (lazy)
-    Buf<double> glk_xchg;         // ... over shards: [local row | world gathered rows] of moment sums
-    int glk_world = 0;
-    // two-phase NUTS launches (smcn_set_nuts_cap): doublings of the first launch, records and list of the parked trees
-    int nuts_jcap = 0, nuts_wide2 = 1;
-    Buf<double> nuts_resume;
-    Buf<unsigned int> nuts_pend;
-    Buf<unsigned int> nuts_mq;    // list of the trees parked at the inner level of a launch (smcn_set_nuts_requeue)
-    Buf<double> nuts_mq_rec;      // ... and their records ([N][128])
-    int nuts_mq_b = 0;                  // ... after this many doublings (0: no inner level)
-    bool nuts_mq_used = false;          // the last proposal had an inner level (its hand-over count is checked behind the wait)
-    bool nuts_mq_ok = false;            // set by the entry points that wait for the proposal and check that count (smcn_propose_nuts)
-    int64_t nuts_parked = 0;            // trees the last launch parked
-    Buf<double> stage;  // [N*D] host<->device staging, also [M*D] for target_eval
-    Buf<double> stage2;
-    Buf<double> cstage;   // SMCN_MODEL_HGLM / ORDINAL / MLGLM: the constrained population the moment kernels read ([ngen][D][N])
-    Buf<int32_t> nleap, depth, ndraws, flags;
-    Buf<int64_t> idx;
-    Buf<unsigned int> queue;
-    Buf<double> kin0;     // wave-per-particle NUTS kernels: |r|^2, |r'|^2 and the all-coordinates-moved flag per particle
-    Buf<double> kin1;
-    Buf<int32_t> moved_i;
-    bool kin_valid = false;     // written by the last NUTS launch (consumed by the device-resident re-weighting)
-    // Momentum layout.  Targets whose particle fills a wavefront (nuts_wave_kernel: coordinate c on lane c % 64) read and
-    // write a particle's momentum as ONE contiguous row: r / r_new then hold [N][D] ("particle-major": 512-byte coalesced
-    // rows) instead of the [D][N] every other kernel uses -- converted in place (momentum_dn) before any of those reads them
-    bool r_pm = false, r_new_pm = false;
-    Buf<unsigned long long> prof;
-    Buf<double> tape_d;
-    Buf<int64_t> tape_off_d;
-    bool momentum_set = false, lg_set = false, q_set = false, u_set = false;
-    // device-resident loop (smcn_fast_*)
-    Buf<double> hist, ss, lp, gath, hist_x, hist_logw;
-    Buf<double> u_res;
-    Buf<double> in_rec, out_rec;   // nuts2 per-particle records
-    Buf<double> nuts_scratch;                  // HBM tree stacks (large D)
-    int64_t fast_K = -1;
-    bool fast_hist = false;
-    // fused transitions (smcn_super_*)
-    int fuse_max = 0;
-    int64_t rec_cap = 0;          // transitions the record buffers hold
-    int resample_scheme = 0;   // 0 multinomial (reference), 1 systematic
-    bool fused_ok = false;     // the model's NUTS kernel takes B > 1 transitions per launch
-    bool lane_kernel = false;  // NUTS by nuts3_kernel (one lane per particle)
-    int64_t arma_T = 0;        // series length of an arma context
-    Buf<double> tb_state, tb_part, tb_local, tb_gath;   // device-side ESS bisection
-    int tb_world = 0, tb_blocks = 0;
-    int wide_eval = 1;         // nuts3_kernel: lane groups evaluate a wavefront's last stragglers (smcn_set_wide_eval)
-    int64_t lane_grid_cap = 0; // nuts3_kernel: wavefronts launched at most (0: one per SIMD; < 0: no cap, a wavefront per 64 particles)
-    int lane_segments = 0;     // nuts3_kernel, fewer lanes than particles: segments a block is worked off in (0: auto, 1: whole blocks)
-    Buf<unsigned long long> handover;  // [N][segments - 1][VH + 1 pairs] (lane queue: x', running log-weight between segments)
-    bool plain_block = false;  // the last smcn_fuse_run ran ONE transition of a model without fused transitions
-    // pipelined blocks (smcn_block_*): what follows the NUTS launch (smcn_set_block_post)
-    int block_post_mode = 1;   // 1: block_stream_kernel + block_tail_kernel (smcn_block_post.hpp); 0: the separate launches
-    bool cnt_zeroed = false;   // smcn_block_launch cleared the block's counters (mode 0 accumulates into them)
-    int streamed_g = 0;        // > 0: the post pass of the block was block_stream_kernel on this many cells per generation
-    double block_phi = 1.0;    // the block's temperature as smcn_block_launch got it
-    // the tail kernel of a one-shard block combines as well, with the arguments smcn_block_stats is expected to bring;
-    // smcn_block_stats launches nothing when it brings exactly these (and nobody has rewritten gathB in between)
-    struct { int64_t k0 = -1; int B = 0; double n_total = 0.0, phi = 0.0; } tail_combined;
-    // ... and leaves the block's last generation in x_next / logw_next as well: smcn_block_commit of the WHOLE block swaps
-    // them in instead of copying the generation out of the history -- only while nothing but the block's own entry points
-    // (statistics, exchange, wait) has been called since that post pass; anything else falls back to the copies.
-    Buf<double> x_next, logw_next;
-    uint64_t api_seq = 0;      // entry points called on this context (CHECK_CTX)
-    struct { uint64_t seq = 0; int64_t k0 = -1; int B = 0; } next;
-    // in-library shard exchange (RCCL) and the routed global resampling (smcn_gres_*)
-    ncclComm_t comm = nullptr;
-    int comm_rank = 0, comm_world = 1;
-    Buf<double> g_ttot_all, g_toff_all, g_keys, g_keys_send, g_keys_recv, g_rows_send, g_rows_recv;
-    Buf<int32_t> g_dest, g_order;
-    int64_t g_serve_cap = 0;
-    int g_world = 0;
-    smcn_host_target_fn host_fn = nullptr;   // SMCN_MODEL_HOST: the caller's density
-    void* host_user = nullptr;
-    Buf<double> hc_vec, hc_sc, hc_gp, hc_gl;   // host-target NUTS state
-    Buf<int32_t> hc_st;
-    std::vector<double> hx, hlp, hll, hgp, hgl;   // host staging of the callback
-    Buf<double> n2_ovf;           // v2 kernel: overflow tree-stack levels
-    Buf<double> ss_scratch;       // pipelined blocks: step scalars of the inner generations
-    DevBuf<double, PinnedMem> rows_h;   // pinned: history rows of the block being validated
-    DevBuf<double, PinnedMem> hist_h;   // pinned: the whole scalar history, downloaded behind a run's last block
-    bool hist_h_valid = false;
-    DevEvent<HipEv, false> ev_rows;     // (no timing: only waited for)
-    hipStream_t dl_stream = nullptr;    // history download beside the loop (smcn_history_download)
-    Buf<double> dl_stage;
-    Buf<double> lpB, gathB, gen_x, gen_logw, cnt, shiftB;
-
-    // NUTS kernel timing (HIP events on the launch stream)
-    Event ev0[kTimerRing], ev1[kTimerRing];
-    int ev_n = 0;
-    double nuts_ms = 0.0;
-    int64_t nuts_launches = 0;
-
-    // pointwise criteria (smcn_pointwise_*): log-weights, slice partials and the result of a call; its kernels' time
-    Buf<double> pw_buf;
-    Event pw_ev0, pw_ev1;     // (around the kernels of smcn_predict_partials and smcn_predict_draws too)
-    double pw_ms = 0.0;
-
-    // Pareto-smoothed LOO (smcn_psis_*): header, log-weights, the staged slab of ll, candidates, cutoffs, body partials and
-    // the result of a call; device time of the stages of the last calls (candidates, body, fit, whole smcn_psis_loo)
-    Buf<double> ps_buf;
-    Event ps_ev[4];
-    double ps_ms[4] = {};
-
-    // held-out prediction (smcn_predict_*): the new rows' image [block | padding | table] as smcn_ctx_create lays out the
-    // training data, its layout (pr.n new rows, 0: none set) and whether they came with y
-    Buf<double> pr_md;
-    RegLayout pr;
-    int pr_has_y = 0;
-    double pr_ms = 0.0;
-
-    // posterior predictive draws (smcn_predict_draws): weights, scan, ancestors, gathered particles and the draws of a call
-    Buf<double> dr_buf;
-    double dr_ms = 0.0;
-
-    // posterior summaries (smcn_summary_*): the staged population of a call (constrained values, fixed-point weights,
-    // selection state), its histograms, and the device time of its kernels
-    Buf<double> sm_buf;
-    Buf<unsigned long long> sm_hist;
-    int64_t sm_M = 0;
-    int sm_Dc = 0, sm_cur = 0, sm_stage_state = 0;    // (state: 0 nothing staged, 1 values, 2 values and weights)
-    std::vector<unsigned long long> sm_pfx_h, sm_thr_h;
-    Event sm_ev[10];
-    double sm_ms = 0.0, sm_pass_ms[8] = {};
-    // posterior covariance (smcn_cov_*): weights, centre, slice and group partials, result
-    Buf<double> cov_buf;
-    Event cov_ev[2];
-    double cov_ms = 0.0;
-};
-
-#define CHECK_CTX(c)             \
-    if (!(c)) return -1;         \
-    ++(c)->api_seq;              \
-    (void)hipSetDevice((c)->device)
-#define HIPC(c, call)                                                                         \
-    do {                                                                                      \
-        const hipError_t e_ = (hipError_t)(call);                                                            \
-        if (e_ != hipSuccess) {                                                               \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                     \
-            return -2;                                                                        \
-        }                                                                                     \
-    } while (0)
-// Waiting for the stream: a blocking hipStreamSynchronize wakes the host ~20-30 us after the last kernel has ended (interrupt,
-// scheduler), and a step-by-step iteration waits a dozen times for kernels of a few microseconds.  So: poll the stream for a
-// short while first (a query is ~1 us), then block.  SMCN_SPIN_US (default 120) bounds the polling, 0 switches it off.
-static inline hipError_t stream_wait(hipStream_t s) {
-    static const long spin_us = [] { const char* e = getenv("SMCN_SPIN_US"); return e ? atol(e) : 120L; }();
-    if (spin_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            const hipError_t q = hipStreamQuery(s);
-            if (q != hipErrorNotReady) return q;
-            if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() >= spin_us) break;
-        }
-    }
-    return hipStreamSynchronize(s);
-}
-
-#define FAIL(c, msg)      \
-    do {                  \
-        (c)->err = (msg); \
-        return -3;        \
-    } while (0)
-
 static int dl_prepare(smcn_ctx* c);
-static int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 static int final_grid(int nv) { return nv < 1 ? 1 : (nv < 1024 ? nv : 1024); }   // sum_final_kernel: a block per vector
 static int red_grid(int64_t n) {
     int g = grid_for(n, kRedBlock);
@@ -394,19 +184,8 @@ hipError_t cached_free(void* p, bool synced = false, bool keep = true) {
 }  // namespace
 int CacheMem::alloc(void** p, size_t bytes) { return (int)cached_malloc(p, bytes); }
 void CacheMem::free(void* p, bool synced) { (void)cached_free(p, synced); }
-// A buffer that may still be in use grows behind a wait for the context's stream.  (Buffers made lazily as a SET are asked
-// for by the set's LAST member -- `if (!c->moved_i)` for kin0, kin1, moved_i -- so that a set a failed allocation left
-// incomplete is made again; a capacity that is no length -- rec_cap, g_world -- is 0 while its buffers are being made.)
-template <class B>
-static int grow(smcn_ctx* c, B& buf, int64_t need) {
-    if (need <= buf.len()) return 0;
-    HIPC(c, stream_wait(c->stream));
-    HIPC(c, buf.grow(need));
-    return 0;
-}
 
 #ifdef SMCN_TRACE_SETUP   // (diagnostic build: where a context's set-up time goes, on stderr)
-#include <chrono>
 struct SetupTrace {
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
     void operator()(const char* what) {
@@ -827,16 +606,16 @@ int smcn_set_seed(smcn_ctx* c, uint64_t seed) {
     return 0;
 }
 
-// ---- staging helpers --------------------------------------------------------------
-static int ensure_stage(smcn_ctx* c, int64_t n) { return grow(c, c->stage, n); }
-static int ensure_stage2(smcn_ctx* c, int64_t n) { return grow(c, c->stage2, n); }
+}  // extern "C"
+
+// ---- staging helpers (ensure_stage, ensure_stage2: smcn_ctx.hpp) and the launchers other units call -----------------
 // models whose constrained space is not coordinate-wise: the moment kernels read a constrained copy of the population
-static bool has_constrain_pass(const smcn_ctx* c) {
+bool smcn_host::has_constrain_pass(const smcn_ctx* c) {
     return c->model == SMCN_MODEL_HGLM || c->model == SMCN_MODEL_ORDINAL || c->model == SMCN_MODEL_MLGLM;
 }
 // their constrain pass over M particles, particle t's coordinate c at x[(t / Np) * Np * D + (t % Np) * si + c * sc]
-static void launch_constrain_pass(smcn_ctx* c, const double* x, double* out, int64_t M, int64_t Np, int64_t si,
-                                  int64_t sc) {
+void smcn_host::launch_constrain_pass(smcn_ctx* c, const double* x, double* out, int64_t M, int64_t Np, int64_t si,
+                                      int64_t sc) {
     if (c->model == SMCN_MODEL_ORDINAL)
         ord_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D, (int)c->reg.p, si, sc);
     else if (c->model == SMCN_MODEL_MLGLM) {
@@ -849,6 +628,22 @@ static void launch_constrain_pass(smcn_ctx* c, const double* x, double* out, int
         hglm_constrain_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(x, out, M, Np, c->D,
                                                                        c->reg.Dc, (int)c->reg.J, si, sc);
 }
+void smcn_host::launch_constrain_rows(smcn_ctx* c, const double* x, double* out, int64_t M) {
+    if (has_constrain_pass(c))
+        launch_constrain_pass(c, x, out, M, M, c->D, 1);
+    else
+        constrain_kernel<<<grid_for(M * c->D, 256), 256, 0, c->stream>>>(x, out, M, c->D, c->cmodel);
+}
+void smcn_host::launch_transpose(smcn_ctx* c, const double* in, double* out, int64_t rows, int64_t cols) {
+    transpose_kernel<<<grid_for(rows * cols, 256), 256, 0, c->stream>>>(in, out, rows, cols);
+}
+void smcn_host::launch_scan(smcn_ctx* c, const double* w, int64_t M, int nt, double* local, double* ttot, double* toff) {
+    scan_tile_kernel<<<nt, 256, 0, c->stream>>>(w, M, local, ttot);
+    scan_offsets_kernel<<<1, 64, 0, c->stream>>>(ttot, nt, toff);
+}
+
+extern "C" {
+
 // SMCN_MODEL_HGLM / _ORDINAL / _MLGLM: the constrained population of ngen consecutive generations ([ngen][D][N] from x)
 // into c->cstage, on the context's stream; *out is what the moment kernels then read with the identity (c->cmodel)
 static int model_constrained(smcn_ctx* c, const double* x, int ngen, const double** out) {
@@ -1042,10 +837,7 @@ int smcn_target_constrain(smcn_ctx* c, const double* x, int64_t M, double* out) 
     if (rc) return rc;
     if ((rc = ensure_stage2(c, n))) return rc;
     HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    if (has_constrain_pass(c))
-        launch_constrain_pass(c, c->stage, c->stage2, M, M, c->D, 1);
-    else
-        constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->cmodel);
+    launch_constrain_rows(c, c->stage, c->stage2, M);
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(out, c->stage2, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, stream_wait(c->stream));
@@ -3160,990 +2952,6 @@ int smcn_selftest_recur(smcn_ctx* c, const double* x, int64_t n, double* out) {
 
 }  // extern "C"
 
-// ---- pointwise log-likelihood and its reductions over particles (smcn_pointwise.hpp) ------------------------------------
-static const char* kPwScope =
-    "pointwise criteria cover the SMCN_MODEL_GLM families (bernoulli_logit, poisson_log, normal, neg_binomial_2_log) "
-    "only; hierarchical, categorical, ordinal, arma, PRMwCD, Gaussian and host-evaluated targets are not implemented";
-
-static const char* kPwWeighted =
-    "pointwise criteria and LOO of a fit with weights (SMCN_MODEL_OGLM, flags & 2) are not implemented: what a weighted "
-    "row's leave-one-out term and the standard error of the sum should be is not settled here";
-// "" or why the pointwise entry points do not serve this context
-static std::string pw_refusal(const smcn_ctx* c) {
-    if (c->model == SMCN_MODEL_OGLM) return (c->reg.flags & 2) ? kPwWeighted : "";
-    return c->model == SMCN_MODEL_GLM ? "" : kPwScope;
-}
-// the GLM walk's arguments over the image `md` of the block L describes (the training data, or the new rows)
-static PwArgs pw_args(const RegLayout& L, const double* md, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
-    PwArgs a;
-    a.md = md;
-    a.x = x;
-    a.rs = rs;
-    a.cs = cs;
-    a.M = M;
-    a.cps = cps;
-    a.fam = L.fam;
-    a.n = (int)L.n;
-    a.p = (int)L.p;
-    a.Dc = L.Dc;
-    return a;
-}
-// f(row capacity) for table rows of Dc columns: DP <= 16 / 32 / 64 doubles
-template <class F>
-static void row_cap(int Dc, F&& f) {
-    const int DP = (Dc + 1) & ~1;
-    if (DP <= 16) f(std::integral_constant<int, 16>{});
-    else if (DP <= 32) f(std::integral_constant<int, 32>{});
-    else f(std::integral_constant<int, 64>{});
-}
-// f(row capacity, dispersion family)
-template <class F>
-static void row_cap_disp(int Dc, int fam, F&& f) {
-    row_cap(Dc, [&](auto dp) { fam >= 2 ? f(dp, std::true_type{}) : f(dp, std::false_type{}); });
-}
-// f(row capacity, dispersion family, offset table): the GLM walk's instantiation for the block L describes
-template <class F>
-static void row_cap_glm(const RegLayout& L, F&& f) {
-    row_cap_disp(L.Dc, L.fam, [&](auto dp, auto disp) {
-        L.model == SMCN_MODEL_OGLM ? f(dp, disp, std::true_type{}) : f(dp, disp, std::false_type{});
-    });
-}
-// categorical: f(row capacity, non-reference classes), the pairs that cover (K - 1) Dc <= 64
-template <class F>
-static void cat_cap(int Dc, F&& f) {
-    using std::integral_constant;
-    if (Dc <= 4) f(integral_constant<int, 4>{}, integral_constant<int, 15>{});
-    else if (Dc <= 8) f(integral_constant<int, 8>{}, integral_constant<int, 12>{});
-    else if (Dc <= 16) f(integral_constant<int, 16>{}, integral_constant<int, 7>{});
-    else if (Dc <= 32) f(integral_constant<int, 32>{}, integral_constant<int, 3>{});
-    else f(integral_constant<int, 64>{}, integral_constant<int, 1>{});
-}
-// The particles a post-fit entry point works on: the caller's x [M][D] uploaded to c->stage, with logw (or zeros) in
-// `lw_stage` -- or, x = NULL, the resident ones with their resident log-weights.
-struct Particles {
-    const double* xd;
-    int64_t rs, cs;
-    double* lw;
-};
-static int stage_particles(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* lw_stage, Particles* P) {
-    if (!x) {
-        *P = {c->x, 1, c->N, c->logw};
-        return 0;
-    }
-    const int rc = ensure_stage(c, M * c->D);
-    if (rc) return rc;
-    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
-    if (logw) HIPC(c, hipMemcpyAsync(lw_stage, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-    else HIPC(c, hipMemsetAsync(lw_stage, 0, sizeof(double) * M, c->stream));
-    *P = {c->stage, c->D, 1, lw_stage};
-    return 0;
-}
-
-extern "C" {
-
-int smcn_pointwise_dims(const smcn_ctx* cc, int64_t* n_obs, int* n_cols) {
-    smcn_ctx* c = const_cast<smcn_ctx*>(cc);
-    if (!c) return -1;
-    if (!pw_refusal(c).empty()) FAIL(c, "smcn_pointwise_dims: " + pw_refusal(c));
-    if (n_obs) *n_obs = c->reg.n;
-    if (n_cols) *n_cols = kPwCols;
-    return 0;
-}
-
-int smcn_pointwise_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
-    CHECK_CTX(c);
-    if (!pw_refusal(c).empty()) FAIL(c, "smcn_pointwise_loglik: " + pw_refusal(c));
-    if (!x || !out || M < 1) FAIL(c, "smcn_pointwise_loglik: bad arguments");
-    const int64_t n = c->reg.n, tiles = (n + 63) / 64;
-    int64_t cps = 1;
-    const int64_t slices = pointwise_slices(M, n, &cps);
-    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_pointwise_loglik: too many observations");
-    int rc = ensure_stage(c, M * c->D);
-    if (rc) return rc;
-    if ((rc = grow(c, c->pw_buf, M * n))) return rc;
-    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
-    const PwArgs a = pw_args(c->reg, c->mdata, c->stage, c->D, 1, M, cps);
-    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
-        pointwise_loglik_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
-            <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, c->pw_buf);
-    });
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(out, c->pw_buf, sizeof(double) * M * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    return 0;
-}
-
-int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
-    CHECK_CTX(c);
-    if (!pw_refusal(c).empty()) FAIL(c, "smcn_pointwise_partials: " + pw_refusal(c));
-    if (!out || M < 1) FAIL(c, "smcn_pointwise_partials: bad arguments");
-    if (!x && (M != c->N || logw)) FAIL(c, "smcn_pointwise_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    const int64_t n = c->reg.n, tiles = (n + 63) / 64, npad = tiles * 64;
-    int64_t cps = 1;
-    const int64_t slices = pointwise_slices(M, n, &cps);
-    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_pointwise_partials: too many observations");
-    // pw_buf: [header 16 | lw M | slice partials | group partials | result (1 + n) Q]
-    const int64_t groups = (slices + kPwGroup - 1) / kPwGroup;
-    const int64_t o_lw = 16, o_part = o_lw + (M + 15) / 16 * 16, o_grp = o_part + slices * kPwCols * npad;
-    const int64_t o_out = o_grp + groups * kPwCols * npad;
-    int rc = grow(c, c->pw_buf, o_out + (1 + n) * kPwCols);
-    if (rc) return rc;
-    double* const head = c->pw_buf;
-    double* const part = c->pw_buf + o_part;
-    double* const grp = c->pw_buf + o_grp;
-    double* const res = c->pw_buf + o_out;
-    Particles P;
-    if ((rc = stage_particles(c, x, logw, M, c->pw_buf + o_lw, &P))) return rc;
-    const double* const lw = P.lw;
-    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, cps);
-    HIPC(c, c->pw_ev0.record(c->stream));
-    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
-    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
-        pointwise_stats_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
-            <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, lw, head, part);
-    });
-    // (groups <= 256 blocks in y: pointwise_slices keeps the slices near 4096)
-    pointwise_combine_kernel<false><<<dim3((unsigned)grid_for(n, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, n, npad, grp);
-    pointwise_combine_kernel<true><<<grid_for(n, 64), 64, 0, c->stream>>>(grp, head, groups, n, npad, res);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->pw_ev1.record(c->stream));
-    HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * (1 + n) * kPwCols, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    HIPC(c, c->pw_ev1.since(c->pw_ev0, &c->pw_ms));
-    return 0;
-}
-
-int smcn_pointwise_last_ms(const smcn_ctx* c, double* ms) {
-    if (!c || !ms) return -1;
-    *ms = c->pw_ms;
-    return 0;
-}
-
-}  // extern "C"
-// ---- Pareto-smoothed importance-sampling LOO (smcn_psis.hpp) ---------------------------------------------------------------
-namespace {
-// ps_buf of a call over particles: [header 16 | lw | slab of ll | candidates lr, ll [n][stride] | cutoff npad | slice
-// partials | group partials | body [n][4] | out [n][6]]
-struct PsLayout {
-    int64_t n, tiles, npad, M, Mpad, cps, slices, groups, slab_tiles, stride;
-    int64_t o_lw, o_stage, o_clr, o_cll, o_cut, o_part, o_grp, o_body, o_out, total;
-};
-constexpr int64_t kPsSlab = 1ll << 25;     // doubles of ll staged at once (256 MB), one observation tile at the least
-}  // namespace
-
-static int ps_layout(smcn_ctx* c, const char* who, int64_t M, int64_t S_bound, PsLayout* L) {
-    if (!pw_refusal(c).empty()) FAIL(c, std::string(who) + ": " + pw_refusal(c));
-    if (M < 1 || M > 2147483647LL) FAIL(c, std::string(who) + ": bad arguments");
-    if (S_bound < 1) FAIL(c, std::string(who) + ": no contributing particle (S < 1)");
-    L->stride = psis_tail_len(S_bound) + 1;
-    if (L->stride > kPsMaxCap)
-        FAIL(c, std::string(who) + ": the tail of " + std::to_string(L->stride - 1) + " candidates per observation exceeds " +
-                    std::to_string(kPsMaxCap - 1) + " (more than 1863225 contributing particles are not implemented)");
-    L->n = c->reg.n;
-    L->tiles = (L->n + 63) / 64;
-    L->npad = L->tiles * 64;
-    L->M = M;
-    L->Mpad = (M + 63) / 64 * 64;
-    L->slices = pointwise_slices(M, L->n, &L->cps);
-    L->groups = (L->slices + kPwGroup - 1) / kPwGroup;
-    int64_t st = kPsSlab / (64 * L->Mpad);
-    st = st < 1 ? 1 : (st > L->tiles ? L->tiles : st);
-    while (st > 1 && st * L->slices > 2147483647LL) --st;
-    L->slab_tiles = st;
-    if (L->tiles * L->slices > 2147483647LL) FAIL(c, std::string(who) + ": too many observations");
-    L->o_lw = 16;
-    L->o_stage = L->o_lw + L->Mpad;
-    L->o_clr = L->o_stage + st * 64 * L->Mpad;
-    L->o_cll = L->o_clr + L->n * L->stride;
-    L->o_cut = L->o_cll + L->n * L->stride;
-    L->o_part = L->o_cut + L->npad;
-    L->o_grp = L->o_part + L->slices * kPsBodyCols * L->npad;
-    L->o_body = L->o_grp + L->groups * kPsBodyCols * L->npad;
-    L->o_out = L->o_body + L->n * kPsBodyCols;
-    L->total = L->o_out + L->n * kPsOutCols;
-    return grow(c, c->ps_buf, L->total);
-}
-// header of a staged call from the caller's (mw, S)
-static int ps_put_head(smcn_ctx* c, double mw, int64_t S) {
-    const double h[16] = {mw, 0.0, 0.0, (double)S};
-    HIPC(c, hipMemcpyAsync(c->ps_buf, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, stream_wait(c->stream));      // (h is a local)
-    return 0;
-}
-static void ps_run_candidates(smcn_ctx* c, const PsLayout& L, const PwArgs& a, const double* lw) {
-    double* const B = c->ps_buf;
-    for (int64_t t0 = 0; t0 < L.tiles; t0 += L.slab_tiles) {
-        const int64_t nt = L.tiles - t0 < L.slab_tiles ? L.tiles - t0 : L.slab_tiles;
-        row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
-            psis_stage_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
-                <<<(int)(nt * L.slices), 64, 0, c->stream>>>(a, t0, nt, lw, B, L.Mpad, B + L.o_stage);
-        });
-        psis_select_kernel<<<(int)(nt * 64), kPsBlock, 0, c->stream>>>(B + L.o_stage, L.Mpad, lw, B, L.M, t0 * 64, L.n,
-                                                                       (int)L.stride, B + L.o_clr, B + L.o_cll, B + L.o_cut);
-    }
-}
-static void ps_run_body(smcn_ctx* c, const PsLayout& L, const PwArgs& a, const double* lw) {
-    double* const B = c->ps_buf;
-    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
-        psis_body_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
-            <<<(int)(L.tiles * L.slices), 64, 0, c->stream>>>(a, L.tiles, lw, B, B + L.o_cut, B + L.o_part);
-    });
-    psis_body_combine_kernel<false><<<dim3((unsigned)grid_for(L.n, 64), (unsigned)L.groups), 64, 0, c->stream>>>(
-        B + L.o_part, L.slices, L.n, L.npad, B + L.o_grp);
-    psis_body_combine_kernel<true><<<grid_for(L.n, 64), 64, 0, c->stream>>>(B + L.o_grp, L.groups, L.n, L.npad, B + L.o_body);
-}
-static int ps_elapsed(smcn_ctx* c, int slot, int e0, int e1) {
-    HIPC(c, c->ps_ev[e1].since(c->ps_ev[e0], &c->ps_ms[slot]));
-    return 0;
-}
-
-extern "C" {
-
-int smcn_psis_candidates(smcn_ctx* c, const double* x, const double* logw, int64_t M, double mw, int64_t S, double* cand) {
-    CHECK_CTX(c);
-    if (!cand) FAIL(c, "smcn_psis_candidates: bad arguments");
-    if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_candidates: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    PsLayout L;
-    int rc = ps_layout(c, "smcn_psis_candidates", M, S, &L);
-    if (rc || (rc = ps_put_head(c, mw, S))) return rc;
-    Particles P;
-    if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
-    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
-    HIPC(c, c->ps_ev[0].record(c->stream));
-    ps_run_candidates(c, L, a, P.lw);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->ps_ev[1].record(c->stream));
-    HIPC(c, hipMemcpyAsync(cand, c->ps_buf + L.o_clr, sizeof(double) * 2 * L.n * L.stride, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    return ps_elapsed(c, 0, 0, 1);
-}
-
-int smcn_psis_body(smcn_ctx* c, const double* x, const double* logw, int64_t M, double mw, int64_t S, const double* cutoff,
-                   double* body) {
-    CHECK_CTX(c);
-    if (!cutoff || !body) FAIL(c, "smcn_psis_body: bad arguments");
-    if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_body: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    PsLayout L;
-    int rc = ps_layout(c, "smcn_psis_body", M, S, &L);
-    if (rc || (rc = ps_put_head(c, mw, S))) return rc;
-    Particles P;
-    if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
-    HIPC(c, hipMemcpyAsync(c->ps_buf + L.o_cut, cutoff, sizeof(double) * L.n, hipMemcpyHostToDevice, c->stream));
-    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
-    HIPC(c, c->ps_ev[0].record(c->stream));
-    ps_run_body(c, L, a, P.lw);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->ps_ev[1].record(c->stream));
-    HIPC(c, hipMemcpyAsync(body, c->ps_buf + L.o_body, sizeof(double) * L.n * kPsBodyCols, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    return ps_elapsed(c, 1, 0, 1);
-}
-
-int smcn_psis_fit(smcn_ctx* c, const double* cand, const double* body, int64_t n_obs, double mw, int64_t S, double* out) {
-    CHECK_CTX(c);
-    if (!cand || !body || !out || n_obs < 1 || n_obs > 2147483647LL) FAIL(c, "smcn_psis_fit: bad arguments");
-    if (S < 1) FAIL(c, "smcn_psis_fit: no contributing particle (S < 1)");
-    const int64_t stride = psis_tail_len(S) + 1;
-    if (stride > kPsMaxTail + 1)
-        FAIL(c, "smcn_psis_fit: the tail of " + std::to_string(stride - 1) + " candidates per observation exceeds " +
-                    std::to_string(kPsMaxTail));
-    // ps_buf: [header 16 | candidates lr, ll [n][stride] | body [n][4] | out [n][6]]
-    const int64_t o_c = 16, o_b = o_c + 2 * n_obs * stride, o_o = o_b + n_obs * kPsBodyCols;
-    int rc = grow(c, c->ps_buf, o_o + n_obs * kPsOutCols);
-    if (rc || (rc = ps_put_head(c, mw, S))) return rc;
-    double* const B = c->ps_buf;
-    HIPC(c, hipMemcpyAsync(B + o_c, cand, sizeof(double) * 2 * n_obs * stride, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(B + o_b, body, sizeof(double) * n_obs * kPsBodyCols, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, c->ps_ev[0].record(c->stream));
-    psis_fit_kernel<<<(int)n_obs, kPsBlock, 0, c->stream>>>(B + o_c, B + o_c + n_obs * stride, B + o_b, B, (int)stride, B + o_o);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->ps_ev[1].record(c->stream));
-    HIPC(c, hipMemcpyAsync(out, B + o_o, sizeof(double) * n_obs * kPsOutCols, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    return ps_elapsed(c, 2, 0, 1);
-}
-
-int smcn_psis_loo(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out, double* head_out) {
-    CHECK_CTX(c);
-    if (!out) FAIL(c, "smcn_psis_loo: bad arguments");
-    if (!x && (M != c->N || logw)) FAIL(c, "smcn_psis_loo: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    // S <= M is known on the device only: the candidate rows are laid out for S = M, the kernels read S from the header
-    PsLayout L;
-    int rc = ps_layout(c, "smcn_psis_loo", M, M, &L);
-    if (rc) return rc;
-    Particles P;
-    if ((rc = stage_particles(c, x, logw, M, c->ps_buf + L.o_lw, &P))) return rc;
-    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, L.cps);
-    double* const B = c->ps_buf;
-    HIPC(c, c->ps_ev[0].record(c->stream));
-    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(P.lw, M, B);
-    ps_run_candidates(c, L, a, P.lw);
-    HIPC(c, c->ps_ev[1].record(c->stream));
-    ps_run_body(c, L, a, P.lw);
-    HIPC(c, c->ps_ev[2].record(c->stream));
-    psis_fit_kernel<<<(int)L.n, kPsBlock, 0, c->stream>>>(B + L.o_clr, B + L.o_cll, B + L.o_body, B, (int)L.stride, B + L.o_out);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->ps_ev[3].record(c->stream));
-    HIPC(c, hipMemcpyAsync(out, B + L.o_out, sizeof(double) * L.n * kPsOutCols, hipMemcpyDeviceToHost, c->stream));
-    if (head_out) HIPC(c, hipMemcpyAsync(head_out, B, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    if ((rc = ps_elapsed(c, 0, 0, 1)) || (rc = ps_elapsed(c, 1, 1, 2)) || (rc = ps_elapsed(c, 2, 2, 3))) return rc;
-    return ps_elapsed(c, 3, 0, 3);
-}
-
-int smcn_psis_last_ms(const smcn_ctx* c, double* ms) {
-    if (!c || !ms) return -1;
-    for (int k = 0; k < 4; ++k) ms[k] = c->ps_ms[k];
-    return 0;
-}
-
-}  // extern "C"
-// ---- posterior summaries: weighted quantiles and tail masses (smcn_quantile.hpp) -------------------------------------------
-namespace {
-struct SmLayout {
-    double *vals, *lw, *head, *thr_at, *out, *cdf_out;
-    u64 *fw, *tot, *pfx[2], *thr[2], *thr0, *cnt;
-    int *nan, *nan_cdf;
-};
-int64_t sm_words(int64_t M, int Dc) { return (int64_t)Dc * M + 2 * M + 48 + (int64_t)Dc * (4 + 8 * kSmMaxQ); }
-SmLayout sm_layout(const smcn_ctx* c) {
-    const int64_t M = c->sm_M, S = (int64_t)c->sm_Dc * kSmMaxQ;
-    const int Dc = c->sm_Dc;
-    SmLayout L;
-    double* p = c->sm_buf;
-    L.vals = p; p += (int64_t)Dc * M;
-    L.fw = (u64*)p; p += M;
-    L.lw = p; p += M;
-    L.head = p; p += 16;
-    L.tot = (u64*)p; p += 16;
-    L.thr0 = (u64*)p; p += 16;
-    L.nan = (int*)p; p += Dc;
-    for (int i = 0; i < 2; ++i) { L.pfx[i] = (u64*)p; p += S; }
-    for (int i = 0; i < 2; ++i) { L.thr[i] = (u64*)p; p += S; }
-    L.thr_at = p; p += S;
-    L.cnt = (u64*)p; p += S;
-    L.out = p; p += S + Dc;
-    L.nan_cdf = (int*)p; p += Dc;
-    L.cdf_out = p;                  // S + Dc
-    return L;
-}
-}  // namespace
-// waits for the stream and adds the time between sm_ev[0] and sm_ev[last] to the call's device time
-static int sm_finish(smcn_ctx* c, int last) {
-    HIPC(c, stream_wait(c->stream));
-    double ms = 0.0;
-    HIPC(c, c->sm_ev[last].since(c->sm_ev[0], &ms));
-    c->sm_ms += ms;
-    return 0;
-}
-static int sm_hist_ensure(smcn_ctx* c) { return grow(c, c->sm_hist, (int64_t)c->sm_Dc * kSmMaxQ * 256 * 2 + c->sm_Dc); }
-static dim3 sm_grid(const smcn_ctx* c) {
-    return dim3((unsigned)grid_for(c->sm_M, kSmBlock * kSmElems), (unsigned)c->sm_Dc);
-}
-// one histogram pass over the staged population with the prefixes of state set c->sm_cur
-static int sm_launch_hist(smcn_ctx* c, const SmLayout& L, int nq, int pass) {
-    const int64_t bins = (int64_t)c->sm_Dc * nq * 256;
-    HIPC(c, hipMemsetAsync(c->sm_hist, 0, sizeof(u64) * bins, c->stream));
-    sm_hist_kernel<<<sm_grid(c), kSmBlock, sizeof(u64) * nq * 256, c->stream>>>(L.vals, c->sm_M, L.fw, L.pfx[c->sm_cur], nq,
-                                                                                 pass, c->sm_hist, L.nan);
-    HIPC(c, hipGetLastError());
-    return 0;
-}
-
-extern "C" {
-
-int smcn_summary_begin(smcn_ctx* c, const double* x, const double* logw, const double* v, int64_t M, int Dv, double* head) {
-    CHECK_CTX(c);
-    if (!head || M < 1) FAIL(c, "smcn_summary_begin: bad arguments");
-    if (x && v) FAIL(c, "smcn_summary_begin: pass x (unconstrained) or v (constrained), not both");
-    if (!x && !v && (M != c->N || logw))
-        FAIL(c, "smcn_summary_begin: the resident particles come with their resident log-weights (x = v = NULL: logw = NULL, M = N)");
-    if (v && (Dv < 1 || Dv > 65535)) FAIL(c, "smcn_summary_begin: v needs its number of columns (1 .. 65535)");
-    if (M > (int64_t)1 << 40) FAIL(c, "smcn_summary_begin: too many particles");
-    const int Dc = v ? Dv : c->Dc;
-    c->sm_stage_state = 0;
-    if (int rc = grow(c, c->sm_buf, sm_words(M, Dc))) return rc;
-    c->sm_M = M;
-    c->sm_Dc = Dc;
-    int rc = 0;
-    const SmLayout L = sm_layout(c);
-    const int64_t n = M * Dc;
-    if (x || v) {
-        if ((rc = ensure_stage(c, n))) return rc;
-        if (x && (rc = ensure_stage2(c, n))) return rc;
-        HIPC(c, hipMemcpyAsync(c->stage, x ? x : v, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-        if (logw) HIPC(c, hipMemcpyAsync(L.lw, logw, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
-        else HIPC(c, hipMemsetAsync(L.lw, 0, sizeof(double) * M, c->stream));
-    }
-    HIPC(c, c->sm_ev[0].record(c->stream));
-    if (x) {                    // [M][D] through the model's constrain path, then coordinate-major
-        if (has_constrain_pass(c))
-            launch_constrain_pass(c, c->stage, c->stage2, M, M, c->D, 1);
-        else
-            constrain_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, c->stage2, M, c->D, c->cmodel);
-        transpose_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage2, L.vals, M, Dc);
-    } else if (v) {
-        transpose_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->stage, L.vals, M, Dc);
-    } else {                    // the resident generation, already [D][N]
-        if (has_constrain_pass(c))
-            launch_constrain_pass(c, c->x, L.vals, M, M, 1, M);
-        else
-            sm_stage_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->x, L.vals, M, c->D, c->cmodel);
-        HIPC(c, hipMemcpyAsync(L.lw, c->logw, sizeof(double) * M, hipMemcpyDeviceToDevice, c->stream));
-    }
-    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(L.lw, M, L.head);
-    // the header's sum once more, as an integer sum: the same bits for every order of the particles
-    HIPC(c, hipMemsetAsync(L.tot, 0, sizeof(u64) * 4, c->stream));
-    sm_total_kernel<<<grid_for(M, kSmBlock), kSmBlock, 0, c->stream>>>(L.lw, M, L.head, L.tot + 2);
-    sm_total_final_kernel<<<1, 64, 0, c->stream>>>(L.tot + 2, L.head);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->sm_ev[1].record(c->stream));
-    HIPC(c, hipMemcpyAsync(head, L.head, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
-    c->sm_ms = 0.0;
-    for (double& p : c->sm_pass_ms) p = 0.0;
-    if ((rc = sm_finish(c, 1))) return rc;
-    c->sm_stage_state = 1;
-    return 0;
-}
-
-int smcn_summary_weights(smcn_ctx* c, double lw_max, double lw_sum, double* mass) {
-    CHECK_CTX(c);
-    if (c->sm_stage_state < 1) FAIL(c, "smcn_summary_weights: call smcn_summary_begin first");
-    if (!mass || !std::isfinite(lw_max) || !(lw_sum > 0.0) || !std::isfinite(lw_sum))
-        FAIL(c, "smcn_summary_weights: bad arguments (no particle with positive weight?)");
-    const SmLayout L = sm_layout(c);
-    HIPC(c, hipMemsetAsync(L.tot, 0, sizeof(u64) * 2, c->stream));
-    HIPC(c, c->sm_ev[0].record(c->stream));
-    sm_fixed_kernel<<<grid_for(c->sm_M, kSmBlock), kSmBlock, 0, c->stream>>>(L.lw, c->sm_M, lw_max, lw_sum, L.fw, L.tot);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->sm_ev[1].record(c->stream));
-    u64 tot = 0;
-    HIPC(c, hipMemcpyAsync(&tot, L.tot, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    int rc = sm_finish(c, 1);
-    if (rc) return rc;
-    *mass = (double)tot;
-    c->sm_stage_state = 2;
-    return 0;
-}
-
-static int sm_check_nq(smcn_ctx* c, const char* who, int nq) {
-    if (c->sm_stage_state < 2) FAIL(c, std::string(who) + ": call smcn_summary_begin and smcn_summary_weights first");
-    if (nq < 1 || nq > kSmMaxQ) FAIL(c, std::string(who) + ": 1 .. 16 probabilities");
-    return sm_hist_ensure(c);
-}
-
-int smcn_summary_select(smcn_ctx* c, int nq, const double* thr) {
-    CHECK_CTX(c);
-    int rc = sm_check_nq(c, "smcn_summary_select", nq);
-    if (rc) return rc;
-    if (!thr) FAIL(c, "smcn_summary_select: bad arguments");
-    c->sm_thr_h.assign(kSmMaxQ, 0);
-    for (int q = 0; q < nq; ++q) {
-        if (!(thr[q] >= 1.0 && thr[q] <= 9007199254740992.0) || (q && thr[q] < thr[q - 1]))
-            FAIL(c, "smcn_summary_select: thresholds are masses in 1 .. 2^53, in ascending order");
-        c->sm_thr_h[q] = (u64)thr[q];
-    }
-    const SmLayout L = sm_layout(c);
-    HIPC(c, hipMemcpyAsync(L.thr0, c->sm_thr_h.data(), sizeof(u64) * kSmMaxQ, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemsetAsync(L.nan, 0, sizeof(int) * c->sm_Dc, c->stream));
-    c->sm_cur = 0;
-    HIPC(c, c->sm_ev[0].record(c->stream));
-    for (int pass = 0; pass < 8; ++pass) {
-        if ((rc = sm_launch_hist(c, L, nq, pass))) return rc;
-        sm_pick_kernel<<<c->sm_Dc * nq, 256, 0, c->stream>>>(c->sm_hist, L.pfx[c->sm_cur], L.thr[c->sm_cur], L.thr0,
-                                                             L.pfx[c->sm_cur ^ 1], L.thr[c->sm_cur ^ 1], nq, pass);
-        HIPC(c, hipGetLastError());
-        c->sm_cur ^= 1;
-        HIPC(c, c->sm_ev[pass + 1].record(c->stream));
-    }
-    if ((rc = sm_finish(c, 8))) return rc;
-    for (int pass = 0; pass < 8; ++pass) HIPC(c, c->sm_ev[pass + 1].since(c->sm_ev[pass], &c->sm_pass_ms[pass]));
-    return 0;
-}
-
-int smcn_summary_hist(smcn_ctx* c, int pass, int nq, double* out) {
-    CHECK_CTX(c);
-    int rc = sm_check_nq(c, "smcn_summary_hist", nq);
-    if (rc) return rc;
-    if (!out || pass < 0 || pass > 7) FAIL(c, "smcn_summary_hist: bad arguments");
-    const SmLayout L = sm_layout(c);
-    if (pass == 0) {
-        HIPC(c, hipMemsetAsync(L.nan, 0, sizeof(int) * c->sm_Dc, c->stream));
-        c->sm_cur = 0;
-        c->sm_pfx_h.assign((size_t)c->sm_Dc * nq, 0);
-    } else if (c->sm_pfx_h.size() != (size_t)c->sm_Dc * nq) {
-        FAIL(c, "smcn_summary_hist: passes 1 .. 7 follow smcn_summary_descend of the pass before, with the same probabilities");
-    }
-    const int64_t n = (int64_t)c->sm_Dc * (pass == 0 ? 1 : nq) * 256 + c->sm_Dc;
-    double* const dout = (double*)(c->sm_hist + (int64_t)c->sm_Dc * kSmMaxQ * 256);
-    HIPC(c, c->sm_ev[0].record(c->stream));
-    if ((rc = sm_launch_hist(c, L, nq, pass))) return rc;
-    sm_export_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(c->sm_hist, L.pfx[c->sm_cur], L.nan, c->sm_Dc, nq, pass, dout);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->sm_ev[1].record(c->stream));
-    HIPC(c, hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = sm_finish(c, 1))) return rc;
-    HIPC(c, c->sm_ev[1].since(c->sm_ev[0], &c->sm_pass_ms[pass]));
-    return 0;
-}
-
-int smcn_summary_descend(smcn_ctx* c, int pass, int nq, const int32_t* digits, const double* residual) {
-    CHECK_CTX(c);
-    int rc = sm_check_nq(c, "smcn_summary_descend", nq);
-    if (rc) return rc;
-    const size_t S = (size_t)c->sm_Dc * nq;
-    if (!digits || !residual || pass < 0 || pass > 7 || c->sm_pfx_h.size() != S)
-        FAIL(c, "smcn_summary_descend: follows smcn_summary_hist of the same pass");
-    c->sm_thr_h.assign(S, 0);
-    for (size_t i = 0; i < S; ++i) {
-        if (digits[i] < 0 || digits[i] > 255 || !(residual[i] >= 0.0 && residual[i] <= 9007199254740992.0))
-            FAIL(c, "smcn_summary_descend: digits are 0 .. 255, residual masses 0 .. 2^53");
-        c->sm_pfx_h[i] = (pass == 0 ? 0ull : c->sm_pfx_h[i] << 8) | (u64)digits[i];
-        c->sm_thr_h[i] = (u64)residual[i];
-    }
-    const SmLayout L = sm_layout(c);
-    HIPC(c, hipMemcpyAsync(L.pfx[c->sm_cur], c->sm_pfx_h.data(), sizeof(u64) * S, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(L.thr[c->sm_cur], c->sm_thr_h.data(), sizeof(u64) * S, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    return 0;
-}
-
-int smcn_summary_values(smcn_ctx* c, int nq, double* out, double* nan_flags) {
-    CHECK_CTX(c);
-    int rc = sm_check_nq(c, "smcn_summary_values", nq);
-    if (rc) return rc;
-    if (!out || !nan_flags) FAIL(c, "smcn_summary_values: bad arguments");
-    const SmLayout L = sm_layout(c);
-    const int S = c->sm_Dc * nq;
-    sm_values_kernel<<<grid_for(S, 256), 256, 0, c->stream>>>(L.pfx[c->sm_cur], S, L.out);
-    sm_counts_kernel<<<grid_for(c->sm_Dc, 256), 256, 0, c->stream>>>(L.cnt, L.nan, 0, c->sm_Dc, L.out + S);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(out, L.out, sizeof(double) * S, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(nan_flags, L.out + S, sizeof(double) * c->sm_Dc, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    return 0;
-}
-
-int smcn_summary_cdf(smcn_ctx* c, int T, const double* at, double* out) {
-    CHECK_CTX(c);
-    if (c->sm_stage_state < 2) FAIL(c, "smcn_summary_cdf: call smcn_summary_begin and smcn_summary_weights first");
-    if (T < 1 || T > kSmMaxQ || !at || !out) FAIL(c, "smcn_summary_cdf: 1 .. 16 thresholds per coordinate");
-    const SmLayout L = sm_layout(c);
-    const int S = c->sm_Dc * T;
-    int* const nan = L.nan_cdf;      // (its own NaN flags: the call does not depend on a selection before it)
-    HIPC(c, hipMemcpyAsync(L.thr_at, at, sizeof(double) * S, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemsetAsync(L.cnt, 0, sizeof(u64) * S, c->stream));
-    HIPC(c, hipMemsetAsync(nan, 0, sizeof(int) * c->sm_Dc, c->stream));
-    HIPC(c, c->sm_ev[0].record(c->stream));
-    sm_cdf_kernel<<<sm_grid(c), kSmBlock, 0, c->stream>>>(L.vals, c->sm_M, L.fw, L.thr_at, T, L.cnt, nan);
-    double* const dout = L.cdf_out;
-    sm_counts_kernel<<<grid_for(S + c->sm_Dc, 256), 256, 0, c->stream>>>(L.cnt, nan, S, c->sm_Dc, dout);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->sm_ev[1].record(c->stream));
-    HIPC(c, hipMemcpyAsync(out, dout, sizeof(double) * (S + c->sm_Dc), hipMemcpyDeviceToHost, c->stream));
-    return sm_finish(c, 1);
-}
-
-int smcn_summary_last_ms(const smcn_ctx* c, double* ms) {
-    if (!c || !ms) return -1;
-    *ms = c->sm_ms;
-    return 0;
-}
-
-int smcn_summary_pass_ms(const smcn_ctx* c, double* ms) {
-    if (!c || !ms) return -1;
-    for (int i = 0; i < 8; ++i) ms[i] = c->sm_pass_ms[i];
-    return 0;
-}
-
-// ---- posterior covariance (smcn_cov.hpp) ---------------------------------------------------------------------------------
-int smcn_cov_dims(const smcn_ctx* c, int64_t* out) {
-    if (!c || !out) return -1;
-    if (c->sm_stage_state < 1) return -3;
-    out[0] = c->sm_M;
-    out[1] = c->sm_Dc;
-    out[2] = c->sm_Dc <= kCovMaxDc ? cov_slices(c->sm_M, c->sm_Dc) : 0;
-    out[3] = c->sm_Dc <= kCovMaxDc ? cov_slice_cap(c->sm_Dc) : 0;
-    return 0;
-}
-
-int smcn_cov_partials(smcn_ctx* c, double lw_max, const double* centre, int64_t slices, double* out, double* centre_out) {
-    CHECK_CTX(c);
-    if (c->sm_stage_state < 1) FAIL(c, "smcn_cov_partials: call smcn_summary_begin first");
-    if (!out && !centre_out) FAIL(c, "smcn_cov_partials: bad arguments");
-    if (!std::isfinite(lw_max)) FAIL(c, "smcn_cov_partials: lw_max must be finite (no particle with positive weight?)");
-    const int Dc = c->sm_Dc;
-    const int64_t M = c->sm_M;
-    if (Dc > kCovMaxDc)
-        FAIL(c, "smcn_cov_partials: at most 1023 constrained coordinates, not " + std::to_string(Dc));
-    const int64_t cap = cov_slice_cap(Dc);
-    if (slices < 0 || slices > cap)
-        FAIL(c, "smcn_cov_partials: slices must be 0 (the rule's own count) or 1 .. " + std::to_string(cap) +
-                    " for " + std::to_string(Dc) + " coordinates");
-    if (slices == 0) slices = cov_slices(M, Dc);
-    const int T = cov_tiles(Dc), Da = Dc + 1, NB = (T + kCovBlock - 1) / kCovBlock;
-    const int64_t entries = cov_tile_pairs(Dc) * 256, groups = (slices + kCovGroup - 1) / kCovGroup;
-    const int64_t chunks = (M + 15) / 16, cps = (chunks + slices - 1) / slices;
-    // cov_buf: [w M | centre 16 T | slice partials | group partials | result Da Da | the centre's chunk sums 2 Dc nch]
-    const int64_t nch = (M + kCovCentreChunk - 1) / kCovCentreChunk;
-    const int64_t o_c = (M + 15) / 16 * 16, o_part = o_c + 16 * T, o_grp = o_part + slices * entries;
-    const int64_t o_out = o_grp + groups * entries, o_cp = o_out + (int64_t)Da * Da, words = o_cp + 2 * Dc * nch;
-    if (int rc = grow(c, c->cov_buf, words)) return rc;
-    const SmLayout L = sm_layout(c);
-    double *const w = c->cov_buf, *const cen = c->cov_buf + o_c, *const part = c->cov_buf + o_part;
-    double *const grp = c->cov_buf + o_grp, *const res = c->cov_buf + o_out;
-    if (centre) HIPC(c, hipMemcpyAsync(cen, centre, sizeof(double) * Dc, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, c->cov_ev[0].record(c->stream));
-    cov_weight_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(L.lw, M, lw_max, w);
-    if (!centre) {
-        double* const cp = c->cov_buf + o_cp;
-        cov_centre_partial_kernel<<<dim3((unsigned)nch, (unsigned)Dc), kRedBlock, 0, c->stream>>>(L.vals, w, M, nch, cp);
-        cov_centre_final_kernel<<<Dc, kRedBlock, 0, c->stream>>>(cp, nch, cen);
-    }
-    if (out) {
-        cov_partials_kernel<kCovBlock><<<dim3((unsigned)(NB * (NB + 1) / 2), (unsigned)slices), 64, 0, c->stream>>>(
-            L.vals, w, cen, M, Dc, T, NB, cps, part);
-        cov_combine_kernel<false><<<dim3((unsigned)grid_for(entries, 256), (unsigned)groups), 256, 0, c->stream>>>(
-            part, slices, entries, T, Da, grp);
-        cov_combine_kernel<true><<<grid_for(entries, 256), 256, 0, c->stream>>>(grp, groups, entries, T, Da, res);
-    }
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->cov_ev[1].record(c->stream));
-    if (out) HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * Da * Da, hipMemcpyDeviceToHost, c->stream));
-    if (centre_out) HIPC(c, hipMemcpyAsync(centre_out, cen, sizeof(double) * Dc, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    HIPC(c, c->cov_ev[1].since(c->cov_ev[0], &c->cov_ms));
-    return 0;
-}
-
-int smcn_cov_last_ms(const smcn_ctx* c, double* ms) {
-    if (!c || !ms) return -1;
-    *ms = c->cov_ms;
-    return 0;
-}
-
-}  // extern "C"
-// ---- held-out prediction at new rows (smcn_predict.hpp) ----------------------------------------------------------------
-static const char* kPrScope =
-    "held-out prediction covers the regression targets (SMCN_MODEL_GLM, SMCN_MODEL_OGLM, SMCN_MODEL_HGLM, "
-    "SMCN_MODEL_CATEGORICAL, SMCN_MODEL_ORDINAL); arma, PRMwCD, Gaussian and host-evaluated targets are not supported";
-static bool pr_model(const smcn_ctx* c) {
-    return c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM || c->model == SMCN_MODEL_HGLM ||
-           c->model == SMCN_MODEL_CATEGORICAL || c->model == SMCN_MODEL_ORDINAL;
-}
-static int pr_cols(const smcn_ctx* c) {
-    const int K = c->reg.K;
-    if (c->model == SMCN_MODEL_CATEGORICAL) return kPrCatP0 + K;
-    if (c->model == SMCN_MODEL_ORDINAL) return kPrOrdP0 + (K <= kPrMaxProb ? K : 0);
-    return kPrColsGlm;
-}
-// the arguments of the hierarchical, categorical and ordinal kernels over the new rows (c->pr)
-static PrArgs pr_args(const smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps) {
-    PrArgs a;
-    a.T = c->pr_md + c->pr.t0;
-    a.x = x;
-    a.rs = rs;
-    a.cs = cs;
-    a.M = M;
-    a.cps = cps;
-    a.m = (int)c->pr.n;
-    a.D = c->D;
-    a.fam = c->reg.fam;
-    a.J = (int)c->reg.J;
-    a.K = c->reg.K;
-    a.Dc = c->reg.Dc;
-    return a;
-}
-// Dynamic LDS of one wavefront's area V[r][64 particles] (smcn_predict.hpp): J rows (hierarchical), D (categorical),
-// 2 (K - 1) or, with the class probabilities, 3 (K - 1) (ordinal); none for the GLM families.  The largest a model's
-// limits allow is the ordinal model at p = 0, K = 65: 128 rows = kPrMaxLdsBytes exactly, what a launch may ask for
-// without hipFuncSetAttribute.
-constexpr size_t kPrMaxLdsBytes = 64 * 1024;
-static size_t pr_lds_bytes(const smcn_ctx* c, bool stats) {
-    const RegLayout& L = c->reg;
-    size_t rows = 0;
-    if (c->model == SMCN_MODEL_HGLM) rows = (size_t)L.J;
-    else if (c->model == SMCN_MODEL_ORDINAL) rows = (size_t)(L.K - 1) * ((stats && L.K <= kPrMaxProb) ? 3 : 2);
-    else if (c->model == SMCN_MODEL_CATEGORICAL) rows = (size_t)L.D;
-    return sizeof(double) * 64 * rows;
-}
-#define PR_CHECK_LDS(c, stats, who)                                                                                     \
-    if (pr_lds_bytes(c, stats) > kPrMaxLdsBytes)                                                                        \
-        FAIL(c, std::string(who) + ": the model's per-wavefront LDS area (" + std::to_string(pr_lds_bytes(c, stats)) +  \
-                    " B) is above the 65536 B a launch may ask for")
-// Launches the model's matrix (STATS = false: out [M][m]) or statistics kernel over `blocks` wavefronts
-template <bool STATS>
-static void pr_launch(smcn_ctx* c, const double* x, int64_t rs, int64_t cs, int64_t M, int64_t cps, int64_t tiles,
-                      int64_t blocks, const double* lw, const double* head, double* out) {
-    const int g = (int)blocks;
-    hipStream_t st = c->stream;
-    if (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM) {
-        const PwArgs a = pw_args(c->pr, c->pr_md, x, rs, cs, M, cps);
-        row_cap_glm(c->pr, [&](auto dp, auto disp, auto ow) {
-            constexpr int DP = decltype(dp)::value;
-            constexpr bool DI = decltype(disp)::value, OW = decltype(ow)::value;
-            if constexpr (STATS) predict_glm_stats_kernel<DP, DI, OW><<<g, 64, 0, st>>>(a, tiles, lw, head, out);
-            else pointwise_loglik_kernel<DP, DI, OW><<<g, 64, 0, st>>>(a, tiles, out);
-        });
-        return;
-    }
-    const PrArgs a = pr_args(c, x, rs, cs, M, cps);
-    const size_t lds = pr_lds_bytes(c, STATS);
-    if (c->model == SMCN_MODEL_HGLM) {
-        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
-            constexpr int DPM = decltype(dp)::value;
-            constexpr bool DI = decltype(disp)::value;
-            if constexpr (STATS) predict_hier_stats_kernel<DPM, DI><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
-            else predict_hier_loglik_kernel<DPM, DI><<<g, 64, lds, st>>>(a, tiles, out);
-        });
-    } else if (c->model == SMCN_MODEL_ORDINAL) {
-        const bool prob = a.K <= kPrMaxProb;
-        row_cap(a.Dc, [&](auto dp) {
-            constexpr int DPM = decltype(dp)::value;
-            if constexpr (STATS) {
-                if (prob) predict_ord_stats_kernel<DPM, true><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
-                else predict_ord_stats_kernel<DPM, false><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
-            } else {
-                predict_ord_loglik_kernel<DPM><<<g, 64, lds, st>>>(a, tiles, out);
-            }
-        });
-    } else {
-        cat_cap(a.Dc, [&](auto dc, auto km) {
-            constexpr int DCM = decltype(dc)::value, KM = decltype(km)::value;
-            if constexpr (STATS) predict_cat_stats_kernel<DCM, KM><<<g, 64, lds, st>>>(a, tiles, lw, head, out);
-            else predict_cat_loglik_kernel<DCM, KM><<<g, 64, lds, st>>>(a, tiles, out);
-        });
-    }
-}
-
-extern "C" {
-
-int smcn_predict_set_data(smcn_ctx* c, const double* block, int64_t len, int has_y) {
-    CHECK_CTX(c);
-    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_set_data: ") + kPrScope);
-    // the priors of the training block spliced in: the block smcn_ctx_create would take, checked by the same routine
-    std::vector<double> full, mup;
-    std::string why = reg_splice(c->reg, c->mdata_h.data(), block, len, full);
-    if (!why.empty()) FAIL(c, why);
-    RegLayout L;
-    why = reg_check(c->model, full.data(), (int64_t)full.size(), &L);
-    if (!why.empty()) FAIL(c, "smcn_predict_set_data (new rows, with the training priors spliced in): " + why);
-    if (L.D != c->D) FAIL(c, "smcn_predict_set_data: the new rows give another dimension than the training data");
-    reg_repack(L, full.data(), mup);
-    c->pr.n = 0;
-    const int rc = grow(c, c->pr_md, L.rlen);
-    if (rc) return rc;
-    HIPC(c, hipMemcpyAsync(c->pr_md, mup.data(), sizeof(double) * L.rlen, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, stream_wait(c->stream));                             // (mup is a local)
-    c->pr = L;
-    c->pr_has_y = has_y ? 1 : 0;
-    return 0;
-}
-
-int smcn_predict_dims(smcn_ctx* c, int64_t* n_rows, int* n_cols, int* has_y) {
-    CHECK_CTX(c);
-    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_dims: ") + kPrScope);
-    if (c->pr.n < 1) FAIL(c, "smcn_predict_dims: no new rows (smcn_predict_set_data first)");
-    if (n_rows) *n_rows = c->pr.n;
-    if (n_cols) *n_cols = pr_cols(c);
-    if (has_y) *has_y = c->pr_has_y;
-    return 0;
-}
-
-int smcn_predict_loglik(smcn_ctx* c, const double* x, int64_t M, double* out) {
-    CHECK_CTX(c);
-    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_loglik: ") + kPrScope);
-    if (c->pr.n < 1) FAIL(c, "smcn_predict_loglik: no new rows (smcn_predict_set_data first)");
-    if (!c->pr_has_y) FAIL(c, "smcn_predict_loglik: the new rows were given without y");
-    if (!x || !out || M < 1) FAIL(c, "smcn_predict_loglik: bad arguments");
-    PR_CHECK_LDS(c, false, "smcn_predict_loglik");
-    const int64_t m = c->pr.n, tiles = (m + 63) / 64;
-    int64_t cps = 1;
-    const int64_t slices = pointwise_slices(M, m, &cps);
-    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_predict_loglik: too many rows");
-    int rc = ensure_stage(c, M * c->D);
-    if (rc) return rc;
-    if ((rc = grow(c, c->pw_buf, M * m))) return rc;
-    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
-    pr_launch<false>(c, c->stage, c->D, 1, M, cps, tiles, tiles * slices, nullptr, nullptr, c->pw_buf);
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(out, c->pw_buf, sizeof(double) * M * m, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    return 0;
-}
-
-int smcn_predict_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
-    CHECK_CTX(c);
-    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_partials: ") + kPrScope);
-    if (c->pr.n < 1) FAIL(c, "smcn_predict_partials: no new rows (smcn_predict_set_data first)");
-    if (!out || M < 1) FAIL(c, "smcn_predict_partials: bad arguments");
-    PR_CHECK_LDS(c, true, "smcn_predict_partials");
-    if (!x && (M != c->N || logw)) FAIL(c, "smcn_predict_partials: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    const int64_t m = c->pr.n, tiles = (m + 63) / 64, mpad = tiles * 64;
-    const int Q = pr_cols(c), mom = (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM || c->model == SMCN_MODEL_HGLM) ? 1 : 0;
-    int64_t cps = 1;
-    const int64_t slices = pointwise_slices(M, m, &cps);
-    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_predict_partials: too many rows");
-    // pw_buf: [header 16 | lw M | slice partials | group partials | result (1 + m) Q]
-    const int64_t groups = (slices + kPwGroup - 1) / kPwGroup;
-    const int64_t o_lw = 16, o_part = o_lw + (M + 15) / 16 * 16, o_grp = o_part + slices * Q * mpad;
-    const int64_t o_out = o_grp + groups * Q * mpad;
-    int rc = grow(c, c->pw_buf, o_out + (1 + m) * Q);
-    if (rc) return rc;
-    double* const head = c->pw_buf;
-    double* const part = c->pw_buf + o_part;
-    double* const grp = c->pw_buf + o_grp;
-    double* const res = c->pw_buf + o_out;
-    Particles P;
-    if ((rc = stage_particles(c, x, logw, M, c->pw_buf + o_lw, &P))) return rc;
-    const double* const lw = P.lw;
-    HIPC(c, c->pw_ev0.record(c->stream));
-    pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
-    pr_launch<true>(c, P.xd, P.rs, P.cs, M, cps, tiles, tiles * slices, lw, head, part);
-    predict_combine_kernel<false><<<dim3((unsigned)grid_for(m, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, m, mpad, Q, mom, grp);
-    predict_combine_kernel<true><<<grid_for(m, 64), 64, 0, c->stream>>>(grp, head, groups, m, mpad, Q, mom, res);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->pw_ev1.record(c->stream));
-    HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * (1 + m) * Q, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    HIPC(c, c->pw_ev1.since(c->pw_ev0, &c->pr_ms));
-    return 0;
-}
-
-int smcn_predict_last_ms(const smcn_ctx* c, double* ms) {
-    if (!c || !ms) return -1;
-    *ms = c->pr_ms;
-    return 0;
-}
-
-}  // extern "C"
-// ---- posterior predictive draws (smcn_predict_draws.hpp) ---------------------------------------------------------------
-// Which (model, row capacity) instantiations sample inside the walk; the others store the law's mean and
-// draws_sample_kernel samples it (Posterior predictive draws: the register counts behind the choice)
-template <int DPMAX, bool DISP>
-constexpr bool kDrawsFusedGlm = DPMAX <= 16;
-template <int DPMAX, bool DISP>
-constexpr bool kDrawsFusedHier = DPMAX <= 16;
-
-// Launches the model's draw kernel over the n gathered particles xg [D][n] -> out [n][m]
-static void dr_launch(smcn_ctx* c, const double* xg, int64_t n, const DrawArgs& d, double* out) {
-    const int64_t m = c->pr.n, tiles = (m + 63) / 64;
-    int64_t cps = 1;
-    const int64_t slices = pointwise_slices(n, m, &cps);
-    const int g = (int)(tiles * slices);
-    hipStream_t st = c->stream;
-    const auto second = [&](int fam, bool disp, int tau_coord) {
-        draws_sample_kernel<<<grid_for(n * m, 256), 256, 0, st>>>(fam, m, n, d, disp ? xg + (int64_t)tau_coord * n : nullptr, out);
-    };
-    if (c->model == SMCN_MODEL_GLM || c->model == SMCN_MODEL_OGLM) {
-        const PwArgs a = pw_args(c->pr, c->pr_md, xg, 1, n, n, cps);
-        row_cap_glm(c->pr, [&](auto dp, auto disp, auto ow) {
-            constexpr int DP = decltype(dp)::value;
-            constexpr bool DI = decltype(disp)::value;
-            constexpr bool FU = kDrawsFusedGlm<DP, DI>;
-            draws_glm_kernel<DP, DI, FU, decltype(ow)::value><<<g, 64, 0, st>>>(a, tiles, d, out);
-            if (!FU) second(a.fam, DI, a.Dc);
-        });
-        return;
-    }
-    const PrArgs a = pr_args(c, xg, 1, n, n, cps);
-    const size_t lds = pr_lds_bytes(c, false);
-    if (c->model == SMCN_MODEL_HGLM) {
-        row_cap_disp(a.Dc, a.fam, [&](auto dp, auto disp) {
-            constexpr int DPM = decltype(dp)::value;
-            constexpr bool DI = decltype(disp)::value;
-            constexpr bool FU = kDrawsFusedHier<DPM, DI>;
-            draws_hier_kernel<DPM, DI, FU><<<g, 64, lds, st>>>(a, tiles, d, out);
-            if (!FU) second(a.fam, DI, a.Dc + a.J + 1);
-        });
-    } else if (c->model == SMCN_MODEL_ORDINAL) {
-        row_cap(a.Dc, [&](auto dp) { draws_ord_kernel<decltype(dp)::value><<<g, 64, lds, st>>>(a, tiles, d, out); });
-    } else {
-        cat_cap(a.Dc, [&](auto dc, auto km) {
-            draws_cat_kernel<decltype(dc)::value, decltype(km)::value><<<g, 64, lds, st>>>(a, tiles, d, out);
-        });
-    }
-}
-
-extern "C" {
-
-int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t M, int64_t S, uint64_t seed,
-                       const int64_t* ancestors, const int64_t* new_group, int64_t s_first, int64_t s_count, double* y_out,
-                       int64_t* ancestors_out, int64_t* n_bad_out) {
-    CHECK_CTX(c);
-    if (!pr_model(c)) FAIL(c, std::string("smcn_predict_draws: ") + kPrScope);
-    if (c->pr.n < 1) FAIL(c, "smcn_predict_draws: no new rows (smcn_predict_set_data first)");
-    if (M < 1) FAIL(c, "smcn_predict_draws: M must be at least 1");
-    if (S < 1 || S > 2147483647LL) FAIL(c, "smcn_predict_draws: the number of draws S must be in 1..2^31-1");
-    if (s_first < 0 || s_count < 1 || s_first + s_count > S)
-        FAIL(c, "smcn_predict_draws: the slot range [s_first, s_first + s_count) must be non-empty and lie in 0..S");
-    if (!y_out) FAIL(c, "smcn_predict_draws: y_out is null");
-    if (!x && (M != c->N || logw)) FAIL(c, "smcn_predict_draws: the resident particles come with their resident log-weights (x = NULL: logw = NULL, M = N)");
-    if (new_group && c->model != SMCN_MODEL_HGLM) FAIL(c, "smcn_predict_draws: new_group is for SMCN_MODEL_HGLM only");
-    const int64_t m = c->pr.n, tiles = (m + 63) / 64, n = s_count;
-    if (new_group)
-        for (int64_t i = 0; i < m; ++i)
-            if (new_group[i] < 0 || new_group[i] > 4294967295LL)
-                FAIL(c, "smcn_predict_draws: new_group[" + std::to_string(i) + "] is not a label in 0..2^32-1");
-    if (ancestors)
-        for (int64_t s = 0; s < S; ++s)
-            if (ancestors[s] < 0 || ancestors[s] >= M)
-                FAIL(c, "smcn_predict_draws: ancestors[" + std::to_string(s) + "] is not a particle in 0..M-1");
-    PR_CHECK_LDS(c, false, "smcn_predict_draws");
-    int64_t cps = 1;
-    if (tiles * pointwise_slices(n, m, &cps) > 2147483647LL) FAIL(c, "smcn_predict_draws: too many rows");
-    // dr_buf: [header 16 | lw M | w M | scan M | tile totals nt | tile offsets nt + 1 | ancestors n | labels m | xg D n | y n m]
-    const int nt = (int)((M + kScanTile - 1) / kScanTile);
-    const auto pad = [](int64_t v) { return (v + 15) / 16 * 16; };
-    const int64_t o_lw = 16, o_w = o_lw + pad(M), o_loc = o_w + pad(M), o_tt = o_loc + pad(M), o_to = o_tt + pad(nt);
-    const int64_t o_anc = o_to + pad(nt + 1), o_ng = o_anc + pad(n), o_xg = o_ng + pad(m), o_y = o_xg + pad(n * c->D);
-    const int64_t need = o_y + n * m;
-    int rc = grow(c, c->dr_buf, need);
-    if (rc) return rc;
-    double* const B = c->dr_buf;
-    double* const head = B;
-    int64_t* const anc = (int64_t*)(B + o_anc);
-    int64_t* const ng = (int64_t*)(B + o_ng);
-    Particles P;
-    if ((rc = stage_particles(c, x, logw, M, B + o_lw, &P))) return rc;
-    const double* const lw = P.lw;
-    if (new_group) HIPC(c, hipMemcpyAsync(ng, new_group, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
-    if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, c->pw_ev0.record(c->stream));
-    if (!ancestors) {
-        pointwise_header_kernel<<<1, kRedBlock, 0, c->stream>>>(lw, M, head);
-        draws_weights_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(lw, head, M, B + o_w);
-        scan_tile_kernel<<<nt, 256, 0, c->stream>>>(B + o_w, M, B + o_loc, B + o_tt);
-        scan_offsets_kernel<<<1, 64, 0, c->stream>>>(B + o_tt, nt, B + o_to);
-        draws_ancestors_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(B + o_loc, B + o_to, nt, M, lw, S, s_first, n, seed, anc);
-    }
-    draws_gather_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(P.xd, P.rs, P.cs, anc, n, c->D, B + o_xg);
-    const DrawArgs d{seed, s_first, new_group ? ng : nullptr};
-    dr_launch(c, B + o_xg, n, d, B + o_y);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->pw_ev1.record(c->stream));
-    double cnt = 1.0;
-    if (!ancestors) HIPC(c, hipMemcpyAsync(&cnt, head + 3, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (ancestors_out) HIPC(c, hipMemcpyAsync(ancestors_out, anc, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(y_out, B + o_y, sizeof(double) * n * m, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    HIPC(c, c->pw_ev1.since(c->pw_ev0, &c->dr_ms));
-    if (cnt == 0.0) FAIL(c, "smcn_predict_draws: no particle has a finite log-weight");
-    if (n_bad_out) {
-        int64_t nb = 0;
-        for (int64_t e = 0; e < n * m; ++e) nb += y_out[e] != y_out[e] ? 1 : 0;
-        *n_bad_out = nb;
-    }
-    return 0;
-}
-
-int smcn_predict_draws_last_ms(const smcn_ctx* c, double* ms) {
-    if (!c || !ms) return -1;
-    *ms = c->dr_ms;
-    return 0;
-}
-
-}  // extern "C"
 // ---- measured roofline denominators (bench.py: roofline.peak_measured) ---------------------------------------------
 __global__ void __launch_bounds__(256) peak_copy_kernel(const double2* __restrict__ a, double2* __restrict__ b, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) b[i] = a[i];

@@ -22,7 +22,7 @@
 // (groups of 16, then the groups: pointwise_combine_kernel's scheme) and mirrors the upper triangle.  No LDS, no
 // atomics, no scratch; a result depends on (inputs, slices) alone.
 #pragma once
-#include "smcn_pointwise.hpp"
+#include "smcn_pw_walk.hpp"
 
 namespace smcn {
 

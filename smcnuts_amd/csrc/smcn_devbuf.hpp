@@ -1,4 +1,4 @@
-// Owners of what a context keeps on the device: its buffers and its timing events (smcn_api.hip).  Host-only and free of
+// Owners of what a context keeps on the device: its buffers and its timing events (smcn_ctx.hpp).  Host-only and free of
 // HIP: the runtime's calls come in through a policy, so that tests/devbuf_driver.cpp checks the rules below with a
 // counting allocator under the host sanitizers.
 //   - a buffer is a member of smcn_ctx and releases itself with it; nothing names it a second time in order to free it

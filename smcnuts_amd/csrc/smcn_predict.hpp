@@ -38,7 +38,7 @@
 //   V             sum w Var(y | x_p)
 //   EM, P_k       sum w sum_k sigma(eta - c_k);  sum w P(y = k | x_p)
 #pragma once
-#include "smcn_pointwise.hpp"
+#include "smcn_pw_walk.hpp"
 
 namespace smcn {
 

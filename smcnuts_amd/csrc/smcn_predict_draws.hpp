@@ -16,7 +16,6 @@
 // outside the range the density accepts, e^eta or e^(2 lt) overflowing, an attempt cap reached.
 #pragma once
 #include "smcn_predict.hpp"
-#include "smcn_weights.hpp"
 
 namespace smcn {
 

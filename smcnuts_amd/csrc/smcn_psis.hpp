@@ -19,7 +19,7 @@
 // The cutoff on the lr scale is the largest candidate whose z = lr - mx does not exceed c (z of the T_cap-th largest):
 // "z > c" is then the same set as "lr > cutoff" even where the subtraction of mx rounds two lr onto one z.
 #pragma once
-#include "smcn_quantile.hpp"
+#include "smcn_pointwise.hpp"
 
 namespace smcn {
 

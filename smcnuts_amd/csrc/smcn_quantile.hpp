@@ -22,7 +22,7 @@
 // slots are then flushed wave-wide: lanes holding the same bin sum their masses across the wavefront and ONE lane adds
 // (sm_wave_add).  A block then adds its non-empty bins to the global histogram.
 #pragma once
-#include "smcn_pointwise.hpp"
+#include "smcn_pw_walk.hpp"   // (pw_exp_neg)
 
 namespace smcn {
 
@@ -31,17 +31,7 @@ constexpr int kSmBlock = 256;
 constexpr int kSmElems = 8;            // elements per thread of the counting kernels
 constexpr double kSmUnit = 4503599627370496.0;   // 2^52 units of fixed-point mass make the whole
 
-using u64 = unsigned long long;
-
-// order-preserving key: -inf < ... < -0.0 < +0.0 < ... < +inf as unsigned integers
-__device__ __forceinline__ u64 sm_key(double v) {
-    const u64 b = (u64)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b ^ 0x8000000000000000ull);
-}
-__device__ __forceinline__ double sm_unkey(u64 k) {
-    const u64 b = (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k;
-    return __longlong_as_double((long long)b);
-}
+// (u64 and the order-preserving key sm_key / sm_unkey: smcn_device.hpp, PSIS selects on the same key)
 
 __device__ __forceinline__ u64 sm_wave_sum(u64 v) {
 #pragma unroll

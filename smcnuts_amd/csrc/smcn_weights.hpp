@@ -14,8 +14,6 @@
 
 namespace smcn {
 
-constexpr int kScanTile = 1024;  // 256 threads x 4 consecutive elements
-
 // ---- Box-Muller normals, [D][N], Philox (seed, iter, particle, stream) ------
 __global__ void normals_kernel(double* out, int64_t N, int D, int64_t particle_base, uint64_t seed,
                                uint32_t iter, uint32_t stream) {
@@ -100,12 +98,7 @@ __global__ void __launch_bounds__(256) eval_kernel(const double* mdata, const do
     }
 }
 
-// constrain(): exp() on the last coordinate for arma (sigma) / PRMwCD (Gamma)
-__device__ __forceinline__ double constrain_coord(int model_id, int c, int D, double v) {
-    // arma (1) / PRMwCD (2): the last coordinate is a log scale; Gaussian (0) and host-evaluated (3: the
-    // caller constrains) are the identity
-    return ((model_id == 1 || model_id == 2) && c == D - 1) ? exp(v) : v;
-}
+// (constrain_coord: smcn_device.hpp)
 __global__ void constrain_kernel(const double* x, double* out, int64_t M, int D, int model_id) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M * D) return;
@@ -342,50 +335,7 @@ __device__ __forceinline__ const double* tile_offsets_lds(const double* __restri
     __syncthreads();
     return sh;
 }
-// searchsorted(cdf, key, 'right') on cdf[i] = (toff[i / 1024] + local[i]) / total.  tiles_first (offsets in LDS): first
-// the TILE (its last cdf value is toff[t + 1] / total, the very sum the element-wise search sees at that position), then
-// the element inside it with three pivots per step -- 5 dependent global round trips instead of 16 (the search is
-// latency-bound: 8 bytes per probe).
-__device__ __forceinline__ int64_t cdf_search(double key, double total, const double* toff, const double* __restrict__ local,
-                                              int nt, int64_t N, bool tiles_first) {
-    int64_t lo = 0, hi = N;
-    if (tiles_first) {
-        int tl = 0, th = nt;
-        while (tl < th) {
-            const int tm = tl + ((th - tl) >> 1);
-            if (key < toff[tm + 1] / total) th = tm;
-            else tl = tm + 1;
-        }
-        if (tl < nt) {
-            const double off = toff[tl];
-            lo = (int64_t)tl * kScanTile;
-            hi = lo + kScanTile < N ? lo + kScanTile : N;
-            while (hi - lo > 7) {
-                const int64_t w = hi - lo, p1 = lo + (w >> 2), p2 = lo + (w >> 1), p3 = lo + w - (w >> 2) - 1;   // lo <= p1 < p2 < p3 < hi
-                const double c1 = (off + local[p1]) / total, c2 = (off + local[p2]) / total, c3 = (off + local[p3]) / total;
-                if (key < c1) hi = p1;
-                else if (key < c2) { lo = p1 + 1; hi = p2; }
-                else if (key < c3) { lo = p2 + 1; hi = p3; }
-                else lo = p3 + 1;
-            }
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (key < (off + local[mid]) / total) hi = mid;
-                else lo = mid + 1;
-            }
-        } else {
-            lo = N;
-        }
-    } else {
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            const double cv = (toff[mid / kScanTile] + local[mid]) / total;
-            if (key < cv) hi = mid;
-            else lo = mid + 1;
-        }
-    }
-    return lo;
-}
+// (cdf_search: smcn_device.hpp, the predictive draws search the same sums)
 // ttot != null (nt <= kFusedOffsetsMaxTiles): tile offsets from the tile totals, in LDS; else `toff` (global)
 __global__ void __launch_bounds__(256) search_gather_kernel(const double* local, const double* toff, int nt, int64_t N,
                                                             const double* u, uint64_t seed, uint32_t iter,

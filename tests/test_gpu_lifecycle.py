@@ -3,8 +3,8 @@ same bits whether their buffers are fresh, have just been regrown for a larger M
 they hold -- and again in a context whose buffers come, zeroed, out of the cache the closed contexts left.
 
 A flat Bernoulli GLMTarget with n = 65 rows (two observation tiles) and p = 2, 64 resident particles.  M = 64 fits the
-staging buffer smcn_ctx_create makes; M = 130 (three particle chunks, the last ragged) makes stage, pw_buf, ps_buf,
-dr_buf, sm_buf and cov_buf regrow.  Every comparison is np.array_equal with NaNs compared by position."""
+staging buffer smcn_ctx_create makes; M = 130 (three particle chunks, the last ragged) makes stage, pw.buf, ps.buf,
+dr.buf, sm.buf and cov.buf regrow.  Every comparison is np.array_equal with NaNs compared by position."""
 import numpy as np
 import pytest
 

@@ -1,15 +1,18 @@
 #!/bin/bash
 # Device assembly of one kernel of the library: tools/dis_kernel.sh <mangled-name-substring> [out.s]
+# (every unit's assembly goes to /tmp/dis/<unit>.s, with smcnuts_amd/build.py's flags plus ${SMCN_DEFS})
 set -e
-cd "$(dirname "$0")/../smcnuts_amd"
-mkdir -p /tmp/dis
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -mllvm -amdgpu-atomic-optimizer-strategy=None -S --cuda-device-only ${SMCN_DEFS} -o /tmp/dis/api.s csrc/smcn_api.hip
+cd "$(dirname "$0")/.."
+python3 -m smcnuts_amd.build --asm /tmp/dis ${SMCN_DEFS} > /dev/null
 python3 - "$1" "${2:-/tmp/dis/kernel.s}" <<'PY'
-import sys, re
-s = open('/tmp/dis/api.s').read()
+import glob, sys, re
 pat = sys.argv[1]
-m = re.search(r'^(\S*' + re.escape(pat) + r'[^\s:]*):', s, re.M)
+for f in sorted(glob.glob('/tmp/dis/smcn_*.s')):
+    s = open(f).read()
+    m = re.search(r'^(\S*' + re.escape(pat) + r'[^\s:]*):', s, re.M)
+    if m:
+        break
 i = m.start(); j = s.index('.Lfunc_end', i)
 open(sys.argv[2], 'w').write(s[i:j])
-print(m.group(1), s[i:j].count('\n'), 'lines ->', sys.argv[2])
+print(m.group(1), s[i:j].count('\n'), 'lines ->', sys.argv[2], '(' + f + ')')
 PY
