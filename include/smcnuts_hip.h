@@ -721,6 +721,32 @@ int smcn_cov_partials(smcn_ctx* ctx, double lw_max, const double* centre_or_null
 int smcn_cov_dims(const smcn_ctx* ctx, int64_t* out /* [4] */);
 int smcn_cov_last_ms(const smcn_ctx* ctx, double* ms);
 
+/* ---- step-size probe: short leapfrog trajectories at a ladder of step sizes (every device-native model) ----
+ * x [M][D] with logw [M] (NULL: equal), or x = NULL: the resident particles with their resident log-weights (logw = NULL,
+ * M = N).  Mp = min(M, max_particles) particles are probed, probed particle k being particle (k M) / Mp.  Momenta: r
+ * [Mp][D], or NULL: standard normal draws, Philox keyed by (coordinate pair, particle_base + particle, 0, a stream no
+ * sampler kernel draws from) under `seed`, the Box-Muller of the sampler's momentum draw -- a function of (seed, global
+ * particle index) alone.
+ * Per probed particle and ladder entry j (1 <= L <= 16; finite, positive, strictly increasing) the trajectory restarts
+ * from the same (x, r) and runs n_leapfrog (1 .. 64) steps of size eps_j on log pi_phi = lpri + phi llik:
+ *   r += eps/2 g;  x += eps r;  g = grad log pi_phi(x);  r += eps/2 g;  dH_t = H_t - H_0,  H = -log pi_phi + |r|^2 / 2
+ *   a_j = (1/n) sum_t min(1, exp(-dH_t)).
+ * The first t at which dH_t is not finite or exceeds delta_max marks the pair divergent: that step and all later ones
+ * contribute 0 (first_bad = t, else 0).  A particle whose starting density or log-weight is not finite is excluded
+ * (a = 0, first_bad = 0) and counted.
+ * partials [1 + L][4]: row 0 = (m, Mp, excluded, 0), m the largest finite log-weight probed (-inf: none); row 1 + j =
+ * (sum w a_j, sum w d_j, sum w, number divergent) over the particles that count, w = exp(logw - m), d_j the divergent
+ * flag.  Summed in a fixed order without atomics: two calls give the same bits.  Partials of disjoint particle sets
+ * merge after rescaling by exp(m_r - m).  accept, first_bad [L][Mp] (or NULL): the per-particle values.
+ * The call reads the resident particles and weights and writes buffers of its own and the staging buffer: the sampler's
+ * state, momenta, flags, history and block buffers stay as they were.  SMCN_MODEL_HOST is refused.
+ * smcn_stepsize_last_ms: device time of the last probe's kernels (HIP events on the context's stream); -1: no context. */
+int smcn_stepsize_probe(smcn_ctx* ctx, const double* x, const double* logw, int64_t M, const double* r,
+                        const double* ladder, int L, int n_leapfrog, double phi, double delta_max, uint64_t seed,
+                        int64_t max_particles, double* partials /* [1 + L][4] */, double* accept /* [L][Mp] or NULL */,
+                        int32_t* first_bad /* [L][Mp] or NULL */);
+double smcn_stepsize_last_ms(const smcn_ctx* ctx);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build. */

@@ -165,6 +165,9 @@ SIGNATURES = {
     "smcn_cov_partials": ([_ctx, C.c_double, _dp, C.c_int64, _dp, _dp], C.c_int),
     "smcn_cov_dims": ([_ctx, C.POINTER(C.c_int64)], C.c_int),
     "smcn_cov_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_stepsize_probe": ([_ctx, _dp, _dp, C.c_int64, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64,
+                             C.c_int64, _dp, _dp, _ip], C.c_int),
+    "smcn_stepsize_last_ms": ([_ctx], C.c_double),
 }
 
 _lib = None
@@ -640,6 +643,42 @@ class Context:
         if self._lib.smcn_cov_last_ms(self._h, C.byref(ms)) != 0:
             raise SmcnError("smcn_cov_last_ms failed")
         return ms.value
+
+    # ---- step-size probe (every device-native model) -----------------------------------
+    def stepsize_probe(self, ladder, x=None, logw=None, r=None, n_leapfrog=8, phi=1.0, delta_max=100.0, seed=0,
+                       max_particles=4096, want_particles=False):
+        """(partials [1 + L][4], accept [L][Mp], first_bad [L][Mp]) of one pass over `ladder` (include/smcnuts_hip.h); the
+        last two None unless want_particles.  x=None: the resident particles and weights.  r [Mp][D]: the momenta of
+        the probed particles (None: Philox under `seed`)."""
+        lad = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+        if x is None:
+            if logw is not None:
+                raise ValueError("the resident particles come with their resident log-weights (x=None: logw=None)")
+            xp, lp_, M = None, None, self.N
+        else:
+            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            if x.shape[1] != self.D:
+                raise ValueError(f"x must hold {self.D} coordinates per row")
+            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+            if lw is not None and lw.shape != (x.shape[0],):
+                raise ValueError("logw must hold one log-weight per row of x")
+            xp, lp_, M = dptr(x), dptr(lw), x.shape[0]
+        Mp = min(M, int(max_particles))
+        if r is not None:
+            r = np.ascontiguousarray(r, dtype=np.float64)
+            if r.shape != (Mp, self.D):
+                raise ValueError(f"r must hold the momenta of the {Mp} probed particles, [{Mp}][{self.D}]")
+        part = np.empty((1 + lad.size, 4))
+        acc = np.empty((lad.size, Mp)) if want_particles else None
+        fb = np.empty((lad.size, Mp), dtype=np.int32) if want_particles else None
+        self.call("smcn_stepsize_probe", xp, lp_, M, dptr(r), dptr(lad), lad.size, int(n_leapfrog), float(phi),
+                  float(delta_max), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(max_particles), dptr(part), dptr(acc),
+                  iptr(fb))
+        return part, acc, fb
+
+    def stepsize_last_ms(self):
+        """Device time of the last stepsize_probe's kernels (HIP events on the context's stream)."""
+        return float(self._lib.smcn_stepsize_last_ms(self._h))
 
     def timers(self, reset=False):
         t = np.zeros(6)

@@ -30,6 +30,7 @@
 #include "smcn_glk.hpp"
 #include "smcn_step.hpp"
 #include "smcn_block_post.hpp"
+#include "smcn_stepsize.hpp"
 
 using namespace smcn;
 
@@ -799,7 +800,89 @@ static int launch_eval(smcn_ctx* c, Model, const double* x, int64_t M, int64_t r
     return 0;
 }
 
+// the step-size probe's kernels over a.Mp particles: the grids of the two evaluation kernels above
+template <class LaneModel>
+static int launch_lane_stepsize(smcn_ctx* c, const StepArgs& a) {
+    int64_t blocks = (a.Mp + 255) / 256;
+    const int64_t cap = (int64_t)c->num_cu * 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    lane_stepsize_probe_kernel<LaneModel><<<(int)blocks, 256, 0, c->stream>>>(c->mdata, a);
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+template <class Model>
+static int launch_stepsize(smcn_ctx* c, Model, const StepArgs& a) {
+    constexpr int gpb = 256 / Model::G;
+    int64_t blocks = (a.Mp + gpb - 1) / gpb;
+    const int64_t cap = (int64_t)c->num_cu * 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    stepsize_probe_kernel<Model><<<(int)blocks, 256, sizeof(double) * Model::SHARED, c->stream>>>(c->mdata, a);
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+
 extern "C" {
+int smcn_stepsize_probe(smcn_ctx* c, const double* x, const double* logw, int64_t M, const double* r, const double* ladder,
+                        int L, int n_leapfrog, double phi, double delta_max, uint64_t seed, int64_t max_particles,
+                        double* partials, double* accept, int32_t* first_bad) {
+    CHECK_CTX(c);
+    if (c->model == SMCN_MODEL_HOST)
+        FAIL(c, "smcn_stepsize_probe: a host-evaluated target has no device functor to run the trajectories with; pass "
+                "step_size as a number");
+    if (!ladder || !partials || M < 1 || max_particles < 1) FAIL(c, "smcn_stepsize_probe: bad arguments");
+    if (L < 1 || L > kStepLadderMax)
+        FAIL(c, "smcn_stepsize_probe: 1 .. " + std::to_string(kStepLadderMax) + " ladder entries per call, not " + std::to_string(L));
+    if (n_leapfrog < 1 || n_leapfrog > kStepLeapMax)
+        FAIL(c, "smcn_stepsize_probe: 1 .. " + std::to_string(kStepLeapMax) + " leapfrogs per trajectory, not " + std::to_string(n_leapfrog));
+    for (int j = 0; j < L; ++j)
+        if (!std::isfinite(ladder[j]) || !(ladder[j] > 0.0) || (j > 0 && !(ladder[j] > ladder[j - 1])))
+            FAIL(c, "smcn_stepsize_probe: the ladder must be finite, positive and strictly increasing");
+    if (!std::isfinite(phi) || !(delta_max > 0.0)) FAIL(c, "smcn_stepsize_probe: phi must be finite and delta_max positive");
+    const int64_t Mp = M < max_particles ? M : max_particles;
+    const int D = c->D;
+    // st.buf: [lw M | r Mp D | a L Mp | partials (1 + L) 4];  st.ibuf: [first_bad L Mp | excluded Mp]
+    const int64_t o_r = (M + 15) / 16 * 16, o_a = o_r + (r ? Mp * D : 0), o_p = o_a + (int64_t)L * Mp;
+    int rc = grow(c, c->st.buf, o_p + (1 + kStepLadderMax) * 4);
+    if (rc) return rc;
+    if ((rc = grow(c, c->st.ibuf, (int64_t)(L + 1) * Mp))) return rc;
+    Particles P;
+    if ((rc = stage_particles(c, "smcn_stepsize_probe", x, logw, M, c->st.buf, &P))) return rc;
+    StepArgs a;
+    a.x = P.xd; a.rs = P.rs; a.cs = P.cs;
+    a.logw = P.lw;
+    a.r = nullptr;
+    if (r) {
+        HIPC(c, hipMemcpyAsync(c->st.buf + o_r, r, sizeof(double) * Mp * D, hipMemcpyHostToDevice, c->stream));
+        a.r = c->st.buf + o_r;
+    }
+    a.M = M; a.Mp = Mp;
+    a.particle_base = c->base;
+    a.seed = seed;
+    for (int j = 0; j < kStepLadderMax; ++j) a.ladder[j] = j < L ? ladder[j] : 0.0;
+    a.L = L; a.n = n_leapfrog;
+    a.phi = phi; a.delta_max = delta_max;
+    a.accept = c->st.buf + o_a;
+    a.first_bad = c->st.ibuf;
+    a.excluded = c->st.ibuf + (int64_t)L * Mp;
+    double* const part = c->st.buf + o_p;
+    HIPC(c, c->st.ev0.record(c->stream));
+    if (c->lane_kernel) rc = launch_lane_stepsize<ArmaLaneModel>(c, a);
+    else rc = with_model(c, [&](auto m) { return launch_stepsize(c, m, a); });
+    if (rc) return rc;
+    stepsize_reduce_kernel<<<1, kRedBlock, 0, c->stream>>>(a, part);
+    HIPC(c, hipGetLastError());
+    HIPC(c, c->st.ev1.record(c->stream));
+    HIPC(c, hipMemcpyAsync(partials, part, sizeof(double) * (1 + L) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (accept) HIPC(c, hipMemcpyAsync(accept, a.accept, sizeof(double) * L * Mp, hipMemcpyDeviceToHost, c->stream));
+    if (first_bad) HIPC(c, hipMemcpyAsync(first_bad, a.first_bad, sizeof(int32_t) * L * Mp, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    HIPC(c, c->st.ev1.since(c->st.ev0, &c->st.ms));
+    return 0;
+}
+double smcn_stepsize_last_ms(const smcn_ctx* c) { return c ? c->st.ms : -1.0; }
+
 int smcn_target_eval(smcn_ctx* c, const double* x, int64_t M, double phi, double* logp, double* grad, double* lpri,
                      double* llik) {
     CHECK_CTX(c);

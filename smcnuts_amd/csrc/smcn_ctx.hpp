@@ -86,6 +86,14 @@ struct CovState {
     Event ev[2];
     double ms = 0.0;
 };
+// step-size probe (smcn_stepsize_probe): staged log-weights and momenta, a [L][Mp], the partials; first-bad steps and
+// excluded flags; its kernels' time.  Its own buffers: the probe leaves every resident one as it found it
+struct StState {
+    Buf<double> buf;
+    Buf<int32_t> ibuf;
+    Event ev0, ev1;
+    double ms = 0.0;
+};
 }  // namespace smcn_host
 using namespace smcn_host;
 
@@ -209,6 +217,7 @@ struct smcn_ctx {
     DrState dr;
     SmState sm;
     CovState cov;
+    StState st;      // smcn_api.hip (it runs the models' device functors): the step-size probe
 };
 
 #define CHECK_CTX(c)            \

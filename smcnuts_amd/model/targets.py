@@ -17,6 +17,7 @@ import numpy as np
 from .. import _capi
 from .. import _checks
 from .. import covariance as _covariance
+from .. import stepsize as _stepsize
 from .. import summary as _summary
 from .._checks import GLM_DISPERSION, GLM_FAMILIES, GLM_MAX_DIM
 from ..predict import PredictMixin
@@ -105,6 +106,22 @@ class DeviceTarget:
         x2 = _checks.points(type(self).__name__, x, self.dim)
         lw = _summary.check_logw(logw, x2.shape[0])
         return _covariance.target_covariance(self, self._context(x2.shape[0]), np.ascontiguousarray(x2), lw)
+
+    def probe_step_size(self, x, logw=None, phi=1.0, target_accept=_stepsize.TARGET_ACCEPT,
+                        n_leapfrog=_stepsize.N_LEAPFROG, max_particles=_stepsize.MAX_PARTICLES, seed=0, r=None,
+                        ladder=None, refine=True, delta_max=100.0):
+        """stepsize.StepSizeProbe of the points x [M][D] (unconstrained) with log-weights logw (None: equal) at temperature
+        phi: n_leapfrog leapfrogs from each of min(M, max_particles) points at every step size of `ladder` (None:
+        stepsize.default_ladder()) on the device, and the largest step size whose weighted mean of min(1, exp(-dH))
+        stays at target_accept -- refined by a second pass between the two neighbours that bracket it.  Momenta: r
+        [min(M, max_particles)][D], or standard normal draws under `seed`."""
+        ladder = _stepsize.check_probe_args(target_accept, n_leapfrog, max_particles, ladder, phi, delta_max)
+        x2 = _checks.points(type(self).__name__, x, self.dim)
+        lw = _summary.check_logw(logw, x2.shape[0])
+        one_pass = _stepsize.context_pass(self._context(x2.shape[0]), None, x=np.ascontiguousarray(x2), logw=lw, r=r,
+                                          n_leapfrog=int(n_leapfrog), phi=float(phi), delta_max=float(delta_max),
+                                          seed=seed, max_particles=int(max_particles))
+        return _stepsize.run_probe(one_pass, ladder, float(target_accept), refine)
 
 
 class GaussianTarget(DeviceTarget):
@@ -199,6 +216,10 @@ class HostTarget:
         if ctx is None:
             ctx = self._sum_ctx = _capi.Context(256, self.model_id, self.model_data, device=self.device)
         return _covariance.target_covariance(self, ctx, x2, lw, v=v)
+
+    def probe_step_size(self, x, logw=None, **kw):
+        raise NotImplementedError("HostTarget: the step-size probe runs its trajectories through a device functor, and a "
+                                  "host-evaluated target has none; pass step_size as a number")
 
     def attach(self, ctx):
         """Register the density callback with a context created for this target."""

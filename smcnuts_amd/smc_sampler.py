@@ -58,7 +58,10 @@ class SMCSampler:
     `preallocate` (default True): the constructor allocates every device buffer of the device-resident loop -- the history of
     all K + 1 generations, block partials, per-transition records -- so that sample() starts with its first launch; a caller
     that only drives the host loop (step() / finalise(), which read none of them) or that is short of device memory passes
-    preallocate=False and the buffers are made by the first step_async() / run_fused() / sample() instead."""
+    preallocate=False and the buffers are made by the first step_async() / run_fused() / sample() instead.
+    `step_size`: a number, or "auto": the device measures one on generation 0 and its weights (probe_step_size();
+    DESIGN.md 4.5) before anything reads it -- `step_size` then holds the value and `step_size_probe` the
+    stepsize.StepSizeProbe (None with a number)."""
 
     def __init__(self, K, N, target, step_size, sample_proposal=None, momentum_proposal=None,
                  lkernel="forwardsLKernel", tempering=False, rng=None, *, forward_kernel=None, verbose=False,
@@ -66,6 +69,18 @@ class SMCSampler:
                  shard_resampling="global", resampling="multinomial", wide_eval=True, nuts_cap="auto", preallocate=True):
         from .model.targets import as_target
         target = as_target(target)      # host-evaluated targets are wrapped
+        # step_size="auto": measured on generation 0 by the step-size probe (below, once the particles exist)
+        auto_step = isinstance(step_size, str)
+        if auto_step:
+            if step_size != "auto":
+                raise ValueError(f"step_size={step_size!r}: pass a number, or \"auto\" to have the device measure one")
+            if forward_kernel is not None:
+                raise ValueError("step_size=\"auto\" sets the step size of the sampler's own NUTS proposal; with forward_kernel= "
+                                 "give that kernel its step size (retune_step_size() re-measures it later)")
+            if getattr(target, "host_evaluated", False):
+                raise ValueError("step_size=\"auto\" needs a device-native target (the probe runs through its device functor); "
+                                 "pass a number for a host-evaluated target")
+            step_size = float("nan")    # nothing reads it before the probe below has replaced it
         self.K = K
         self.N = N
         self.target = target
@@ -105,6 +120,10 @@ class SMCSampler:
                                wide_eval=wide_eval, nuts_cap=nuts_cap)
         self.N_local = self.samples.N_local
         self.samples.initialise_samples(x0=x0, logq0=logq0)
+        self.step_size_probe = None
+        if auto_step:
+            self.step_size_probe = self.retune_step_size()      # generation 0 and its weights
+        self.step_size = self.samples.forward_kernel.step_size
 
         Dc = getattr(target, "constrained_dim", target.dim)
         self._touch = None
@@ -502,6 +521,46 @@ class SMCSampler:
         bar = getattr(self, "_bar", None)
         if bar is not None and self.k > bar.n:
             bar.update(self.k - bar.n)
+
+    def probe_step_size(self, target_accept=0.8, n_leapfrog=8, max_particles=4096, seed=None, r=None, ladder=None,
+                        refine=True):
+        """stepsize.StepSizeProbe measured on the resident particles with their current weights at the current
+        temperature: n_leapfrog leapfrogs from each of (at most max_particles, over all shards) particles at every step
+        size of `ladder` (None: 2**-12 .. 2**3) on the device, and the largest step size whose weighted mean of
+        min(1, exp(-dH)) stays at target_accept, refined by a second pass between the two neighbours that bracket it.
+        Valid at any generation boundary -- after construction, between run_fused(upto=) or step() calls, after
+        sample(); it waits for the device first and changes nothing: not the particles, the weights, the momenta, the
+        history or the sampler's step size (retune_step_size() sets that).  seed=None: derived from the sampler's seed
+        and a call counter.  Several shards: each rank probes its shard, one host all-gather of the [1 + L][4]
+        partials per pass, every rank returns the same object."""
+        from . import stepsize as ss
+        fk, s = self.samples.forward_kernel, self.samples
+        delta_max = float(getattr(fk, "delta_max", 100.0))
+        ladder = ss.check_probe_args(target_accept, n_leapfrog, max_particles, ladder, s.phi_new, delta_max)
+        if getattr(self.target, "host_evaluated", False):
+            raise NotImplementedError("probe_step_size(): the probe runs its trajectories through the target's device "
+                                      "functor, and a host-evaluated target has none; pass step_size as a number")
+        if seed is None:                    # (every rank holds the same seed and makes the same calls: the same value everywhere)
+            self._probe_calls = getattr(self, "_probe_calls", 0) + 1
+            seed = (self.seed * 0xD1342543DE82EF95 + self._probe_calls) % 2 ** 64
+        ctx = s.ctx
+        ctx.call("smcn_synchronize")
+        per_shard = max(1, int(max_particles) // self.comm.world_size)
+        one_pass = ss.context_pass(ctx, self.comm, r=r, n_leapfrog=int(n_leapfrog), phi=float(s.phi_new),
+                                   delta_max=delta_max, seed=seed, max_particles=per_shard)
+        return ss.run_probe(one_pass, ladder, float(target_accept), refine)
+
+    def retune_step_size(self, **kw):
+        """probe_step_size(**kw), and the NUTS proposal's step size becomes the value it chose: the next launch uses it.
+        The loops never re-tune by themselves (a block of speculated transitions is launched with ONE step size);
+        between run_fused(upto=k) calls is the supported place.  Returns the StepSizeProbe (also in step_size_probe)."""
+        probe = self.probe_step_size(**kw)
+        if not (np.isfinite(probe.step_size) and probe.step_size > 0.0):
+            raise RuntimeError(f"the step-size probe found no usable value ({probe!r}): pass step_size as a number")
+        self.samples.forward_kernel.step_size = probe.step_size
+        self.step_size = probe.step_size
+        self.step_size_probe = probe
+        return probe
 
     def pointwise(self):
         """Per-observation criteria (criteria.Pointwise: lppd, WAIC, IS-LOO, fitted values) of the final generation and its
