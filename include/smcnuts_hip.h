@@ -747,6 +747,68 @@ int smcn_stepsize_probe(smcn_ctx* ctx, const double* x, const double* logw, int6
                         int32_t* first_bad /* [L][Mp] or NULL */);
 double smcn_stepsize_last_ms(const smcn_ctx* ctx);
 
+/* ---- forecasts of the arma target (SMCN_MODEL_ARMA only; every other model fails with a message that names it) ----
+ * Per point x = (mu, beta, theta, s), sigma = exp(s), and the context's series y_1..y_T (y_0 := mu, err_0 := 0):
+ *   err_1 = fma(-beta, mu, y_1 - mu),  err_t = fma(-theta, err_{t-1}, fma(-beta, y_{t-1}, y_t - mu))   (the density's bits)
+ *   y_{T+h} | y_{1:T}, x ~ N(m_h, v_h):  m_1 = fma(theta, err_T, fma(beta, y_T, mu)),  m_h = fma(beta, m_{h-1}, mu);
+ *   psi_0 = 1, psi_1 = beta + theta, psi_j = beta psi_{j-1};  C_1 = 1, C_h = fma(psi_{h-1}, psi_{h-1}, C_{h-1});
+ *   v_h = (sigma sigma) C_h.   Iterative: no 1 / (1 - beta); |beta| >= 1 gives growing, finite variances.
+ * A point is BAD at h when sigma, m_h or v_h is not finite or v_h <= 0.
+ * With a held-out continuation yf_1..yf_H:
+ *   marginal term  a_h = -0.5 (log 2 pi + log v_h) - 0.5 (yf_h - m_h)^2 / v_h      (NaN when bad at h)
+ *   joint term     J_h = sum_{j<=h} l_j,  l_j = (-0.5 log 2 pi - s) - 0.5 (e_j / sigma)^2, the recurrence continued through
+ *                  the held-out values: e_j = fma(-theta, e_{j-1}, fma(-beta, yf_{j-1}, yf_j - mu)), yf_0 = y_T, e_0 = err_T;
+ *                  J_h = llik(y_{1:T}, yf_{1:h}) - llik(y_{1:T}) of the arma density.
+ *
+ * smcn_forecast_set: the horizon H (1..512), the continuation y_future [H] or NULL, and thresholds at [H][Tn] (Tn 0..16,
+ * NULL with Tn = 0); all finite.  Owned by the context, replaced by the next call.
+ * smcn_forecast_dims: H, the column count Q = 10 + Tn of a partials block, whether y_future was given, Tn.
+ * smcn_forecast_slices: the particle slices of a smcn_forecast_partials call over M particles (a function of M alone:
+ * blocks of 256 particles), merged in slice order.
+ * smcn_forecast_points: the plain form for M caller-supplied points, out[M][W] row-major, W = 1 + 2H, with y_future
+ * 1 + 4H: err_T, m_1..m_H, v_1..v_H (, a_1..a_H, J_1..J_H).  A row with a non-finite coordinate is NaN throughout.
+ * smcn_forecast_partials: MERGEABLE partials out[1 + H][Q]; x == NULL: the resident particles with their resident
+ * log-weights (M = N, logw = NULL); logw == NULL with x: equal weights.  Row 0 is smcn_pointwise_partials' header
+ * [mw, sw, sw2, cnt, 0 ..].  Row h, with lw' = lw - mw, w = exp(lw'), over the contributing particles (finite lw) that are
+ * not bad at h:
+ *   0 ma    max (lw' + a_h) over finite terms  (-inf: none)
+ *   1 Sa    sum exp(lw' + a_h - ma)            lpd_marginal_h = ma + log Sa - log sw
+ *   2 mj    max (lw' + J_h) over finite terms
+ *   3 Sj    sum exp(lw' + J_h - mj)            lpd_joint_h = mj + log Sj - log sw
+ *   4 nbad  contributing particles that are bad at h: the row's moments and cdf are NaN
+ *   5 c     the shift of the moments (NaN: none): a wavefront's weighted mean of m_h, formed about the m_h of its first such
+ *           particle with w > 0; merged blocks keep the first block's
+ *   6 SW    sum w
+ *   7 S1    sum w (m_h - c)                    mean_h = c + S1 / SW
+ *   8 S2    sum w (m_h - c)^2                  between-particle variance S2 / SW - (S1 / SW)^2 (never sum w m^2 - mean^2)
+ *   9 V     sum w v_h                          var_h = V / SW + the between-particle variance
+ *   10 + k  sum w Phi((at[h][k] - m_h) / sqrt(v_h))      cdf[h][k] = that / SW
+ * Without y_future columns 0..3 are (-inf, 0, -inf, 0).  Merging two blocks (disjoint particle sets, in order) follows
+ * smcn_predict_partials: headers and the two (max, sum) pairs as max-shifted sums, the moments re-centred on the first
+ * block's c, every other column scaled by exp(mw_k - max(mw)) and added; nbad adds unscaled.  No atomics: a repeated call
+ * returns identical bits.
+ * smcn_forecast_draws: y_out[j][h - 1] = y_{T+h} of the path of slot s = s_first + j, j < s_count, of S, simulated from
+ * ONE particle a_s.  Ancestors: smcn_predict_draws' systematic rule with u0 = philox_uniform(seed, 0, 0, stream 20, 0);
+ * ancestors != NULL ([S], each in 0..M-1) replaces them.  z_{s,h} = sqrt(-2 log1p(-u_0)) cos(2 pi u_1), (u_0, u_1) the
+ * uniforms q = 0, 1 of philox_uniform(seed, iter = s, particle = h, stream 21), h = 1..H; e_h = sigma z_{s,h};
+ *   y_{T+1} = m_1 + e_1,   y_{T+h} = fma(theta, e_{h-1}, fma(beta, y_{T+h-1}, mu)) + e_h.
+ * A value depends on (seed, s, h) and its ancestor alone: not on S, the slot range or the tiling.  From the first
+ * non-finite value on a path is NaN; *n_bad_out counts the NaN values.
+ * smcn_forecast_last_ms: device time of the kernels of the last smcn_forecast_partials (ms[0]) and smcn_forecast_draws
+ * (ms[1]) (HIP events on the context's stream). */
+int smcn_forecast_set(smcn_ctx* ctx, int64_t H, const double* y_future_or_null /* [H] */,
+                      const double* at_or_null /* [H][Tn] */, int Tn);
+int smcn_forecast_dims(smcn_ctx* ctx, int64_t* H, int* Q, int* has_y, int* Tn);
+int smcn_forecast_slices(smcn_ctx* ctx, int64_t M, int64_t* slices);
+int smcn_forecast_points(smcn_ctx* ctx, const double* x /* [M][4] */, int64_t M, double* out /* [M][W] */);
+int smcn_forecast_partials(smcn_ctx* ctx, const double* x_or_null /* [M][4] */, const double* logw_or_null /* [M] */,
+                           int64_t M, double* out /* [1 + H][Q] */);
+int smcn_forecast_draws(smcn_ctx* ctx, const double* x_or_null /* [M][4] */, const double* logw_or_null /* [M] */, int64_t M,
+                        int64_t S, uint64_t seed, const int64_t* ancestors_or_null /* [S] */, int64_t s_first,
+                        int64_t s_count, double* y_out /* [s_count][H] */, int64_t* ancestors_out /* [s_count] */,
+                        int64_t* n_bad_out);
+int smcn_forecast_last_ms(const smcn_ctx* ctx, double ms[2]);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build. */

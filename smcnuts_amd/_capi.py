@@ -168,6 +168,14 @@ SIGNATURES = {
     "smcn_stepsize_probe": ([_ctx, _dp, _dp, C.c_int64, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64,
                              C.c_int64, _dp, _dp, _ip], C.c_int),
     "smcn_stepsize_last_ms": ([_ctx], C.c_double),
+    "smcn_forecast_set": ([_ctx, C.c_int64, _dp, _dp, C.c_int], C.c_int),
+    "smcn_forecast_dims": ([_ctx, _lp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "smcn_forecast_slices": ([_ctx, C.c_int64, _lp], C.c_int),
+    "smcn_forecast_points": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_forecast_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_forecast_draws": ([_ctx, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, _lp, C.c_int64, C.c_int64, _dp, _lp, _lp],
+                            C.c_int),
+    "smcn_forecast_last_ms": ([_ctx, _dp], C.c_int),
 }
 
 _lib = None
@@ -679,6 +687,80 @@ class Context:
     def stepsize_last_ms(self):
         """Device time of the last stepsize_probe's kernels (HIP events on the context's stream)."""
         return float(self._lib.smcn_stepsize_last_ms(self._h))
+
+    # ---- forecasts (SMCN_MODEL_ARMA; include/smcnuts_hip.h, smcn_forecast_*) --------------
+    def forecast_set(self, horizon, y_future=None, at=None):
+        """The horizon H, the held-out continuation [H] (or None) and the thresholds [H][Tn] (or None)."""
+        yf = None if y_future is None else np.ascontiguousarray(y_future, dtype=np.float64)
+        a = None if at is None else np.ascontiguousarray(at, dtype=np.float64)
+        if yf is not None and yf.shape != (int(horizon),):
+            raise ValueError("y_future must hold one value per horizon")
+        if a is not None and (a.ndim != 2 or a.shape[0] != int(horizon)):
+            raise ValueError("at must be [H][Tn]")
+        Tn = 0 if a is None else a.shape[1]
+        self.call("smcn_forecast_set", int(horizon), dptr(yf), dptr(a) if Tn else None, Tn)
+
+    def forecast_dims(self):
+        H, q, hy, tn = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self.call("smcn_forecast_dims", C.byref(H), C.byref(q), C.byref(hy), C.byref(tn))
+        return H.value, q.value, bool(hy.value), tn.value
+
+    def forecast_slices(self, M):
+        """The particle slices a forecast_partials call over M particles is merged from."""
+        n = C.c_int64(0)
+        self.call("smcn_forecast_slices", int(M), C.byref(n))
+        return n.value
+
+    def forecast_points(self, x):
+        """[M][1 + 2H (+ 2H)]: err_T, m_1..m_H, v_1..v_H and, with y_future, the marginal and the cumulative joint terms."""
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        H, _, hy, _ = self.forecast_dims()
+        out = np.empty((x.shape[0], 1 + (4 if hy else 2) * H))
+        self.call("smcn_forecast_points", dptr(x), x.shape[0], dptr(out))
+        return out
+
+    def forecast_partials(self, x=None, logw=None):
+        """[1 + H][Q] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
+        H, q, _, _ = self.forecast_dims()
+        out = np.empty((1 + H, q))
+        if x is None:
+            self.call("smcn_forecast_partials", None, None, self.N, dptr(out))
+        else:
+            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+            if lw is not None and lw.shape != (x.shape[0],):
+                raise ValueError("logw must hold one log-weight per row of x")
+            self.call("smcn_forecast_partials", dptr(x), dptr(lw), x.shape[0], dptr(out))
+        return out
+
+    def forecast_draws(self, S, seed, x=None, logw=None, ancestors=None, s_first=0, s_count=None):
+        """(y [s_count][H], ancestors [s_count], n_bad): simulated paths of the slots s_first .. of S over the horizon of
+        the last forecast_set (include/smcnuts_hip.h); x=None: the resident particles and weights."""
+        H, _, _, _ = self.forecast_dims()
+        S = int(S)
+        n = S - int(s_first) if s_count is None else int(s_count)
+        y, anc, nbad = np.empty((max(n, 0), H)), np.empty(max(n, 0), dtype=np.int64), C.c_int64(0)
+        a_in = None if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+        if a_in is not None and a_in.shape != (S,):
+            raise ValueError("ancestors must hold one particle index per path")
+        if x is None:
+            xp, lp_, M = None, None, self.N
+        else:
+            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+            if lw is not None and lw.shape != (x.shape[0],):
+                raise ValueError("logw must hold one log-weight per row of x")
+            xp, lp_, M = dptr(x), dptr(lw), x.shape[0]
+        self.call("smcn_forecast_draws", xp, lp_, M, S, C.c_uint64(int(seed) & (2 ** 64 - 1)), lptr(a_in), int(s_first), n,
+                  dptr(y), lptr(anc), C.byref(nbad))
+        return y, anc, nbad.value
+
+    def forecast_last_ms(self):
+        """Device time [partials, draws] of the last forecast calls' kernels (HIP events on the context's stream)."""
+        ms = np.zeros(2)
+        if self._lib.smcn_forecast_last_ms(self._h, dptr(ms)) != 0:
+            raise SmcnError("smcn_forecast_last_ms failed")
+        return ms
 
     def timers(self, reset=False):
         t = np.zeros(6)

@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # The library's translation units (csrc/smcn_ctx.hpp: who owns which kernels).  The core is the longest compile.
-UNITS = ["smcn_api.hip", "smcn_loo.hip", "smcn_predict.hip", "smcn_summary.hip"]
+UNITS = ["smcn_api.hip", "smcn_loo.hip", "smcn_predict.hip", "smcn_summary.hip", "smcn_forecast.hip"]
 LIB = os.path.join(HERE, "libsmcnuts_hip.so")
 
 # Where a build reads and writes.  `flags_file` is this file: the compiler flags live here, so it dates every object.

@@ -1,6 +1,7 @@
 // What the units of libsmcnuts_hip.so share (internal, not installed): the context, its owner types, the entry points'
 // macros and the few host helpers that cross units.  smcn_api.hip is the core (context, sampler, loops, exchange); the
-// post-fit subsystems are smcn_loo.hip, smcn_predict.hip and smcn_summary.hip, each with its own sub-struct of smcn_ctx.
+// post-fit subsystems are smcn_loo.hip, smcn_predict.hip, smcn_summary.hip and smcn_forecast.hip, each with its own
+// sub-struct of smcn_ctx.
 // Every __global__ function is instantiated in exactly ONE unit: a unit that needs another's kernel calls the host
 // launcher declared at the end of this file.  Everything here but smcn_ctx lives in smcn_host, whose symbols are hidden:
 // none of them reaches the library's dynamic symbol table.
@@ -93,6 +94,16 @@ struct StState {
     Buf<int32_t> ibuf;
     Event ev0, ev1;
     double ms = 0.0;
+};
+// arma forecasts (smcn_forecast_*): the setting of the last smcn_forecast_set ([y_future H | at H Tn] on the device, H = 0:
+// none), the slices' and groups' partials and the result of a call, the paths' work area; device time of the last
+// partials and draws calls
+struct FcState {
+    Buf<double> set, buf, dbuf;
+    int64_t H = 0;
+    int Tn = 0, has_y = 0;
+    Event ev0, ev1;
+    double ms[2] = {};
 };
 }  // namespace smcn_host
 using namespace smcn_host;
@@ -218,6 +229,7 @@ struct smcn_ctx {
     SmState sm;
     CovState cov;
     StState st;      // smcn_api.hip (it runs the models' device functors): the step-size probe
+    FcState fc;      // smcn_forecast.hip
 };
 
 #define CHECK_CTX(c)            \
@@ -303,4 +315,9 @@ void launch_scan(smcn_ctx* c, const double* w, int64_t M, int nt, double* local,
 // smcn_loo.hip.  The header of a call's log-weights, and ll [M][n] of the GLM block L describes (a: pw_args over it)
 void launch_pointwise_header(smcn_ctx* c, const double* lw, int64_t M, double* head);
 void launch_glm_loglik(smcn_ctx* c, const RegLayout& L, const PwArgs& a, int64_t tiles, int64_t blocks, double* out);
+// smcn_predict.hip.  The systematic ancestors of the slots s_first .. s_first + n - 1 of S (smcn_predict_draws' rule) from
+// the log-weights lw [M] and their header, the comb's offset uniform on Philox stream `stream`; w, local [M], ttot [nt],
+// toff [nt + 1] (nt = the scan tiles of M): work areas
+void launch_draw_ancestors(smcn_ctx* c, const double* lw, const double* head, int64_t M, int64_t S, int64_t s_first, int64_t n,
+                           uint64_t seed, uint32_t stream, double* w, double* local, double* ttot, double* toff, int64_t* anc);
 }  // namespace smcn_host

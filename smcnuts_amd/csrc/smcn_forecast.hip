@@ -1,0 +1,186 @@
+// libsmcnuts_hip.so, the forecast unit: the arma target's h-step laws, their mixture's partials and simulated paths
+// (smcn_forecast_*).  Owns the kernels of smcn_forecast.hpp and smcn_ctx's fc.
+#include <cmath>
+
+#include "smcn_ctx.hpp"
+#include "smcn_forecast.hpp"
+
+static const char* kFcScope = "forecasts cover SMCN_MODEL_ARMA contexts only";
+#define FC_CHECK(c, who)                                                                       \
+    CHECK_CTX(c);                                                                              \
+    if ((c)->model != SMCN_MODEL_ARMA) FAIL(c, std::string(who) + ": " + kFcScope);
+#define FC_CHECK_SET(c, who) \
+    if ((c)->fc.H < 1) FAIL(c, std::string(who) + ": no horizon (smcn_forecast_set first)")
+
+static int64_t fc_slices(int64_t M) { return (M + kFcBlock - 1) / kFcBlock; }
+// slices whose partials the slab holds at once: whole groups, at most 4096 slices and about 2^22 doubles
+static int64_t fc_window(int64_t H, int Q) {
+    int64_t w = ((int64_t)1 << 22) / (H * Q);
+    w = w > 4096 ? 4096 : w;
+    w = w / kFcGroup * kFcGroup;
+    return w < kFcGroup ? kFcGroup : w;
+}
+static const double* fc_yf(const smcn_ctx* c) { return c->fc.has_y ? (const double*)c->fc.set : nullptr; }
+static const double* fc_at(const smcn_ctx* c) { return c->fc.Tn ? (const double*)c->fc.set + c->fc.H : nullptr; }
+
+extern "C" {
+
+int smcn_forecast_set(smcn_ctx* c, int64_t H, const double* y_future, const double* at, int Tn) {
+    FC_CHECK(c, "smcn_forecast_set");
+    if (H < 1 || H > kFcMaxH) FAIL(c, "smcn_forecast_set: the horizon H must be in 1..512");
+    if (Tn < 0 || Tn > kFcMaxAt) FAIL(c, "smcn_forecast_set: the number of thresholds per horizon Tn must be in 0..16");
+    if ((Tn > 0) != (at != nullptr)) FAIL(c, "smcn_forecast_set: `at` holds [H][Tn] thresholds (NULL with Tn = 0 only)");
+    std::vector<double> h((size_t)(H * (1 + Tn)), 0.0);
+    for (int64_t i = 0; y_future && i < H; ++i) {
+        if (!std::isfinite(y_future[i])) FAIL(c, "smcn_forecast_set: y_future[" + std::to_string(i) + "] is not finite");
+        h[i] = y_future[i];
+    }
+    for (int64_t i = 0; i < H * Tn; ++i) {
+        if (!std::isfinite(at[i])) FAIL(c, "smcn_forecast_set: at[" + std::to_string(i) + "] is not finite");
+        h[H + i] = at[i];
+    }
+    c->fc.H = 0;
+    const int rc = grow(c, c->fc.set, (int64_t)h.size());
+    if (rc) return rc;
+    HIPC(c, stream_wait(c->stream));                             // (a kernel of an earlier call may still read the setting)
+    HIPC(c, hipMemcpyAsync(c->fc.set, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, stream_wait(c->stream));                             // (h is a local)
+    c->fc.H = H;
+    c->fc.Tn = Tn;
+    c->fc.has_y = y_future ? 1 : 0;
+    return 0;
+}
+
+int smcn_forecast_dims(smcn_ctx* c, int64_t* H, int* Q, int* has_y, int* Tn) {
+    FC_CHECK(c, "smcn_forecast_dims");
+    FC_CHECK_SET(c, "smcn_forecast_dims");
+    if (H) *H = c->fc.H;
+    if (Q) *Q = kFcCols + c->fc.Tn;
+    if (has_y) *has_y = c->fc.has_y;
+    if (Tn) *Tn = c->fc.Tn;
+    return 0;
+}
+
+int smcn_forecast_slices(smcn_ctx* c, int64_t M, int64_t* slices) {
+    FC_CHECK(c, "smcn_forecast_slices");
+    FC_CHECK_SET(c, "smcn_forecast_slices");
+    if (M < 1 || !slices) FAIL(c, "smcn_forecast_slices: bad arguments");
+    *slices = fc_slices(M);
+    return 0;
+}
+
+int smcn_forecast_points(smcn_ctx* c, const double* x, int64_t M, double* out) {
+    FC_CHECK(c, "smcn_forecast_points");
+    FC_CHECK_SET(c, "smcn_forecast_points");
+    if (!x || !out || M < 1) FAIL(c, "smcn_forecast_points: bad arguments");
+    const int64_t H = c->fc.H, W = 1 + (c->fc.has_y ? 4 : 2) * H;
+    if (fc_slices(M) > 2147483647LL) FAIL(c, "smcn_forecast_points: too many points");
+    int rc = ensure_stage(c, M * c->D);
+    if (rc) return rc;
+    if ((rc = grow(c, c->fc.buf, M * W))) return rc;
+    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+    forecast_points_kernel<<<(int)fc_slices(M), kFcBlock, 0, c->stream>>>(c->mdata, c->stage, M, (int)H, fc_yf(c), c->fc.buf);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, c->fc.buf, sizeof(double) * M * W, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
+int smcn_forecast_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
+    FC_CHECK(c, "smcn_forecast_partials");
+    FC_CHECK_SET(c, "smcn_forecast_partials");
+    if (!out || M < 1) FAIL(c, "smcn_forecast_partials: bad arguments");
+    const int H = (int)c->fc.H, Tn = c->fc.Tn, Q = kFcCols + Tn;
+    const int64_t slices = fc_slices(M), groups = (slices + kFcGroup - 1) / kFcGroup, win = fc_window(H, Q);
+    const int64_t row = (int64_t)H * Q;
+    if (groups > 65535) FAIL(c, "smcn_forecast_partials: too many particles (M <= 268431360)");
+    // fc.buf: [header 16 | lw M | slab (a window of slices) | group partials | result (1 + H) Q]
+    const int64_t o_lw = 16, o_slab = o_lw + (M + 15) / 16 * 16, o_grp = o_slab + (slices < win ? slices : win) * row;
+    const int64_t o_out = o_grp + groups * row;
+    int rc = grow(c, c->fc.buf, o_out + (1 + H) * Q);
+    if (rc) return rc;
+    double* const B = c->fc.buf;
+    Particles P;
+    if ((rc = stage_particles(c, "smcn_forecast_partials", x, logw, M, B + o_lw, &P))) return rc;
+    HIPC(c, c->fc.ev0.record(c->stream));
+    launch_pointwise_header(c, P.lw, M, B);
+    for (int64_t s0 = 0; s0 < slices; s0 += win) {
+        const int64_t ns = slices - s0 < win ? slices - s0 : win, ng = (ns + kFcGroup - 1) / kFcGroup;
+        if (c->fc.has_y)
+            forecast_partials_kernel<true><<<(int)ns, kFcBlock, 0, c->stream>>>(c->mdata, P.xd, P.rs, P.cs, P.lw, B, M, s0 * kFcBlock, H,
+                                                                                 Tn, fc_yf(c), fc_at(c), B + o_slab);
+        else
+            forecast_partials_kernel<false><<<(int)ns, kFcBlock, 0, c->stream>>>(c->mdata, P.xd, P.rs, P.cs, P.lw, B, M, s0 * kFcBlock, H,
+                                                                                  Tn, nullptr, fc_at(c), B + o_slab);
+        forecast_merge_kernel<false><<<dim3((unsigned)grid_for(row, 256), (unsigned)ng), 256, 0, c->stream>>>(
+            B + o_slab, B, ns, H, Q, B + o_grp + s0 / kFcGroup * row);
+    }
+    forecast_merge_kernel<true><<<grid_for(row, 256), 256, 0, c->stream>>>(B + o_grp, B, groups, H, Q, B + o_out);
+    HIPC(c, hipGetLastError());
+    HIPC(c, c->fc.ev1.record(c->stream));
+    HIPC(c, hipMemcpyAsync(out, B + o_out, sizeof(double) * (1 + H) * Q, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    HIPC(c, c->fc.ev1.since(c->fc.ev0, &c->fc.ms[0]));
+    return 0;
+}
+
+int smcn_forecast_draws(smcn_ctx* c, const double* x, const double* logw, int64_t M, int64_t S, uint64_t seed,
+                        const int64_t* ancestors, int64_t s_first, int64_t s_count, double* y_out, int64_t* ancestors_out,
+                        int64_t* n_bad_out) {
+    FC_CHECK(c, "smcn_forecast_draws");
+    FC_CHECK_SET(c, "smcn_forecast_draws");
+    if (M < 1) FAIL(c, "smcn_forecast_draws: M must be at least 1");
+    if (S < 1 || S > 2147483647LL) FAIL(c, "smcn_forecast_draws: the number of paths S must be in 1..2^31-1");
+    if (s_first < 0 || s_count < 1 || s_first + s_count > S)
+        FAIL(c, "smcn_forecast_draws: the slot range [s_first, s_first + s_count) must be non-empty and lie in 0..S");
+    if (!y_out) FAIL(c, "smcn_forecast_draws: y_out is null");
+    if (ancestors)
+        for (int64_t s = 0; s < S; ++s)
+            if (ancestors[s] < 0 || ancestors[s] >= M)
+                FAIL(c, "smcn_forecast_draws: ancestors[" + std::to_string(s) + "] is not a particle in 0..M-1");
+    const int64_t H = c->fc.H, n = s_count;
+    // fc.dbuf: [header 16 | lw M | w M | scan M | tile totals nt | tile offsets nt + 1 | ancestors n | y n H]
+    const int nt = (int)((M + kScanTile - 1) / kScanTile);
+    const auto pad = [](int64_t v) { return (v + 15) / 16 * 16; };
+    const int64_t o_lw = 16, o_w = o_lw + pad(M), o_loc = o_w + pad(M), o_tt = o_loc + pad(M), o_to = o_tt + pad(nt);
+    const int64_t o_anc = o_to + pad(nt + 1), o_y = o_anc + pad(n);
+    int rc = grow(c, c->fc.dbuf, o_y + n * H);
+    if (rc) return rc;
+    double* const B = c->fc.dbuf;
+    int64_t* const anc = (int64_t*)(B + o_anc);
+    Particles P;
+    if ((rc = stage_particles(c, "smcn_forecast_draws", x, logw, M, B + o_lw, &P))) return rc;
+    if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, c->fc.ev0.record(c->stream));
+    double cnt = 1.0;
+    if (!ancestors) {
+        launch_pointwise_header(c, P.lw, M, B);
+        HIPC(c, hipMemcpyAsync(&cnt, B + 3, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, stream_wait(c->stream));
+        if (cnt == 0.0) FAIL(c, "smcn_forecast_draws: no particle has a finite log-weight");
+        launch_draw_ancestors(c, P.lw, B, M, S, s_first, n, seed, kStreamFcAnc, B + o_w, B + o_loc, B + o_tt, B + o_to, anc);
+    }
+    forecast_draws_kernel<<<grid_for(n, kFcBlock), kFcBlock, 0, c->stream>>>(c->mdata, P.xd, P.rs, P.cs, anc, n, s_first, seed, (int)H,
+                                                                            B + o_y);
+    HIPC(c, hipGetLastError());
+    HIPC(c, c->fc.ev1.record(c->stream));
+    if (ancestors_out) HIPC(c, hipMemcpyAsync(ancestors_out, anc, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(y_out, B + o_y, sizeof(double) * n * H, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    HIPC(c, c->fc.ev1.since(c->fc.ev0, &c->fc.ms[1]));
+    if (n_bad_out) {
+        int64_t nb = 0;
+        for (int64_t e = 0; e < n * H; ++e) nb += y_out[e] != y_out[e] ? 1 : 0;
+        *n_bad_out = nb;
+    }
+    return 0;
+}
+
+int smcn_forecast_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    ms[0] = c->fc.ms[0];
+    ms[1] = c->fc.ms[1];
+    return 0;
+}
+
+}  // extern "C"

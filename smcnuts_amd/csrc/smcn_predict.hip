@@ -257,6 +257,15 @@ static void dr_launch(smcn_ctx* c, const double* xg, int64_t n, const DrawArgs& 
     }
 }
 
+void smcn_host::launch_draw_ancestors(smcn_ctx* c, const double* lw, const double* head, int64_t M, int64_t S, int64_t s_first,
+                                      int64_t n, uint64_t seed, uint32_t stream, double* w, double* local, double* ttot,
+                                      double* toff, int64_t* anc) {
+    const int nt = (int)((M + kScanTile - 1) / kScanTile);
+    draws_weights_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(lw, head, M, w);
+    launch_scan(c, w, M, nt, local, ttot, toff);
+    draws_ancestors_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(local, toff, nt, M, lw, S, s_first, n, seed, stream, anc);
+}
+
 extern "C" {
 
 int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t M, int64_t S, uint64_t seed,
@@ -303,9 +312,7 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
     HIPC(c, c->pw.ev0.record(c->stream));
     if (!ancestors) {
         launch_pointwise_header(c, lw, M, head);
-        draws_weights_kernel<<<grid_for(M, 256), 256, 0, c->stream>>>(lw, head, M, B + o_w);
-        launch_scan(c, B + o_w, M, nt, B + o_loc, B + o_tt, B + o_to);
-        draws_ancestors_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(B + o_loc, B + o_to, nt, M, lw, S, s_first, n, seed, anc);
+        launch_draw_ancestors(c, lw, head, M, S, s_first, n, seed, kStreamDrawAnc, B + o_w, B + o_loc, B + o_tt, B + o_to, anc);
     }
     draws_gather_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(P.xd, P.rs, P.cs, anc, n, c->D, B + o_xg);
     const DrawArgs d{seed, s_first, new_group ? ng : nullptr};

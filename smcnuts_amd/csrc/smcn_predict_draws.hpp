@@ -145,14 +145,14 @@ __global__ void draws_weights_kernel(const double* __restrict__ lw, const double
     const double v = lw[t];
     w[t] = finite_d(v) ? pw_exp_neg(v - head[0]) : 0.0;
 }
-// a_s = min{p : C_p > (s + u0) / S} on C = (tile offset + blocked scan) / total, clamped to the last contributing particle
+// a_s = min{p : C_p > (s + u0) / S}, u0 on Philox stream `stream`, on C = (tile offset + blocked scan) / total, clamped to the last contributing particle
 __global__ void draws_ancestors_kernel(const double* __restrict__ local, const double* __restrict__ toff, int nt, int64_t M,
                                        const double* __restrict__ lw, int64_t S, int64_t s_first, int64_t s_count,
-                                       uint64_t seed, int64_t* __restrict__ anc) {
+                                       uint64_t seed, uint32_t stream, int64_t* __restrict__ anc) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= s_count) return;
     const double total = toff[(M - 1) / kScanTile] + local[M - 1];
-    const double u0 = philox_uniform(seed, 0u, 0u, kStreamDrawAnc, 0u);
+    const double u0 = philox_uniform(seed, 0u, 0u, stream, 0u);
     const double key = ((double)(s_first + j) + u0) / (double)S;
     int64_t lo = cdf_search(key, total, toff, local, nt, M, false);
     if (lo >= M) {

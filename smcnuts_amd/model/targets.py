@@ -17,10 +17,11 @@ import numpy as np
 from .. import _capi
 from .. import _checks
 from .. import covariance as _covariance
+from .. import forecast as _forecast
 from .. import stepsize as _stepsize
 from .. import summary as _summary
 from .._checks import GLM_DISPERSION, GLM_FAMILIES, GLM_MAX_DIM
-from ..predict import PredictMixin
+from ..predict import PredictiveDraws, PredictMixin
 
 DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
@@ -272,12 +273,77 @@ class ArmaModel(DeviceTarget):
     """stan_models/arma/arma.stan; unconstrained (mu, beta, theta, log sigma)."""
     model_id = _capi.MODEL_ARMA
 
-    def __init__(self, data_path=None):
-        d = _load_json(data_path or os.path.join(DATA_DIR, "arma.json"))
-        y = np.asarray(d["y"], dtype=np.float64)
-        if int(d["T"]) != y.size:
-            raise ValueError("arma data: T != len(y)")
+    def __init__(self, data_path=None, *, y=None):
+        """The series from a JSON file {"T": .., "y": [..]} (None: the shipped one), or as an array y (1-D, finite, at
+        least one value)."""
+        if y is not None:
+            if data_path is not None:
+                raise ValueError("ArmaModel: give the series as data_path or as y, not both")
+            try:
+                y = np.asarray(y, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("ArmaModel: y must be numeric") from None
+            if y.ndim != 1 or y.size < 1:
+                raise ValueError("ArmaModel: y must be a 1-D series of at least one value")
+            if not np.all(np.isfinite(y)):
+                raise ValueError("ArmaModel: y must be finite")
+        else:
+            d = _load_json(data_path or os.path.join(DATA_DIR, "arma.json"))
+            y = np.asarray(d["y"], dtype=np.float64)
+            if int(d["T"]) != y.size:
+                raise ValueError("arma data: T != len(y)")
         super().__init__(np.concatenate([[float(y.size)], y]), 4, ["mu", "beta", "theta", "sigma"])
+
+    # ---- forecasts (smcnuts_amd/forecast.py); every argument check runs on the host, before a context exists ----
+    def _forecast_args(self, who, horizon, y_future=None, at=None):
+        H = _forecast.check_horizon(who, horizon)
+        return H, _forecast.check_y_future(who, y_future, H), _forecast.check_at(who, at, H)
+
+    def forecast_points(self, x, horizon, y_future=None):
+        """Per point of x ([4] or [M, 4]) the h-step laws of y_{T+1..T+H}: dict(err_T [M], m [M, H], v [M, H]) and, with
+        y_future, marginal [M, H] (log N(yf_h | m_h, v_h)) and joint [M, H] (the cumulative log density of yf_1..yf_h
+        given the series).  A point with a non-finite coordinate gives NaN."""
+        H, yf, _ = self._forecast_args("ArmaModel.forecast_points", horizon, y_future)
+        x2 = _checks.points("ArmaModel", x, self.dim)
+        ctx = self._context(x2.shape[0])
+        ctx.forecast_set(H, yf)
+        o = ctx.forecast_points(x2)
+        out = dict(err_T=o[:, 0], m=o[:, 1:1 + H], v=o[:, 1 + H:1 + 2 * H])
+        if yf is not None:
+            out.update(marginal=o[:, 1 + 2 * H:1 + 3 * H], joint=o[:, 1 + 3 * H:1 + 4 * H])
+        return out
+
+    def forecast_partials(self, x, horizon, logw=None, y_future=None, at=None):
+        """The mergeable partials of x's rows over the horizon ([1 + H][10 + Tn], include/smcnuts_hip.h)."""
+        H, yf, a = self._forecast_args("ArmaModel.forecast", horizon, y_future, at)
+        x2 = _checks.points("ArmaModel", x, self.dim)
+        if logw is not None and np.shape(logw) != (x2.shape[0],):
+            raise ValueError("ArmaModel.forecast: logw must hold one log-weight per row of x")
+        ctx = self._context(x2.shape[0])
+        ctx.forecast_set(H, yf, a)
+        return ctx.forecast_partials(x2, logw)
+
+    def forecast(self, x, horizon, logw=None, y_future=None, at=None):
+        """Posterior predictive summaries of y_{T+1..T+H} from the weighted points (x [M, 4], logw unnormalised or None
+        for equal weights) -> forecast.Forecast: mean, var, sd; with `at` (a scalar, [Tn] or [H][Tn], Tn <= 16) the
+        mixture's cdf there; with y_future [H] the log predictive densities lpd_marginal and lpd_joint."""
+        part = self.forecast_partials(x, horizon, logw, y_future, at)
+        a = _forecast.check_at("ArmaModel.forecast", at, int(horizon))
+        return _forecast.combine_forecast_partials([part], 0 if a is None else a.shape[1], y_future is not None, a)
+
+    def forecast_draws(self, x, horizon, n_draws, seed=0, logw=None, ancestors=None):
+        """n_draws simulated paths y_{T+1..T+H} from the weighted points (x [M, 4], logw unnormalised or None for equal
+        weights; ancestors: the particle of each path instead of the systematic resampling) -> predict.PredictiveDraws
+        (y [n_draws][H]): mean(), interval() and pvalue() give predictive intervals and path statistics."""
+        H = _forecast.check_horizon("ArmaModel.forecast_draws", horizon)
+        x2 = _checks.points("ArmaModel", x, self.dim)
+        M = x2.shape[0]
+        S, ancestors = _forecast.check_draws("ArmaModel.forecast_draws", n_draws, ancestors, M)
+        if logw is not None and np.shape(logw) != (M,):
+            raise ValueError("ArmaModel.forecast_draws: logw must hold one log-weight per row of x")
+        ctx = self._context(M)
+        ctx.forecast_set(H)
+        return PredictiveDraws(*ctx.forecast_draws(S, seed, x2, logw, ancestors))
 
 
 class PRMwCDModel(DeviceTarget):

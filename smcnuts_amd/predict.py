@@ -181,8 +181,9 @@ def _philox_uniform(seed, it, particle, stream, q):
 ANCESTOR_STREAM = 16
 
 
-def shard_slots(lw, S, seed, comm):
-    """Several shards, one systematic comb: (s_first, s_count, local ancestors [S] (0 outside the range), rank offsets).
+def shard_slots(lw, S, seed, comm, stream=ANCESTOR_STREAM):
+    """Several shards, one systematic comb (its offset u0 on Philox stream `stream`): (s_first, s_count, local ancestors
+    [S] (0 outside the range), rank offsets).
     Every rank all-gathers (largest finite log-weight, sum of exp(lw - that)); A, the ranks' cumulative weight bounds, is
     summed on the host in rank order with the last bound +inf; rank r owns the slots whose position (s + u0) / S falls in
     [A_r, A_r+1) and searches its own cumulative sum, offset by A_r, for them."""
@@ -200,7 +201,7 @@ def shard_slots(lw, S, seed, comm):
     A = np.concatenate([[0.0], np.cumsum(tot)])
     total = A[-1]
     r = comm.rank
-    pos = (np.arange(S) + _philox_uniform(int(seed), 0, 0, ANCESTOR_STREAM, 0)) / S
+    pos = (np.arange(S) + _philox_uniform(int(seed), 0, 0, stream, 0)) / S
     bounds = A / total
     bounds[-1] = np.inf
     own = np.nonzero((pos >= bounds[r]) & (pos < bounds[r + 1]))[0]

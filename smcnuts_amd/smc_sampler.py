@@ -752,6 +752,75 @@ class SMCSampler:
         tot = allp.sum(0)           # (every slot has one owner; the others hold zeros there)
         return PredictiveDraws(tot[:S * m].reshape(S, m), tot[S * m:S * m + S].astype(np.int64), int(tot[-1]))
 
+    def _forecast_guards(self, who):
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError(f"{who}(): the asymptotic L-kernel's estimates pool generations; forecasts over the "
+                                      "pooled generations are not implemented")
+        if not hasattr(self.target, "forecast_partials"):
+            raise NotImplementedError(f"{type(self.target).__name__}: forecasts are implemented for ArmaModel")
+
+    def _forecast_ready(self, who):
+        if not self._finalised:
+            raise RuntimeError(f"{who}(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"{who}(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
+                               "target the posterior")
+
+    def forecast(self, horizon, y_future=None, at=None):
+        """Posterior predictive summaries of y_{T+1..T+horizon} of an ArmaModel (forecast.Forecast: mean, var, sd; with
+        `at` the mixture's cdf at the thresholds; with y_future the marginal and the cumulative joint log predictive
+        densities) of the final generation and its weights, after sample() / finalise(): computed from the resident
+        particles, nothing is downloaded but the [1 + H][Q] partials.  Several shards: every rank computes its partials,
+        ONE host all-gather moves them, every rank combines them in rank order."""
+        from .forecast import combine_forecast_partials
+        self._forecast_guards("forecast")
+        H, yf, a = self.target._forecast_args("forecast", horizon, y_future, at)
+        self._forecast_ready("forecast")
+        Tn = 0 if a is None else a.shape[1]
+        ctx = self.samples.ctx
+        ctx.call("smcn_synchronize")
+        ctx.forecast_set(H, yf, a)
+        part = ctx.forecast_partials()
+        if self.comm.world_size > 1:
+            allp = np.asarray(self.comm.allgather(part.reshape(-1)))
+            return combine_forecast_partials([p.reshape(part.shape) for p in allp], Tn, yf is not None, a)
+        return combine_forecast_partials([part], Tn, yf is not None, a)
+
+    def forecast_draws(self, horizon, n_draws=1000, seed=None):
+        """Simulated paths y_{T+1..T+horizon} of an ArmaModel (predict.PredictiveDraws: y [n_draws][horizon], each path
+        from one particle of the final generation chosen by systematic resampling of its weights), after sample() /
+        finalise().  seed=None: derived from the sampler's rng.  Several shards: one host all-gather of the ranks' weight
+        totals assigns every rank the slots of the comb that fall in its share, each rank simulates its own, one host
+        all-gather assembles [S][H]."""
+        from .forecast import ANCESTOR_STREAM, check_draws, check_horizon
+        from .predict import PredictiveDraws, shard_slots
+        self._forecast_guards("forecast_draws")
+        H = check_horizon("forecast_draws", horizon)
+        S, _ = check_draws("forecast_draws", n_draws, None, None)
+        self._forecast_ready("forecast_draws")
+        if seed is None:                    # (every rank holds the same rng / seed: the same value everywhere)
+            if self.rng is not None:
+                seed = int(self.rng.integers(0, 2 ** 63))
+            else:
+                self._draws_calls = getattr(self, "_draws_calls", 0) + 1
+                seed = (self.seed * 0x9E3779B97F4A7C15 + self._draws_calls) % 2 ** 64
+        ctx = self.samples.ctx
+        ctx.call("smcn_synchronize")
+        ctx.forecast_set(H)
+        if self.comm.world_size == 1:
+            return PredictiveDraws(*ctx.forecast_draws(S, seed))
+        _, lw, _ = ctx.get_state(x=False)
+        s0, n, anc, offs = shard_slots(lw, S, seed, self.comm, stream=ANCESTOR_STREAM)
+        mine = np.zeros(S * H + S + 1)
+        if n:
+            y, _, nbad = ctx.forecast_draws(S, seed, ancestors=anc, s_first=s0, s_count=n)
+            mine[s0 * H:(s0 + n) * H] = y.reshape(-1)
+            mine[S * H + s0:S * H + s0 + n] = anc[s0:s0 + n] + offs[self.comm.rank]
+            mine[-1] = nbad
+        allp = np.asarray(self.comm.allgather(mine)).reshape(self.comm.world_size, -1)
+        tot = allp.sum(0)           # (every slot has one owner; the others hold zeros there)
+        return PredictiveDraws(tot[:S * H].reshape(S, H), tot[S * H:S * H + S].astype(np.int64), int(tot[-1]))
+
     def sample(self, show_progress=True):
         start_time = time()
         if self.device_resident and not self._host_loop_used:
