@@ -178,6 +178,11 @@ __global__ void __launch_bounds__(64) temper_multi_decide_kernel(const double* g
             fv = __builtin_nan("");
         } else if (q.mx == -kInf) {
             fv = __builtin_nan("");                       // every weight -inf: ESS undefined (the reference's nan)
+        } else if (q.s1 == 0.0 && finite_d(q.mx)) {
+            // every weight that is not masked sits at the maximum: (sum w)^2 / sum w^2 = cnt^2 / s2, their count, exactly --
+            // not the count times the rounding of e^(-2 log cnt).  (f(phi_old) at phi_old = 0 is this case: with a
+            // target of N it is the root at the left end that bisect.c returns, and an error of either sign otherwise.)
+            fv = q.cnt * q.cnt / q.s2 - target;
         } else {
             const double shift = finite_d(q.mx) ? q.mx : 0.0;
             const double sm = q.s1 == 0.0 ? q.s1 : q.s1 / q.cnt;
@@ -210,7 +215,9 @@ __global__ void __launch_bounds__(64) temper_multi_decide_kernel(const double* g
         const double fm = f[node - 1];
         ++steps;
         node = 2 * node;
-        if (fm * fa >= 0.0) { xa = xm; node += 1; }
+        // fm * fa >= 0 without the product, which underflows to +-0 for two tiny values of opposite sign (and -0 >= 0);
+        // a NaN on either side keeps xa, as the product did
+        if ((fm > 0.0 && fa > 0.0) || (fm < 0.0 && fa < 0.0) || fm == 0.0) { xa = xm; node += 1; }
         if (fm == 0.0 || fabs(dm) < xtol + rtol * fabs(xm)) { st[TB_RESULT] = xm; st[TB_DONE] = 1.0; break; }
         if (steps >= 100) { st[TB_ERROR] = 2.0; st[TB_DONE] = 1.0; st[TB_RESULT] = __builtin_nan(""); break; }   // "Failed to converge"
     }

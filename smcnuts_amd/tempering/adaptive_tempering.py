@@ -27,7 +27,7 @@ def bisect(f, xa, xb, xtol=_XTOL, rtol=_RTOL, maxiter=_MAXITER):
         dm *= 0.5
         xm = xa + dm
         fm = f(xm)
-        if fm * fa >= 0:
+        if (fm > 0 and fa > 0) or (fm < 0 and fa < 0) or fm == 0:      # fm * fa >= 0 without the product, which underflows
             xa = xm
         if fm == 0 or abs(dm) < xtol + rtol * abs(xm):
             return xm
