@@ -261,6 +261,23 @@ class Context:
         if rc != 0:
             raise SmcnError(f"{name}: {self._lib.smcn_last_error(self._h).decode()}")
 
+    def _particles(self, x, logw):
+        """(x, logw, M) as the post-fit entry points take them: x=None: the resident particles and weights."""
+        if x is None:
+            return None, None, self.N
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
+        if lw is not None and lw.shape != (x.shape[0],):
+            raise ValueError("logw must hold one log-weight per row of x")
+        return dptr(x), dptr(lw), x.shape[0]
+
+    def _last_ms(self, name, n=0):
+        """What the timer entry point `name` reports: a number, or n of them."""
+        ms = np.zeros(max(n, 1))
+        if getattr(self._lib, name)(self._h, dptr(ms)) != 0:
+            raise SmcnError(f"{name} failed")
+        return ms if n else float(ms[0])
+
     # ---- convenience wrappers -------------------------------------------------
     def set_seed(self, seed):
         self.call("smcn_set_seed", C.c_uint64(int(seed) & (2 ** 64 - 1)))
@@ -410,52 +427,32 @@ class Context:
         """[1 + n][Q] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
         n, q = self.pointwise_dims()
         out = np.empty((1 + n, q))
-        if x is None:
-            self.call("smcn_pointwise_partials", None, None, self.N, dptr(out))
-        else:
-            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-            if lw is not None and lw.shape != (x.shape[0],):
-                raise ValueError("logw must hold one log-weight per row of x")
-            self.call("smcn_pointwise_partials", dptr(x), dptr(lw), x.shape[0], dptr(out))
+        self.call("smcn_pointwise_partials", *self._particles(x, logw), dptr(out))
         return out
 
     def pointwise_last_ms(self):
         """Device time of the last pointwise_partials' kernels (HIP events on the context's stream)."""
-        ms = C.c_double(0.0)
-        rc = self._lib.smcn_pointwise_last_ms(self._h, C.byref(ms))
-        if rc != 0:
-            raise SmcnError("smcn_pointwise_last_ms failed")
-        return ms.value
+        return self._last_ms("smcn_pointwise_last_ms")
 
     # ---- Pareto-smoothed LOO (SMCN_MODEL_GLM; include/smcnuts_hip.h, smcn_psis_*) ------
-    def _psis_points(self, x, logw):
-        if x is None:
-            return None, None, self.N
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-        lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-        if lw is not None and lw.shape != (x.shape[0],):
-            raise ValueError("logw must hold one log-weight per row of x")
-        return x, lw, x.shape[0]
-
     def psis_candidates(self, mw, S, x=None, logw=None):
         """(lr, ll), each [n][T_cap]: this rank's T_cap largest ratios per observation, descending."""
         from .psis import tail_len
-        x, lw, M = self._psis_points(x, logw)
+        xp, lp_, M = self._particles(x, logw)
         n, _ = self.pointwise_dims()
         out = np.empty((2, n, tail_len(S) + 1))
-        self.call("smcn_psis_candidates", dptr(x), dptr(lw), M, float(mw), int(S), dptr(out))
+        self.call("smcn_psis_candidates", xp, lp_, M, float(mw), int(S), dptr(out))
         return out[0], out[1]
 
     def psis_body(self, mw, S, cutoff, x=None, logw=None):
         """[n][4] body partials (mb, Sb, Sb2, Sw) of the particles at or below the per-observation cutoffs."""
-        x, lw, M = self._psis_points(x, logw)
+        xp, lp_, M = self._particles(x, logw)
         n, _ = self.pointwise_dims()
         cutoff = np.ascontiguousarray(cutoff, dtype=np.float64)
         if cutoff.shape != (n,):
             raise ValueError("cutoff must hold one value per observation")
         out = np.empty((n, 4))
-        self.call("smcn_psis_body", dptr(x), dptr(lw), M, float(mw), int(S), dptr(cutoff), dptr(out))
+        self.call("smcn_psis_body", xp, lp_, M, float(mw), int(S), dptr(cutoff), dptr(out))
         return out
 
     def psis_fit(self, lr, ll, body, mw, S):
@@ -472,18 +469,15 @@ class Context:
 
     def psis_loo(self, x=None, logw=None):
         """([n][6], header [mw, sw, sw2, S]) of one rank's particles: the three stages without a host round trip."""
-        x, lw, M = self._psis_points(x, logw)
+        xp, lp_, M = self._particles(x, logw)
         n, _ = self.pointwise_dims()
         out, head = np.empty((n, 6)), np.empty(4)
-        self.call("smcn_psis_loo", dptr(x), dptr(lw), M, dptr(out), dptr(head))
+        self.call("smcn_psis_loo", xp, lp_, M, dptr(out), dptr(head))
         return out, head
 
     def psis_last_ms(self):
         """Device time [candidates, body, fit, whole psis_loo] of the last calls (HIP events on the context's stream)."""
-        ms = np.zeros(4)
-        if self._lib.smcn_psis_last_ms(self._h, dptr(ms)) != 0:
-            raise SmcnError("smcn_psis_last_ms failed")
-        return ms
+        return self._last_ms("smcn_psis_last_ms", 4)
 
     # ---- held-out prediction (GLM, hierarchical, categorical, ordinal) ----------------
     def predict_set_data(self, block, has_y):
@@ -507,57 +501,37 @@ class Context:
         """[1 + m][Q] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
         m, q, _ = self.predict_dims()
         out = np.empty((1 + m, q))
-        if x is None:
-            self.call("smcn_predict_partials", None, None, self.N, dptr(out))
-        else:
-            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-            if lw is not None and lw.shape != (x.shape[0],):
-                raise ValueError("logw must hold one log-weight per row of x")
-            self.call("smcn_predict_partials", dptr(x), dptr(lw), x.shape[0], dptr(out))
+        self.call("smcn_predict_partials", *self._particles(x, logw), dptr(out))
         return out
 
     def predict_last_ms(self):
         """Device time of the last predict_partials' kernels (HIP events on the context's stream)."""
-        ms = C.c_double(0.0)
-        rc = self._lib.smcn_predict_last_ms(self._h, C.byref(ms))
-        if rc != 0:
-            raise SmcnError("smcn_predict_last_ms failed")
-        return ms.value
+        return self._last_ms("smcn_predict_last_ms")
+
+    def _draws(self, fn, width, noun, S, seed, x, logw, ancestors, s_first, s_count, grouped=False, new_group=None):
+        """The body of predict_draws and forecast_draws: `width` values per `noun`; grouped: `fn` takes new_group."""
+        S = int(S)
+        n = S - int(s_first) if s_count is None else int(s_count)
+        y, anc, nbad = np.empty((max(n, 0), width)), np.empty(max(n, 0), dtype=np.int64), C.c_int64(0)
+        a_in = None if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+        if a_in is not None and a_in.shape != (S,):
+            raise ValueError(f"ancestors must hold one particle index per {noun}")
+        g_in = None if new_group is None else np.ascontiguousarray(new_group, dtype=np.int64)
+        if g_in is not None and g_in.shape != (width,):
+            raise ValueError("new_group must hold one label per new row")
+        self.call(fn, *self._particles(x, logw), S, C.c_uint64(int(seed) & (2 ** 64 - 1)), lptr(a_in),
+                  *((lptr(g_in),) if grouped else ()), int(s_first), n, dptr(y), lptr(anc), C.byref(nbad))
+        return y, anc, nbad.value
 
     def predict_draws(self, S, seed, x=None, logw=None, ancestors=None, new_group=None, s_first=0, s_count=None):
         """(y [s_count][m], ancestors [s_count], n_bad): posterior predictive draws of the slots s_first .. of S at the
         rows of the last predict_set_data (include/smcnuts_hip.h); x=None: the resident particles and weights."""
-        m, _, _ = self.predict_dims()
-        S = int(S)
-        n = S - int(s_first) if s_count is None else int(s_count)
-        y, anc, nbad = np.empty((max(n, 0), m)), np.empty(max(n, 0), dtype=np.int64), C.c_int64(0)
-        ip = lambda a: None if a is None else a.ctypes.data_as(_lp)
-        a_in = None if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
-        if a_in is not None and a_in.shape != (S,):
-            raise ValueError("ancestors must hold one particle index per draw")
-        g_in = None if new_group is None else np.ascontiguousarray(new_group, dtype=np.int64)
-        if g_in is not None and g_in.shape != (m,):
-            raise ValueError("new_group must hold one label per new row")
-        if x is None:
-            xp, lp_, M = None, None, self.N
-        else:
-            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-            if lw is not None and lw.shape != (x.shape[0],):
-                raise ValueError("logw must hold one log-weight per row of x")
-            xp, lp_, M = dptr(x), dptr(lw), x.shape[0]
-        self.call("smcn_predict_draws", xp, lp_, M, S, C.c_uint64(int(seed) & (2 ** 64 - 1)), ip(a_in), ip(g_in),
-                  int(s_first), n, dptr(y), ip(anc), C.byref(nbad))
-        return y, anc, nbad.value
+        return self._draws("smcn_predict_draws", self.predict_dims()[0], "draw", S, seed, x, logw, ancestors, s_first, s_count,
+                           True, new_group)
 
     def predict_draws_last_ms(self):
         """Device time of the last predict_draws' kernels (HIP events on the context's stream)."""
-        ms = C.c_double(0.0)
-        rc = self._lib.smcn_predict_draws_last_ms(self._h, C.byref(ms))
-        if rc != 0:
-            raise SmcnError("smcn_predict_draws_last_ms failed")
-        return ms.value
+        return self._last_ms("smcn_predict_draws_last_ms")
 
     # ---- posterior summaries (every model) ---------------------------------------------
     def summary_begin(self, x=None, logw=None, v=None):
@@ -567,15 +541,12 @@ class Context:
         if x is None and v is None:
             self.call("smcn_summary_begin", None, None, None, self.N, 0, dptr(head))
             return head, self.Dc
-        a = np.ascontiguousarray(np.atleast_2d(x if v is None else v), dtype=np.float64)
-        lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-        if lw is not None and lw.shape != (a.shape[0],):
-            raise ValueError("logw must hold one log-weight per row of x")
+        ap, lp_, M = self._particles(x if v is None else v, logw)
         if v is None:
-            self.call("smcn_summary_begin", dptr(a), dptr(lw), None, a.shape[0], 0, dptr(head))
+            self.call("smcn_summary_begin", ap, lp_, None, M, 0, dptr(head))
             return head, self.Dc
-        self.call("smcn_summary_begin", None, dptr(lw), dptr(a), a.shape[0], a.shape[1], dptr(head))
-        return head, a.shape[1]
+        self.call("smcn_summary_begin", None, lp_, ap, M, np.atleast_2d(v).shape[1], dptr(head))
+        return head, np.atleast_2d(v).shape[1]
 
     def summary_weights(self, lw_max, lw_sum):
         m = C.c_double(0.0)
@@ -610,16 +581,10 @@ class Context:
 
     def summary_last_ms(self):
         """Device time of the summary kernels since the last summary_begin (HIP events on the context's stream)."""
-        ms = C.c_double(0.0)
-        if self._lib.smcn_summary_last_ms(self._h, C.byref(ms)) != 0:
-            raise SmcnError("smcn_summary_last_ms failed")
-        return ms.value
+        return self._last_ms("smcn_summary_last_ms")
 
     def summary_pass_ms(self):
-        ms = np.zeros(8)
-        if self._lib.smcn_summary_pass_ms(self._h, dptr(ms)) != 0:
-            raise SmcnError("smcn_summary_pass_ms failed")
-        return ms
+        return self._last_ms("smcn_summary_pass_ms", 8)
 
     # ---- posterior covariance (every model; the population staged by summary_begin) -----
     def cov_dims(self):
@@ -647,10 +612,7 @@ class Context:
 
     def cov_last_ms(self):
         """Device time of the last cov_partials' kernels (HIP events on the context's stream)."""
-        ms = C.c_double(0.0)
-        if self._lib.smcn_cov_last_ms(self._h, C.byref(ms)) != 0:
-            raise SmcnError("smcn_cov_last_ms failed")
-        return ms.value
+        return self._last_ms("smcn_cov_last_ms")
 
     # ---- step-size probe (every device-native model) -----------------------------------
     def stepsize_probe(self, ladder, x=None, logw=None, r=None, n_leapfrog=8, phi=1.0, delta_max=100.0, seed=0,
@@ -662,15 +624,11 @@ class Context:
         if x is None:
             if logw is not None:
                 raise ValueError("the resident particles come with their resident log-weights (x=None: logw=None)")
-            xp, lp_, M = None, None, self.N
         else:
             x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
             if x.shape[1] != self.D:
                 raise ValueError(f"x must hold {self.D} coordinates per row")
-            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-            if lw is not None and lw.shape != (x.shape[0],):
-                raise ValueError("logw must hold one log-weight per row of x")
-            xp, lp_, M = dptr(x), dptr(lw), x.shape[0]
+        xp, lp_, M = self._particles(x, logw)
         Mp = min(M, int(max_particles))
         if r is not None:
             r = np.ascontiguousarray(r, dtype=np.float64)
@@ -723,44 +681,18 @@ class Context:
         """[1 + H][Q] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
         H, q, _, _ = self.forecast_dims()
         out = np.empty((1 + H, q))
-        if x is None:
-            self.call("smcn_forecast_partials", None, None, self.N, dptr(out))
-        else:
-            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-            if lw is not None and lw.shape != (x.shape[0],):
-                raise ValueError("logw must hold one log-weight per row of x")
-            self.call("smcn_forecast_partials", dptr(x), dptr(lw), x.shape[0], dptr(out))
+        self.call("smcn_forecast_partials", *self._particles(x, logw), dptr(out))
         return out
 
     def forecast_draws(self, S, seed, x=None, logw=None, ancestors=None, s_first=0, s_count=None):
         """(y [s_count][H], ancestors [s_count], n_bad): simulated paths of the slots s_first .. of S over the horizon of
         the last forecast_set (include/smcnuts_hip.h); x=None: the resident particles and weights."""
-        H, _, _, _ = self.forecast_dims()
-        S = int(S)
-        n = S - int(s_first) if s_count is None else int(s_count)
-        y, anc, nbad = np.empty((max(n, 0), H)), np.empty(max(n, 0), dtype=np.int64), C.c_int64(0)
-        a_in = None if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
-        if a_in is not None and a_in.shape != (S,):
-            raise ValueError("ancestors must hold one particle index per path")
-        if x is None:
-            xp, lp_, M = None, None, self.N
-        else:
-            x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-            lw = None if logw is None else np.ascontiguousarray(logw, dtype=np.float64)
-            if lw is not None and lw.shape != (x.shape[0],):
-                raise ValueError("logw must hold one log-weight per row of x")
-            xp, lp_, M = dptr(x), dptr(lw), x.shape[0]
-        self.call("smcn_forecast_draws", xp, lp_, M, S, C.c_uint64(int(seed) & (2 ** 64 - 1)), lptr(a_in), int(s_first), n,
-                  dptr(y), lptr(anc), C.byref(nbad))
-        return y, anc, nbad.value
+        return self._draws("smcn_forecast_draws", self.forecast_dims()[0], "path", S, seed, x, logw, ancestors, s_first,
+                           s_count)
 
     def forecast_last_ms(self):
         """Device time [partials, draws] of the last forecast calls' kernels (HIP events on the context's stream)."""
-        ms = np.zeros(2)
-        if self._lib.smcn_forecast_last_ms(self._h, dptr(ms)) != 0:
-            raise SmcnError("smcn_forecast_last_ms failed")
-        return ms
+        return self._last_ms("smcn_forecast_last_ms", 2)
 
     def timers(self, reset=False):
         t = np.zeros(6)

@@ -17,6 +17,7 @@
 #include "../../include/smcnuts_hip.h"
 #include "smcn_comm.hpp"
 #include "smcn_devbuf.hpp"
+#include "smcn_draw_plan.hpp"
 #include "smcn_regdata.hpp"
 
 namespace smcn { struct PwArgs; }   // (smcn_pw_walk.hpp)
@@ -320,4 +321,42 @@ void launch_glm_loglik(smcn_ctx* c, const RegLayout& L, const PwArgs& a, int64_t
 // toff [nt + 1] (nt = the scan tiles of M): work areas
 void launch_draw_ancestors(smcn_ctx* c, const double* lw, const double* head, int64_t M, int64_t S, int64_t s_first, int64_t n,
                            uint64_t seed, uint32_t stream, double* w, double* local, double* ttot, double* toff, int64_t* anc);
+
+// ---- the two ends of a draw call (smcn_predict_draws, smcn_forecast_draws) over the work area B (smcn_draw_plan.hpp) ------
+// The ancestors of the call's n slots in B + p.o_anc: the caller's, uploaded ahead of ev0, or behind it the systematic
+// ones from lw.  check_now: read the weights' finite count and refuse a population without one before the ancestors are
+// launched (otherwise draw_finish reads it with the result)
+inline int draw_ancestors(smcn_ctx* c, const char* who, Event& ev0, const DrawPlan& p, double* B, const double* lw, int64_t M,
+                          int64_t S, int64_t s_first, int64_t n, uint64_t seed, uint32_t stream, const int64_t* ancestors,
+                          bool check_now) {
+    int64_t* const anc = (int64_t*)(B + p.o_anc);
+    if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, ev0.record(c->stream));
+    if (ancestors) return 0;
+    launch_pointwise_header(c, lw, M, B);
+    if (check_now) {
+        double cnt = 1.0;
+        HIPC(c, hipMemcpyAsync(&cnt, B + 3, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, stream_wait(c->stream));
+        if (cnt == 0.0) FAIL(c, std::string(who) + ": no particle has a finite log-weight");
+    }
+    launch_draw_ancestors(c, lw, B, M, S, s_first, n, seed, stream, B + p.o_w, B + p.o_loc, B + p.o_tt, B + p.o_to, anc);
+    return 0;
+}
+// Behind the call's last kernel: ev1, the downloads (cnt_d: the finite count to check, or NULL; the ancestors if asked
+// for; y [len]), the wait, the kernels' time and the NaN count
+inline int draw_finish(smcn_ctx* c, const char* who, Event& ev0, Event& ev1, double* ms, const double* cnt_d, const int64_t* anc,
+                       int64_t n, const double* y, int64_t len, double* y_out, int64_t* ancestors_out, int64_t* n_bad_out) {
+    HIPC(c, hipGetLastError());
+    HIPC(c, ev1.record(c->stream));
+    double cnt = 1.0;
+    if (cnt_d) HIPC(c, hipMemcpyAsync(&cnt, cnt_d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (ancestors_out) HIPC(c, hipMemcpyAsync(ancestors_out, anc, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(y_out, y, sizeof(double) * len, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    HIPC(c, ev1.since(ev0, ms));
+    if (cnt == 0.0) FAIL(c, std::string(who) + ": no particle has a finite log-weight");
+    if (n_bad_out) *n_bad_out = count_nan(y_out, len);
+    return 0;
+}
 }  // namespace smcn_host

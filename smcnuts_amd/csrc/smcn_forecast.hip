@@ -129,51 +129,24 @@ int smcn_forecast_draws(smcn_ctx* c, const double* x, const double* logw, int64_
                         int64_t* n_bad_out) {
     FC_CHECK(c, "smcn_forecast_draws");
     FC_CHECK_SET(c, "smcn_forecast_draws");
-    if (M < 1) FAIL(c, "smcn_forecast_draws: M must be at least 1");
-    if (S < 1 || S > 2147483647LL) FAIL(c, "smcn_forecast_draws: the number of paths S must be in 1..2^31-1");
-    if (s_first < 0 || s_count < 1 || s_first + s_count > S)
-        FAIL(c, "smcn_forecast_draws: the slot range [s_first, s_first + s_count) must be non-empty and lie in 0..S");
-    if (!y_out) FAIL(c, "smcn_forecast_draws: y_out is null");
-    if (ancestors)
-        for (int64_t s = 0; s < S; ++s)
-            if (ancestors[s] < 0 || ancestors[s] >= M)
-                FAIL(c, "smcn_forecast_draws: ancestors[" + std::to_string(s) + "] is not a particle in 0..M-1");
+    const std::string why = draw_refusal("smcn_forecast_draws", "paths", M, S, s_first, s_count, y_out, ancestors);
+    if (!why.empty()) FAIL(c, why);
     const int64_t H = c->fc.H, n = s_count;
-    // fc.dbuf: [header 16 | lw M | w M | scan M | tile totals nt | tile offsets nt + 1 | ancestors n | y n H]
-    const int nt = (int)((M + kScanTile - 1) / kScanTile);
-    const auto pad = [](int64_t v) { return (v + 15) / 16 * 16; };
-    const int64_t o_lw = 16, o_w = o_lw + pad(M), o_loc = o_w + pad(M), o_tt = o_loc + pad(M), o_to = o_tt + pad(nt);
-    const int64_t o_anc = o_to + pad(nt + 1), o_y = o_anc + pad(n);
+    // fc.dbuf: [the plan's front | y n H]
+    const DrawPlan p(M, n, kScanTile);
+    const int64_t o_y = p.o_tail;
     int rc = grow(c, c->fc.dbuf, o_y + n * H);
     if (rc) return rc;
     double* const B = c->fc.dbuf;
-    int64_t* const anc = (int64_t*)(B + o_anc);
+    const int64_t* const anc = (const int64_t*)(B + p.o_anc);
     Particles P;
-    if ((rc = stage_particles(c, "smcn_forecast_draws", x, logw, M, B + o_lw, &P))) return rc;
-    if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, c->fc.ev0.record(c->stream));
-    double cnt = 1.0;
-    if (!ancestors) {
-        launch_pointwise_header(c, P.lw, M, B);
-        HIPC(c, hipMemcpyAsync(&cnt, B + 3, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, stream_wait(c->stream));
-        if (cnt == 0.0) FAIL(c, "smcn_forecast_draws: no particle has a finite log-weight");
-        launch_draw_ancestors(c, P.lw, B, M, S, s_first, n, seed, kStreamFcAnc, B + o_w, B + o_loc, B + o_tt, B + o_to, anc);
-    }
+    if ((rc = stage_particles(c, "smcn_forecast_draws", x, logw, M, B + p.o_lw, &P))) return rc;
+    if ((rc = draw_ancestors(c, "smcn_forecast_draws", c->fc.ev0, p, B, P.lw, M, S, s_first, n, seed, kStreamFcAnc, ancestors, true)))
+        return rc;
     forecast_draws_kernel<<<grid_for(n, kFcBlock), kFcBlock, 0, c->stream>>>(c->mdata, P.xd, P.rs, P.cs, anc, n, s_first, seed, (int)H,
                                                                             B + o_y);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->fc.ev1.record(c->stream));
-    if (ancestors_out) HIPC(c, hipMemcpyAsync(ancestors_out, anc, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(y_out, B + o_y, sizeof(double) * n * H, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    HIPC(c, c->fc.ev1.since(c->fc.ev0, &c->fc.ms[1]));
-    if (n_bad_out) {
-        int64_t nb = 0;
-        for (int64_t e = 0; e < n * H; ++e) nb += y_out[e] != y_out[e] ? 1 : 0;
-        *n_bad_out = nb;
-    }
-    return 0;
+    return draw_finish(c, "smcn_forecast_draws", c->fc.ev0, c->fc.ev1, &c->fc.ms[1], nullptr, anc, n, B + o_y, n * H, y_out,
+                       ancestors_out, n_bad_out);
 }
 
 int smcn_forecast_last_ms(const smcn_ctx* c, double* ms) {

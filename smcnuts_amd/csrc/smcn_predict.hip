@@ -274,64 +274,38 @@ int smcn_predict_draws(smcn_ctx* c, const double* x, const double* logw, int64_t
     CHECK_CTX(c);
     if (!pr_model(c)) FAIL(c, std::string("smcn_predict_draws: ") + kPrScope);
     if (c->pr.lay.n < 1) FAIL(c, "smcn_predict_draws: no new rows (smcn_predict_set_data first)");
-    if (M < 1) FAIL(c, "smcn_predict_draws: M must be at least 1");
-    if (S < 1 || S > 2147483647LL) FAIL(c, "smcn_predict_draws: the number of draws S must be in 1..2^31-1");
-    if (s_first < 0 || s_count < 1 || s_first + s_count > S)
-        FAIL(c, "smcn_predict_draws: the slot range [s_first, s_first + s_count) must be non-empty and lie in 0..S");
-    if (!y_out) FAIL(c, "smcn_predict_draws: y_out is null");
+    // (new_group is refused between y_out and the caller's ancestors: the plan's check runs without them first)
+    std::string why = draw_refusal("smcn_predict_draws", "draws", M, S, s_first, s_count, y_out, nullptr);
+    if (!why.empty()) FAIL(c, why);
     if (new_group && c->model != SMCN_MODEL_HGLM) FAIL(c, "smcn_predict_draws: new_group is for SMCN_MODEL_HGLM only");
     const int64_t m = c->pr.lay.n, tiles = (m + 63) / 64, n = s_count;
     if (new_group)
         for (int64_t i = 0; i < m; ++i)
             if (new_group[i] < 0 || new_group[i] > 4294967295LL)
                 FAIL(c, "smcn_predict_draws: new_group[" + std::to_string(i) + "] is not a label in 0..2^32-1");
-    if (ancestors)
-        for (int64_t s = 0; s < S; ++s)
-            if (ancestors[s] < 0 || ancestors[s] >= M)
-                FAIL(c, "smcn_predict_draws: ancestors[" + std::to_string(s) + "] is not a particle in 0..M-1");
+    why = draw_refusal("smcn_predict_draws", "draws", M, S, s_first, s_count, y_out, ancestors);
+    if (!why.empty()) FAIL(c, why);
     PR_CHECK_LDS(c, false, "smcn_predict_draws");
     int64_t cps = 1;
     if (tiles * pointwise_slices(n, m, &cps) > 2147483647LL) FAIL(c, "smcn_predict_draws: too many rows");
-    // dr.buf: [header 16 | lw M | w M | scan M | tile totals nt | tile offsets nt + 1 | ancestors n | labels m | xg D n | y n m]
-    const int nt = (int)((M + kScanTile - 1) / kScanTile);
-    const auto pad = [](int64_t v) { return (v + 15) / 16 * 16; };
-    const int64_t o_lw = 16, o_w = o_lw + pad(M), o_loc = o_w + pad(M), o_tt = o_loc + pad(M), o_to = o_tt + pad(nt);
-    const int64_t o_anc = o_to + pad(nt + 1), o_ng = o_anc + pad(n), o_xg = o_ng + pad(m), o_y = o_xg + pad(n * c->D);
-    const int64_t need = o_y + n * m;
-    int rc = grow(c, c->dr.buf, need);
+    // dr.buf: [the plan's front | labels m | xg D n | y n m]
+    const DrawPlan p(M, n, kScanTile);
+    const int64_t o_ng = p.o_tail, o_xg = o_ng + p.pad(m), o_y = o_xg + p.pad(n * c->D);
+    int rc = grow(c, c->dr.buf, o_y + n * m);
     if (rc) return rc;
     double* const B = c->dr.buf;
-    double* const head = B;
-    int64_t* const anc = (int64_t*)(B + o_anc);
+    const int64_t* const anc = (const int64_t*)(B + p.o_anc);
     int64_t* const ng = (int64_t*)(B + o_ng);
     Particles P;
-    if ((rc = stage_particles(c, "smcn_predict_draws", x, logw, M, B + o_lw, &P))) return rc;
-    const double* const lw = P.lw;
+    if ((rc = stage_particles(c, "smcn_predict_draws", x, logw, M, B + p.o_lw, &P))) return rc;
     if (new_group) HIPC(c, hipMemcpyAsync(ng, new_group, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
-    if (ancestors) HIPC(c, hipMemcpyAsync(anc, ancestors + s_first, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, c->pw.ev0.record(c->stream));
-    if (!ancestors) {
-        launch_pointwise_header(c, lw, M, head);
-        launch_draw_ancestors(c, lw, head, M, S, s_first, n, seed, kStreamDrawAnc, B + o_w, B + o_loc, B + o_tt, B + o_to, anc);
-    }
+    if ((rc = draw_ancestors(c, "smcn_predict_draws", c->pw.ev0, p, B, P.lw, M, S, s_first, n, seed, kStreamDrawAnc, ancestors, false)))
+        return rc;
     draws_gather_kernel<<<grid_for(n, 256), 256, 0, c->stream>>>(P.xd, P.rs, P.cs, anc, n, c->D, B + o_xg);
     const DrawArgs d{seed, s_first, new_group ? ng : nullptr};
     dr_launch(c, B + o_xg, n, d, B + o_y);
-    HIPC(c, hipGetLastError());
-    HIPC(c, c->pw.ev1.record(c->stream));
-    double cnt = 1.0;
-    if (!ancestors) HIPC(c, hipMemcpyAsync(&cnt, head + 3, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (ancestors_out) HIPC(c, hipMemcpyAsync(ancestors_out, anc, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(y_out, B + o_y, sizeof(double) * n * m, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_wait(c->stream));
-    HIPC(c, c->pw.ev1.since(c->pw.ev0, &c->dr.ms));
-    if (cnt == 0.0) FAIL(c, "smcn_predict_draws: no particle has a finite log-weight");
-    if (n_bad_out) {
-        int64_t nb = 0;
-        for (int64_t e = 0; e < n * m; ++e) nb += y_out[e] != y_out[e] ? 1 : 0;
-        *n_bad_out = nb;
-    }
-    return 0;
+    return draw_finish(c, "smcn_predict_draws", c->pw.ev0, c->pw.ev1, &c->dr.ms, ancestors ? nullptr : B + 3, anc, n, B + o_y, n * m,
+                       y_out, ancestors_out, n_bad_out);
 }
 
 int smcn_predict_draws_last_ms(const smcn_ctx* c, double* ms) {

@@ -562,31 +562,78 @@ class SMCSampler:
         self.step_size_probe = probe
         return probe
 
+    # ---- what the post-fit products share: a new one starts from these ------------------------------------
+    def _refuse_pooled(self, who, noun):
+        if self.lkernel == "asymptoticLKernel":
+            raise NotImplementedError(f"{who}(): the asymptotic L-kernel's estimates pool generations; {noun} over the "
+                                      "pooled generations are not implemented")
+
+    def _final_generation(self, who):
+        """The context of the final generation at phi = 1, the device waited for."""
+        if not self._finalised:
+            raise RuntimeError(f"{who}(): run sample() (or step() K times and finalise()) first")
+        if self.phi[self.K] != 1.0:
+            raise RuntimeError(f"{who}(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
+                               "target the posterior")
+        self.samples.ctx.call("smcn_synchronize")
+        return self.samples.ctx
+
+    def _gather_partials(self, part):
+        """Every rank's partials in rank order: ONE host all-gather."""
+        if self.comm.world_size == 1:
+            return [part]
+        return [p.reshape(part.shape) for p in np.asarray(self.comm.allgather(part.reshape(-1)))]
+
+    def _constrained_population(self, ctx):
+        """(keywords for device_summary / device_covariance, the parameters' names): a host-evaluated target's own
+        constrain() runs on the host (as for the moments)."""
+        t, kw = self.target, {}
+        if getattr(t, "host_evaluated", False) and callable(getattr(t.target, "constrain", None)):
+            x, lw, _ = ctx.get_state()
+            kw = dict(v=np.ascontiguousarray(t.constrain(x), dtype=np.float64), logw=lw)
+        names, Dc = list(t.param_names()), self.mean_estimate.shape[1]
+        return kw, names if len(names) == Dc else [f"x.{i + 1}" for i in range(Dc)]
+
+    def _draw_seed(self, seed):
+        if seed is not None:
+            return seed
+        if self.rng is not None:            # (every rank holds the same rng / seed: the same value everywhere)
+            return int(self.rng.integers(0, 2 ** 63))
+        self._draws_calls = getattr(self, "_draws_calls", 0) + 1
+        return (self.seed * 0x9E3779B97F4A7C15 + self._draws_calls) % 2 ** 64
+
+    def _sharded_draws(self, ctx, S, width, seed, stream, draw):
+        """predict.PredictiveDraws [S][width] of draw(ancestors, s_first, s_count) -> (y, anc, n_bad).  Several shards: one
+        host all-gather of the ranks' weight totals assigns every rank the slots of the comb (Philox stream `stream`) that
+        fall in its share (predict.shard_slots), each rank draws its own, one host all-gather assembles them."""
+        from .predict import PredictiveDraws, shard_slots
+        if self.comm.world_size == 1:
+            return PredictiveDraws(*draw(None, 0, None))
+        _, lw, _ = ctx.get_state(x=False)
+        s0, n, anc, offs = shard_slots(lw, S, seed, self.comm, stream=stream)
+        mine = np.zeros(S * width + S + 1)
+        if n:
+            y, _, nbad = draw(anc, s0, n)
+            mine[s0 * width:(s0 + n) * width] = y.reshape(-1)
+            mine[S * width + s0:S * width + s0 + n] = anc[s0:s0 + n] + offs[self.comm.rank]
+            mine[-1] = nbad
+        tot = np.asarray(self.comm.allgather(mine)).reshape(self.comm.world_size, -1).sum(0)
+        # (every slot has one owner; the others hold zeros there)
+        return PredictiveDraws(tot[:S * width].reshape(S, width), tot[S * width:S * width + S].astype(np.int64), int(tot[-1]))
+
     def pointwise(self):
         """Per-observation criteria (criteria.Pointwise: lppd, WAIC, IS-LOO, fitted values) of the final generation and its
         weights, after sample() / finalise(): computed from the resident particles, nothing is downloaded but the
         [1 + n][Q] partials.  Several shards: every rank computes its partials, ONE host all-gather moves them, every rank
         combines them in rank order."""
         from .criteria import combine_pointwise_partials
-        if self.lkernel == "asymptoticLKernel":
-            raise NotImplementedError("pointwise(): the asymptotic L-kernel's estimates pool generations; criteria over the "
-                                      "pooled generations are not implemented")
+        self._refuse_pooled("pointwise", "criteria")
         if not hasattr(self.target, "pointwise_partials"):
             self.target.pointwise(None)         # raises NotImplementedError naming the supported targets
         if hasattr(self.target, "_refuse_weighted"):
             self.target._refuse_weighted()      # (a GLMTarget fitted with weights: NotImplementedError)
-        if not self._finalised:
-            raise RuntimeError("pointwise(): run sample() (or step() K times and finalise()) first")
-        if self.phi[self.K] != 1.0:
-            raise RuntimeError(f"pointwise(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
-                               "target the posterior")
-        ctx = self.samples.ctx
-        ctx.call("smcn_synchronize")
-        part = ctx.pointwise_partials()
-        if self.comm.world_size > 1:
-            allp = np.asarray(self.comm.allgather(part.reshape(-1)))
-            return combine_pointwise_partials([p.reshape(part.shape) for p in allp])
-        return combine_pointwise_partials([part])
+        ctx = self._final_generation("pointwise")
+        return combine_pointwise_partials(self._gather_partials(ctx.pointwise_partials()))
 
     def loo(self):
         """Pareto-smoothed importance-sampling LOO (psis.PsisLoo: elpd_loo_i, pareto_k_i, psis_ess_i and `plain`, what
@@ -595,21 +642,12 @@ class SMCSampler:
         for the global mw and S, the ranks' candidates, the body partials), the fit on every rank; every rank returns the
         same object."""
         from .psis import loo_from_context
-        if self.lkernel == "asymptoticLKernel":
-            raise NotImplementedError("loo(): the asymptotic L-kernel's estimates pool generations; criteria over the "
-                                      "pooled generations are not implemented")
+        self._refuse_pooled("loo", "criteria")
         if not hasattr(self.target, "pointwise_partials"):
             self.target.loo(None)               # raises NotImplementedError naming the supported targets
         if hasattr(self.target, "_refuse_weighted"):
             self.target._refuse_weighted()
-        if not self._finalised:
-            raise RuntimeError("loo(): run sample() (or step() K times and finalise()) first")
-        if self.phi[self.K] != 1.0:
-            raise RuntimeError(f"loo(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
-                               "target the posterior")
-        ctx = self.samples.ctx
-        ctx.call("smcn_synchronize")
-        return loo_from_context(ctx, self.comm)
+        return loo_from_context(self._final_generation("loo"), self.comm)
 
     def summary(self, probs=(0.025, 0.25, 0.5, 0.75, 0.975), at=None):
         """Posterior summary (summary.PosteriorSummary: mean, sd, weighted quantiles at `probs`, and with `at` the mass at
@@ -618,27 +656,11 @@ class SMCSampler:
         [Dc][T] masses.  Several shards: the ranks' histograms are summed through one host all-gather per pass; every
         rank returns the same object.  A host-evaluated target's own constrain() runs on the host (as for the moments)."""
         from . import summary as sm
-        if self.lkernel == "asymptoticLKernel":
-            raise NotImplementedError("summary(): the asymptotic L-kernel's estimates pool generations; summaries over the "
-                                      "pooled generations are not implemented")
-        Dc = self.mean_estimate.shape[1]
-        probs, at = sm.check_probs(probs), sm.check_at(at, Dc)
-        if not self._finalised:
-            raise RuntimeError("summary(): run sample() (or step() K times and finalise()) first")
-        if self.phi[self.K] != 1.0:
-            raise RuntimeError(f"summary(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
-                               "target the posterior")
-        ctx, t = self.samples.ctx, self.target
-        ctx.call("smcn_synchronize")
-        if getattr(t, "host_evaluated", False) and callable(getattr(t.target, "constrain", None)):
-            x, lw, _ = ctx.get_state()
-            v = np.ascontiguousarray(t.constrain(x), dtype=np.float64)
-            q, cdf, _ = sm.device_summary(ctx, self.comm, probs, at, v=v, logw=lw)
-        else:
-            q, cdf, _ = sm.device_summary(ctx, self.comm, probs, at)
-        names = list(t.param_names())
-        if len(names) != Dc:
-            names = [f"x.{i + 1}" for i in range(Dc)]
+        self._refuse_pooled("summary", "summaries")
+        probs, at = sm.check_probs(probs), sm.check_at(at, self.mean_estimate.shape[1])
+        ctx = self._final_generation("summary")
+        kw, names = self._constrained_population(ctx)
+        q, cdf, _ = sm.device_summary(ctx, self.comm, probs, at, **kw)
         return sm.PosteriorSummary(names, self.mean_estimate[self.K].copy(), np.sqrt(self.variance_estimate[self.K]),
                                    probs, q, cdf, at, self.ess[self.K], self.N)
 
@@ -650,27 +672,11 @@ class SMCSampler:
         weights' headers and one of the partials; every rank returns the same object.  A host-evaluated target's own
         constrain() runs on the host (as for the moments)."""
         from . import covariance as cv
-        if self.lkernel == "asymptoticLKernel":
-            raise NotImplementedError("covariance(): the asymptotic L-kernel's estimates pool generations; covariances over "
-                                      "the pooled generations are not implemented")
-        if not self._finalised:
-            raise RuntimeError("covariance(): run sample() (or step() K times and finalise()) first")
-        if self.phi[self.K] != 1.0:
-            raise RuntimeError(f"covariance(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do "
-                               "not target the posterior")
-        Dc = self.mean_estimate.shape[1]
-        ctx, t = self.samples.ctx, self.target
+        self._refuse_pooled("covariance", "covariances")
+        ctx = self._final_generation("covariance")
         centre = np.ascontiguousarray(self.mean_estimate[self.K], dtype=np.float64)
-        ctx.call("smcn_synchronize")
-        if getattr(t, "host_evaluated", False) and callable(getattr(t.target, "constrain", None)):
-            x, lw, _ = ctx.get_state()
-            v = np.ascontiguousarray(t.constrain(x), dtype=np.float64)
-            mean, cov, corr, _, _ = cv.device_covariance(ctx, self.comm, centre=centre, v=v, logw=lw)
-        else:
-            mean, cov, corr, _, _ = cv.device_covariance(ctx, self.comm, centre=centre)
-        names = list(t.param_names())
-        if len(names) != Dc:
-            names = [f"x.{i + 1}" for i in range(Dc)]
+        kw, names = self._constrained_population(ctx)
+        mean, cov, corr, _, _ = cv.device_covariance(ctx, self.comm, centre=centre, **kw)
         return cv.PosteriorCovariance(names, mean, cov, corr, self.ess[self.K], self.N, centre=centre)
 
     def predict(self, X_new, y_new=None, groups_new=None, offset_new=None):
@@ -680,39 +686,24 @@ class SMCSampler:
         the [1 + m][Q] partials.  Several shards: every rank computes its partials, ONE host all-gather moves them, every
         rank combines them in rank order."""
         from .predict import combine_predict_partials
-        if self.lkernel == "asymptoticLKernel":
-            raise NotImplementedError("predict(): the asymptotic L-kernel's estimates pool generations; predictions over "
-                                      "the pooled generations are not implemented")
+        self._refuse_pooled("predict", "predictions")
         if not hasattr(self.target, "predict_partials"):
             raise NotImplementedError(f"{type(self.target).__name__}: held-out prediction is implemented for GLMTarget, "
                                       "HierarchicalGLM, CategoricalRegression and OrdinalRegression")
         block, has_y = self.target._predict_block(X_new, y_new, groups_new, offset_new=offset_new)
-        if not self._finalised:
-            raise RuntimeError("predict(): run sample() (or step() K times and finalise()) first")
-        if self.phi[self.K] != 1.0:
-            raise RuntimeError(f"predict(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
-                               "target the posterior")
+        ctx = self._final_generation("predict")
         kind, K = self.target._predict_kind()
-        ctx = self.samples.ctx
-        ctx.call("smcn_synchronize")
         ctx.predict_set_data(block, has_y)
-        part = ctx.predict_partials()
-        if self.comm.world_size > 1:
-            allp = np.asarray(self.comm.allgather(part.reshape(-1)))
-            return combine_predict_partials([p.reshape(part.shape) for p in allp], kind, K, has_y)
-        return combine_predict_partials([part], kind, K, has_y)
+        return combine_predict_partials(self._gather_partials(ctx.predict_partials()), kind, K, has_y)
 
     def predict_draws(self, X_new=None, n_draws=1000, seed=None, groups_new=None, offset_new=None):
         """Posterior predictive draws (predict.PredictiveDraws: n_draws replicated data sets at the rows X_new, each from
         one particle of the final generation chosen by systematic resampling of its weights), after sample() /
         finalise().  X_new=None: the training rows (for HierarchicalGLM with their groups, for a GLMTarget with offsets with
         their offsets; otherwise offset_new gives the new rows' offsets).  seed=None: derived from the
-        sampler's rng.  Several shards: one host all-gather of the ranks' weight totals assigns every rank the slots of
-        the comb that fall in its share, each rank draws its own, one host all-gather assembles [S][m]."""
-        from .predict import PredictiveDraws, shard_slots
-        if self.lkernel == "asymptoticLKernel":
-            raise NotImplementedError("predict_draws(): the asymptotic L-kernel's estimates pool generations; predictions "
-                                      "over the pooled generations are not implemented")
+        sampler's rng.  Several shards: _sharded_draws assembles [S][m]."""
+        from .predict import ANCESTOR_STREAM
+        self._refuse_pooled("predict_draws", "predictions")
         if not hasattr(self.target, "predict_draws"):
             raise NotImplementedError(f"{type(self.target).__name__}: posterior predictive draws are implemented for "
                                       "GLMTarget, HierarchicalGLM, CategoricalRegression and OrdinalRegression")
@@ -723,48 +714,11 @@ class SMCSampler:
             if offset_new is None:
                 offset_new = getattr(self.target, "offset", None)
         block, labels, S, _ = self.target._draws_args(X_new, n_draws, groups_new, None, None, offset_new)
-        if not self._finalised:
-            raise RuntimeError("predict_draws(): run sample() (or step() K times and finalise()) first")
-        if self.phi[self.K] != 1.0:
-            raise RuntimeError(f"predict_draws(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles "
-                               "do not target the posterior")
-        if seed is None:                    # (every rank holds the same rng / seed: the same value everywhere)
-            if self.rng is not None:
-                seed = int(self.rng.integers(0, 2 ** 63))
-            else:
-                self._draws_calls = getattr(self, "_draws_calls", 0) + 1
-                seed = (self.seed * 0x9E3779B97F4A7C15 + self._draws_calls) % 2 ** 64
-        ctx = self.samples.ctx
-        ctx.call("smcn_synchronize")
+        ctx = self._final_generation("predict_draws")
+        seed = self._draw_seed(seed)
         ctx.predict_set_data(block, False)
-        if self.comm.world_size == 1:
-            return PredictiveDraws(*ctx.predict_draws(S, seed, new_group=labels))
-        m = int(block[1])
-        _, lw, _ = ctx.get_state(x=False)
-        s0, n, anc, offs = shard_slots(lw, S, seed, self.comm)
-        mine = np.zeros(S * m + S + 1)
-        if n:
-            y, _, nbad = ctx.predict_draws(S, seed, ancestors=anc, new_group=labels, s_first=s0, s_count=n)
-            mine[s0 * m:(s0 + n) * m] = y.reshape(-1)
-            mine[S * m + s0:S * m + s0 + n] = anc[s0:s0 + n] + offs[self.comm.rank]
-            mine[-1] = nbad
-        allp = np.asarray(self.comm.allgather(mine)).reshape(self.comm.world_size, -1)
-        tot = allp.sum(0)           # (every slot has one owner; the others hold zeros there)
-        return PredictiveDraws(tot[:S * m].reshape(S, m), tot[S * m:S * m + S].astype(np.int64), int(tot[-1]))
-
-    def _forecast_guards(self, who):
-        if self.lkernel == "asymptoticLKernel":
-            raise NotImplementedError(f"{who}(): the asymptotic L-kernel's estimates pool generations; forecasts over the "
-                                      "pooled generations are not implemented")
-        if not hasattr(self.target, "forecast_partials"):
-            raise NotImplementedError(f"{type(self.target).__name__}: forecasts are implemented for ArmaModel")
-
-    def _forecast_ready(self, who):
-        if not self._finalised:
-            raise RuntimeError(f"{who}(): run sample() (or step() K times and finalise()) first")
-        if self.phi[self.K] != 1.0:
-            raise RuntimeError(f"{who}(): the final temperature is phi = {self.phi[self.K]}, not 1: the particles do not "
-                               "target the posterior")
+        return self._sharded_draws(ctx, S, int(block[1]), seed, ANCESTOR_STREAM, lambda anc, s0, n: ctx.predict_draws(
+            S, seed, ancestors=anc, new_group=labels, s_first=s0, s_count=n))
 
     def forecast(self, horizon, y_future=None, at=None):
         """Posterior predictive summaries of y_{T+1..T+horizon} of an ArmaModel (forecast.Forecast: mean, var, sd; with
@@ -773,53 +727,30 @@ class SMCSampler:
         particles, nothing is downloaded but the [1 + H][Q] partials.  Several shards: every rank computes its partials,
         ONE host all-gather moves them, every rank combines them in rank order."""
         from .forecast import combine_forecast_partials
-        self._forecast_guards("forecast")
+        self._refuse_pooled("forecast", "forecasts")
+        if not hasattr(self.target, "forecast_partials"):
+            raise NotImplementedError(f"{type(self.target).__name__}: forecasts are implemented for ArmaModel")
         H, yf, a = self.target._forecast_args("forecast", horizon, y_future, at)
-        self._forecast_ready("forecast")
-        Tn = 0 if a is None else a.shape[1]
-        ctx = self.samples.ctx
-        ctx.call("smcn_synchronize")
+        ctx = self._final_generation("forecast")
         ctx.forecast_set(H, yf, a)
-        part = ctx.forecast_partials()
-        if self.comm.world_size > 1:
-            allp = np.asarray(self.comm.allgather(part.reshape(-1)))
-            return combine_forecast_partials([p.reshape(part.shape) for p in allp], Tn, yf is not None, a)
-        return combine_forecast_partials([part], Tn, yf is not None, a)
+        return combine_forecast_partials(self._gather_partials(ctx.forecast_partials()), 0 if a is None else a.shape[1],
+                                         yf is not None, a)
 
     def forecast_draws(self, horizon, n_draws=1000, seed=None):
         """Simulated paths y_{T+1..T+horizon} of an ArmaModel (predict.PredictiveDraws: y [n_draws][horizon], each path
         from one particle of the final generation chosen by systematic resampling of its weights), after sample() /
-        finalise().  seed=None: derived from the sampler's rng.  Several shards: one host all-gather of the ranks' weight
-        totals assigns every rank the slots of the comb that fall in its share, each rank simulates its own, one host
-        all-gather assembles [S][H]."""
+        finalise().  seed=None: derived from the sampler's rng.  Several shards: _sharded_draws assembles [S][H]."""
         from .forecast import ANCESTOR_STREAM, check_draws, check_horizon
-        from .predict import PredictiveDraws, shard_slots
-        self._forecast_guards("forecast_draws")
+        self._refuse_pooled("forecast_draws", "forecasts")
+        if not hasattr(self.target, "forecast_partials"):
+            raise NotImplementedError(f"{type(self.target).__name__}: forecasts are implemented for ArmaModel")
         H = check_horizon("forecast_draws", horizon)
         S, _ = check_draws("forecast_draws", n_draws, None, None)
-        self._forecast_ready("forecast_draws")
-        if seed is None:                    # (every rank holds the same rng / seed: the same value everywhere)
-            if self.rng is not None:
-                seed = int(self.rng.integers(0, 2 ** 63))
-            else:
-                self._draws_calls = getattr(self, "_draws_calls", 0) + 1
-                seed = (self.seed * 0x9E3779B97F4A7C15 + self._draws_calls) % 2 ** 64
-        ctx = self.samples.ctx
-        ctx.call("smcn_synchronize")
+        ctx = self._final_generation("forecast_draws")
+        seed = self._draw_seed(seed)
         ctx.forecast_set(H)
-        if self.comm.world_size == 1:
-            return PredictiveDraws(*ctx.forecast_draws(S, seed))
-        _, lw, _ = ctx.get_state(x=False)
-        s0, n, anc, offs = shard_slots(lw, S, seed, self.comm, stream=ANCESTOR_STREAM)
-        mine = np.zeros(S * H + S + 1)
-        if n:
-            y, _, nbad = ctx.forecast_draws(S, seed, ancestors=anc, s_first=s0, s_count=n)
-            mine[s0 * H:(s0 + n) * H] = y.reshape(-1)
-            mine[S * H + s0:S * H + s0 + n] = anc[s0:s0 + n] + offs[self.comm.rank]
-            mine[-1] = nbad
-        allp = np.asarray(self.comm.allgather(mine)).reshape(self.comm.world_size, -1)
-        tot = allp.sum(0)           # (every slot has one owner; the others hold zeros there)
-        return PredictiveDraws(tot[:S * H].reshape(S, H), tot[S * H:S * H + S].astype(np.int64), int(tot[-1]))
+        return self._sharded_draws(ctx, S, H, seed, ANCESTOR_STREAM, lambda anc, s0, n: ctx.forecast_draws(
+            S, seed, ancestors=anc, s_first=s0, s_count=n))
 
     def sample(self, show_progress=True):
         start_time = time()

@@ -371,3 +371,10 @@ def test_two_shards():
     assert (~same).sum() <= amb.sum() + 2
     np.testing.assert_array_equal(d0.y[same], od.y[same])
     assert d0.n_bad == int(np.isnan(d0.y).sum())
+
+
+def test_draws_bit_for_bit_with_the_parent_of_the_draw_plan():
+    """tests/_draws_golden.py: y (NaNs by position), ancestors and n_bad of Context.forecast_draws as recorded on an
+    MI355X before smcn_predict_draws and smcn_forecast_draws shared their draw plan."""
+    import _draws_golden as g
+    g.assert_same_as_parent(g.forecast_results(), "forecast/")

@@ -363,3 +363,10 @@ def test_two_shards():
         assert (~same).sum() <= namb + max(2, 1e-4 * S)
         np.testing.assert_array_equal(out[0][0].y[same], one.y[same])
         assert out[0][0].n_bad == int(np.isnan(out[0][0].y).sum())
+
+
+def test_bit_for_bit_with_the_parent_of_the_draw_plan():
+    """tests/_draws_golden.py: y (NaNs by position), ancestors and n_bad of Context.predict_draws as recorded on an
+    MI355X before smcn_predict_draws and smcn_forecast_draws shared their draw plan."""
+    import _draws_golden as g
+    g.assert_same_as_parent(g.predict_results(), "predict/")
