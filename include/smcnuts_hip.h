@@ -172,6 +172,12 @@ int smcn_set_resample_scheme(smcn_ctx* ctx, int scheme);
  * run wide depends on the launch's schedule (iterations per launch, wave mates).  1 (default) = on; 0 = every
  * evaluation by one lane (bit-identical results whatever the schedule: what the fused-vs-stepwise tests pin). */
 int smcn_set_wide_eval(smcn_ctx* ctx, int on);
+/* The lane kernel's tree bookkeeping.  A tree takes an even number of loop iterations unless a leaf diverges, so in every
+ * other iteration all leaves of a wavefront are even ones: they park at level 0 and nothing else happens.  1 (default):
+ * such an iteration, found by one ballot, passes over the merge, top-level and tree-end code in one branch, and an
+ * iteration in which no lane starts a tree or a doubling over the start code; 0: every iteration takes the generic code.
+ * The results are the same bits either way: the schedule, the draws and the arithmetic do not change. */
+int smcn_set_phase_paths(smcn_ctx* ctx, int on);
 /* The lane kernel's schedule: at most `waves` wavefronts are launched (0 = default: one per SIMD, all the chip holds of this
  * kernel; < 0: no cap, one per 64 particles).  With fewer lanes than particles every wavefront owns a contiguous run of
  * particles (N / waves of them) and its 64 lanes work through it, so a population that is no multiple of 65 536 per GPU
@@ -811,7 +817,8 @@ int smcn_forecast_last_ms(const smcn_ctx* ctx, double ms[2]);
 
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
- * and of the longest one); zeros in a normal build. */
+ * and of the longest one); zeros in a normal build.  With -DSMCN_PROFILE_PHASE as well the lane kernel's slots are by the
+ * iteration's number mod 4 instead (csrc/smcn_nuts.hpp; tools/prof_sections.py with PROF_PHASE=1 prints them). */
 int smcn_debug_profile(smcn_ctx* ctx, uint64_t out[16], int reset);
 
 #ifdef __cplusplus

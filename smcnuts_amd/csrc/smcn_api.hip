@@ -565,6 +565,15 @@ int smcn_set_wide_eval(smcn_ctx* c, int on) {
     c->wide_eval = on;
     return 0;
 }
+// nuts3_kernel: 1 (default) = an iteration in which every leaf of a wavefront only parks at level 0, and one in which no
+// lane starts a tree or a doubling, pass over the code they do not need in one scalar branch; 0 = every iteration takes
+// the generic code.  Same bits either way (tests/test_gpu_phase_paths.py).
+int smcn_set_phase_paths(smcn_ctx* c, int on) {
+    CHECK_CTX(c);
+    if (on != 0 && on != 1) FAIL(c, "smcn_set_phase_paths: 0 or 1");
+    c->phase_paths = on;
+    return 0;
+}
 // pipelined fused blocks: what runs between the NUTS launch and the host's wait.  1 (default): one streaming kernel and
 // one tail kernel (smcn_block_post.hpp); 0: the separate launches they replace -- same bits, kept as the tests' reference.
 int smcn_set_block_post(smcn_ctx* c, int mode) {
@@ -1546,6 +1555,7 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
         a.B = B;
         a.logw0 = (fuse_reweight && B > 1) ? c->logw : nullptr;   // compact records for the transitions before the last
         a.wide = (c->wide_eval ? 1 : 0) | 2;    // the helper draws do not touch the bits: on in both modes
+        a.phase_paths = c->phase_paths;
         const bool queued = blocks * kN3Block < N;     // fewer lanes than particles: every wavefront works through a run of them
         a.seg_len = 0;
         a.seg_tail = 0;

@@ -175,6 +175,7 @@ struct smcn_ctx {
     Buf<double> tb_state, tb_part, tb_local, tb_gath;   // device-side ESS bisection
     int tb_world = 0, tb_blocks = 0;
     int wide_eval = 1;         // nuts3_kernel: lane groups evaluate a wavefront's last stragglers (smcn_set_wide_eval)
+    int phase_paths = 1;       // nuts3_kernel: one branch over the bookkeeping no lane needs in an iteration (smcn_set_phase_paths)
     int64_t lane_grid_cap = 0; // nuts3_kernel: wavefronts launched at most (0: one per SIMD; < 0: no cap, a wavefront per 64 particles)
     int lane_segments = 0;     // nuts3_kernel, fewer lanes than particles: segments a block is worked off in (0: auto, 1: whole blocks)
     Buf<unsigned long long> handover;  // [N][segments - 1][VH + 1 pairs] (lane queue: x', running log-weight between segments)

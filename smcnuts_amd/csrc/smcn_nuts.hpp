@@ -96,14 +96,34 @@ __device__ __forceinline__ unsigned long long prof_stamp() {
 // when lane 0 is in it -- the time of a region it skips lands on the next stamp it does execute)
 #define PROF_DECL                                                                                         \
     unsigned long long pt_ = prof_stamp(), pacc_[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};        \
-    bool prof_on_ = true
+    bool prof_on_ = true;                                                                                 \
+    unsigned int prof_ph_ = 0u
 #define PROF_ON(c) prof_on_ = (c)   /* count the following stamps only while c holds (wave-uniform) */
+#ifdef SMCN_PROFILE_PHASE
+// (-DSMCN_PROFILE -DSMCN_PROFILE_PHASE, nuts3_kernel: the slots are re-used -- 0..3 the cycles of everything but the draws,
+// the leapfrog and the evaluation (sections 0..2), split by the iteration's number mod 4 (prof_ph_, set at the loop's top);
+// 12 those three sections; 4..7 / 8..11 are counts the kernel adds itself: iterations per residue, and those of them in
+// which every live lane started its tree in an iteration that was a multiple of 4)
+#define PROF(sec)                                                               \
+    do {                                                                        \
+        const unsigned long long n_ = prof_stamp(), d_ = prof_on_ ? n_ - pt_ : 0ull; \
+        if ((sec) <= 2) pacc_[12] += d_;                                        \
+        else {                                                                  \
+            pacc_[0] += prof_ph_ == 0u ? d_ : 0ull;                             \
+            pacc_[1] += prof_ph_ == 1u ? d_ : 0ull;                             \
+            pacc_[2] += prof_ph_ == 2u ? d_ : 0ull;                             \
+            pacc_[3] += prof_ph_ == 3u ? d_ : 0ull;                             \
+        }                                                                       \
+        pt_ = n_;                                                               \
+    } while (0)
+#else
 #define PROF(sec)                                   \
     do {                                            \
         const unsigned long long n_ = prof_stamp(); \
         pacc_[sec] += prof_on_ ? n_ - pt_ : 0ull;   \
         pt_ = n_;                                   \
     } while (0)
+#endif
 #define PROF_FLUSH(a)                                                               \
     do {                                                                            \
         if ((threadIdx.x & 63u) == 0) {                                             \

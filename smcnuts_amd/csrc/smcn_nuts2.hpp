@@ -42,6 +42,8 @@ struct Nuts2Args {
     unsigned long long* handover = nullptr;  // [N][segments - 1][VH + 1] 16-byte pairs
     int wide = 3;                    // nuts3: bit 0 = lane groups evaluate a wavefront's last stragglers (smcn_set_wide_eval:
                                      // re-associated sums); bit 1 = idle lanes draw the stragglers' uniforms (always on: same bits)
+    int phase_paths = 1;             // nuts3: an iteration in which every leaf of the wavefront only parks at level 0 passes over
+                                     // the merge, top-level and tree-end code in one branch (smcn_set_phase_paths: same bits)
 };
 
 // prep: momentum draw (samples.py:155) + slice exponential (nuts.py:69) + packing of the input records, which are

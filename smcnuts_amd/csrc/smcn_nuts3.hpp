@@ -870,6 +870,9 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
 #ifdef SMCN_PROFILE
     unsigned long long iters = 0;
 #endif
+#ifdef SMCN_PROFILE_PHASE
+    unsigned int prof_t0 = 0u;       // the iteration in which the lane's current tree began
+#endif
     // the output record of the transition a lane has just ended (j doublings, accepted sample rx / rr / rl)
     auto emit_record = [&](bool last, uint32_t qdone, bool ovdone, int nldone) __attribute__((always_inline)) {
         const gptr2 orec = (compact && last) ? out2 + p : out_cur;
@@ -926,6 +929,17 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
 #endif
 #ifdef SMCN_PROFILE
         if (prof_on_) ++iters;
+#endif
+#ifdef SMCN_PROFILE_PHASE   // (iterations by their number mod 4, and those in which every live lane's tree began at a multiple of 4)
+        prof_ph_ = it & 3u;
+        if (phase == INIT) prof_t0 = it;
+        {
+            const unsigned long long inph = __ballot(act && (prof_t0 & 3u) != 0u) == 0ull ? 1ull : 0ull;   // (wave-uniform)
+            pacc_[4] += prof_ph_ == 0u ? 1ull : 0ull; pacc_[8] += prof_ph_ == 0u ? inph : 0ull;
+            pacc_[5] += prof_ph_ == 1u ? 1ull : 0ull; pacc_[9] += prof_ph_ == 1u ? inph : 0ull;
+            pacc_[6] += prof_ph_ == 2u ? 1ull : 0ull; pacc_[10] += prof_ph_ == 2u ? inph : 0ull;
+            pacc_[7] += prof_ph_ == 3u ? 1ull : 0ull; pacc_[11] += prof_ph_ == 3u ? inph : 0ull;
+        }
 #endif
         // ---- uniforms: at least min(draws this leaf can consume, 7) in the ring -----------------
         if constexpr (!TAPE) {
@@ -1035,6 +1049,9 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
         bool start_doubling = false;
         bool tree_end = false;             // (QUEUE: the lane's tree ended in this iteration)
         const bool init = phase == INIT;      // (a lane that ends a tree below turns INIT for the NEXT iteration)
+#ifdef SMCN_PROFILE_PHASE
+        bool prof_park0 = false;
+#endif
         if (phase == LEAF) {
             // ---- second half kick (nuts.py:173), leaf tests (:123-125) ----------------------------
             double kin = 0.0;
@@ -1104,96 +1121,112 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
                 return ssub ? 1 : (m == j ? 2 : ((((i >> m) & 1) == 0) ? 3 : 0));
             };
             how = ends();
-            if (how == 0) {          // level 0 (registers)
-                double u;
-                if constexpr (TAPE) u = ring_draw(); else { u = up0; ++q; }
-                merge(0, u, n0, f1x, f1r);
-                m = 1;
-                how = ends();
-            }
-            if (how == 0) {          // level 1 (registers)
-                double u;
-                if constexpr (TAPE) u = ring_draw(); else { u = up1; ++q; }
-                merge(1, u, n1, f2x, f2r);
-                m = 2;
-                how = ends();
-            }
-            while (how == 0) {       // levels >= 2 (LDS, then the overflow area)
-                double fx[D], fr[D];
-                const int nfirst = (int)*nst_ptr(m);
-                with_first(m + 1, [&](auto fp) __attribute__((always_inline)) { ld_vec(fp, fx); ld_vec(fp + VH * 64, fr); });
-                const double u = ring_draw();     // :142, always
-                merge(m, u, nfirst, fx, fr);
-                ++m;
-                how = ends();
-            }
-            PROF(8);
-            bool done = false, stop = false, acc = false;
-            if (how == 1) {
-                // unwinding: every ancestor whose SECOND half stopped still draws (:142)
-                q += (uint32_t)__popc((unsigned)(i >> m) & ((1u << (j - m)) - 1u));
-                done = true; stop = true;
-            } else if (how == 2) {
-                // top level: accept with prob min(1, n'/n) (:99), U-turn on the outer edges (:105)
-                double u;
-                if (TAPE || !pre_ok) u = ring_draw(); else { u = utop; ++q; }
-                acc = nsub >= n || fma(u, (double)n, -(double)nsub) < 0.0;
-                double A = 0.0, B = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const double d = x[k] - ex[k];
-                    A = fma(d, er[k], A);
-                    B = fma(d, r[k], B);
-                }
-                stop = is_uturn(A, B, dir);
-                done = true;
-            }
-            PROF(9);
-            {   // the candidate goes to the parked slot of level m (3) or becomes the accepted sample (2, accepted)
-                double cx[D], cr[D];
-                d2 cl;
-                const bool park = how == 3;
-                cand_value(park || acc, cx, cr, cl);
-                if (acc) { movv(rx, cx); movv(rr, cr); movd2(rl, cl); }
-                if (park) {
-                    if (m == 0) { movv(c0x, cx); movv(c0r, cr); movd2(c0l, cl); }
-                    else if (m == 1) { movv(c1x, cx); movv(c1r, cr); movd2(c1l, cl); }
-                    else {
-                        with_cand(m, [&](auto crec) __attribute__((always_inline)) { st_vec(crec, cx); st_vec(crec + VH * 64, cr); crec[2 * VH * 64] = cl; });
-                        *nst_ptr(m) = (unsigned short)nsub;
-                    }
-                }
-                n0 = (park && m == 0) ? nsub : n0;
-                n1 = (park && m == 1) ? nsub : n1;
-            }
-            PROF(4);
-            if (!done) {
+            // A tree takes an even number of loop iterations (its start, then a U-turn or the depth cap at a leaf with an odd
+            // index; only a leaf that diverges ends one elsewhere), and every lane starts in iteration 0: in every other
+            // iteration ALL leaves of the wavefront are even ones, which park at level 0 and do nothing else -- no merge,
+            // no draw, no top level, no tree end.  One ballot says so (evaluated, not remembered: exact whatever brought
+            // the lanes there), and one scalar branch then passes over the ~25 regions below, each of which would cost its
+            // mask arithmetic and a taken branch (smcn_set_phase_paths(0): every iteration takes them).
+            const bool all_park0 = a.phase_paths != 0 && __ballot(how != 3) == 0ull;
+#ifdef SMCN_PROFILE_PHASE
+            prof_park0 = all_park0;
+#endif
+            if (all_park0) {         // what the code below does for how == 3, m == 0: the leaf is its own sub-tree's candidate
+                movv(c0x, x); movv(c0r, r); movd2(c0l, leafl);
+                n0 = nsub;
                 ++i;
             } else {
-                n += nsub;                   // :103  (unused after a stop)
-                ++j;
-                if (stop || j > a.max_depth) {   // :89,109 -> emit the output record, start the next transition
-                    if constexpr (QUEUE) {
-                        tree_end = true;         // (handled below, where every lane of the wavefront is, with the hand-overs)
-                    } else {
-                        const bool more = b + 1 < a.B;
-                        // the next transition's record first: its loads are a whole tree old, so this wait
-                        // does not land on the stores below
-                        const int bdone = b;
-                        const uint32_t qdone = q;
-                        const bool ovdone = overflow;
-                        const int nldone = nleap;
-                        if (more) movv(x, rx);        // continue from the sample just drawn
-                        phase = DONE;
-                        take_record(more);
-                        b = more ? bdone + 1 : b;
-                        PROF(10);
-                        emit_record(!more, qdone, ovdone, nldone);
-                        PROF(13);
-                        if (more && bdone + 2 < a.B) request();
+                if (how == 0) {          // level 0 (registers)
+                    double u;
+                    if constexpr (TAPE) u = ring_draw(); else { u = up0; ++q; }
+                    merge(0, u, n0, f1x, f1r);
+                    m = 1;
+                    how = ends();
+                }
+                if (how == 0) {          // level 1 (registers)
+                    double u;
+                    if constexpr (TAPE) u = ring_draw(); else { u = up1; ++q; }
+                    merge(1, u, n1, f2x, f2r);
+                    m = 2;
+                    how = ends();
+                }
+                while (how == 0) {       // levels >= 2 (LDS, then the overflow area)
+                    double fx[D], fr[D];
+                    const int nfirst = (int)*nst_ptr(m);
+                    with_first(m + 1, [&](auto fp) __attribute__((always_inline)) { ld_vec(fp, fx); ld_vec(fp + VH * 64, fr); });
+                    const double u = ring_draw();     // :142, always
+                    merge(m, u, nfirst, fx, fr);
+                    ++m;
+                    how = ends();
+                }
+                PROF(8);
+                bool done = false, stop = false, acc = false;
+                if (how == 1) {
+                    // unwinding: every ancestor whose SECOND half stopped still draws (:142)
+                    q += (uint32_t)__popc((unsigned)(i >> m) & ((1u << (j - m)) - 1u));
+                    done = true; stop = true;
+                } else if (how == 2) {
+                    // top level: accept with prob min(1, n'/n) (:99), U-turn on the outer edges (:105)
+                    double u;
+                    if (TAPE || !pre_ok) u = ring_draw(); else { u = utop; ++q; }
+                    acc = nsub >= n || fma(u, (double)n, -(double)nsub) < 0.0;
+                    double A = 0.0, B = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const double d = x[k] - ex[k];
+                        A = fma(d, er[k], A);
+                        B = fma(d, r[k], B);
                     }
+                    stop = is_uturn(A, B, dir);
+                    done = true;
+                }
+                PROF(9);
+                {   // the candidate goes to the parked slot of level m (3) or becomes the accepted sample (2, accepted)
+                    double cx[D], cr[D];
+                    d2 cl;
+                    const bool park = how == 3;
+                    cand_value(park || acc, cx, cr, cl);
+                    if (acc) { movv(rx, cx); movv(rr, cr); movd2(rl, cl); }
+                    if (park) {
+                        if (m == 0) { movv(c0x, cx); movv(c0r, cr); movd2(c0l, cl); }
+                        else if (m == 1) { movv(c1x, cx); movv(c1r, cr); movd2(c1l, cl); }
+                        else {
+                            with_cand(m, [&](auto crec) __attribute__((always_inline)) { st_vec(crec, cx); st_vec(crec + VH * 64, cr); crec[2 * VH * 64] = cl; });
+                            *nst_ptr(m) = (unsigned short)nsub;
+                        }
+                    }
+                    n0 = (park && m == 0) ? nsub : n0;
+                    n1 = (park && m == 1) ? nsub : n1;
+                }
+                PROF(4);
+                if (!done) {
+                    ++i;
                 } else {
-                    start_doubling = true;
+                    n += nsub;                   // :103  (unused after a stop)
+                    ++j;
+                    if (stop || j > a.max_depth) {   // :89,109 -> emit the output record, start the next transition
+                        if constexpr (QUEUE) {
+                            tree_end = true;         // (handled below, where every lane of the wavefront is, with the hand-overs)
+                        } else {
+                            const bool more = b + 1 < a.B;
+                            // the next transition's record first: its loads are a whole tree old, so this wait
+                            // does not land on the stores below
+                            const int bdone = b;
+                            const uint32_t qdone = q;
+                            const bool ovdone = overflow;
+                            const int nldone = nleap;
+                            if (more) movv(x, rx);        // continue from the sample just drawn
+                            phase = DONE;
+                            take_record(more);
+                            b = more ? bdone + 1 : b;
+                            PROF(10);
+                            emit_record(!more, qdone, ovdone, nldone);
+                            PROF(13);
+                            if (more && bdone + 2 < a.B) request();
+                        }
+                    } else {
+                        start_doubling = true;
+                    }
                 }
             }
         }
@@ -1316,45 +1349,52 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
             }
         }
         PROF(11);
-        {
-            // ---- nuts.py:66-87 ----------------------------------------------------------------
-            double kin = 0.0;
+#ifdef SMCN_PROFILE_PHASE
+        pacc_[13] += __ballot(prof_park0) != 0ull ? 1ull : 0ull;   // iterations in which every leaf parked at level 0
+#endif
+        // (no lane starts a tree or a doubling -- most iterations in which every leaf parks at level 0 --: one scalar branch
+        //  over both blocks, whose moves and selects are all under init or start_doubling)
+        if (a.phase_paths == 0 || __ballot(init || start_doubling) != 0ull) {
+            {
+                // ---- nuts.py:66-87 ----------------------------------------------------------------
+                double kin = 0.0;
 #pragma unroll
-            for (int k = 0; k < D; ++k) kin = fma(r[k], r[k], kin);
-            if (init) {
-                mov64(logu, (lp - 0.5 * kin) - logu);          // H0 - Exp(1)
-                mov64(k0, kin);                                // |r0|^2: q = N(r0; 0, I) of the weight update
-                mov64(lpri0, lpri); mov64(llik0, llik);        // the record's start density
-                movv(rx, x); movv(rr, r);
-                d2 il;
-                il.x = lpri; il.y = llik;
-                movd2(rl, il);
+                for (int k = 0; k < D; ++k) kin = fma(r[k], r[k], kin);
+                if (init) {
+                    mov64(logu, (lp - 0.5 * kin) - logu);          // H0 - Exp(1)
+                    mov64(k0, kin);                                // |r0|^2: q = N(r0; 0, I) of the weight update
+                    mov64(lpri0, lpri); mov64(llik0, llik);        // the record's start density
+                    movv(rx, x); movv(rr, r);
+                    d2 il;
+                    il.x = lpri; il.y = llik;
+                    movd2(rl, il);
+                }
+                j = init ? 0 : j; n = init ? 1 : n;
+                dir = init ? 0 : dir;                 // both edges are (x0, r0, g0)
+                start_doubling = start_doubling || init;
+                phase = init ? (int)LEAF : phase;
             }
-            j = init ? 0 : j; n = init ? 1 : n;
-            dir = init ? 0 : dir;                 // both edges are (x0, r0, g0)
-            start_doubling = start_doubling || init;
-            phase = init ? (int)LEAF : phase;
-        }
-        PROF(5);
-        {
-            // ---- nuts.py:91: direction; the moving state becomes that edge --------------------------
-            int nd = dir;
-            if (start_doubling) {
-                double u;
-                if (TAPE || !pre_ok) u = ring_draw(); else { u = udir; ++q; }
-                nd = (u < 0.5) ? 1 : -1;
-            }
-            const bool first = start_doubling && dir == 0;              // both edges are the start state
-            const bool swap = start_doubling && dir != 0 && nd != dir;  // the moving edge and the parked one trade places
-            if (first || swap) {            // the parked edge takes the moving state; on a swap the moving state takes the parked edge
-                double tx[D], tr[D], tg[D];
+            PROF(5);
+            {
+                // ---- nuts.py:91: direction; the moving state becomes that edge --------------------------
+                int nd = dir;
+                if (start_doubling) {
+                    double u;
+                    if (TAPE || !pre_ok) u = ring_draw(); else { u = udir; ++q; }
+                    nd = (u < 0.5) ? 1 : -1;
+                }
+                const bool first = start_doubling && dir == 0;              // both edges are the start state
+                const bool swap = start_doubling && dir != 0 && nd != dir;  // the moving edge and the parked one trade places
+                if (first || swap) {            // the parked edge takes the moving state; on a swap the moving state takes the parked edge
+                    double tx[D], tr[D], tg[D];
 #pragma unroll
-                for (int k = 0; k < D; ++k) { tx[k] = ex[k]; tr[k] = er[k]; tg[k] = eg[k]; }
-                movv(ex, x); movv(er, r); movv(eg, g);
-                if (swap) { movv(x, tx); movv(r, tr); movv(g, tg); }
+                    for (int k = 0; k < D; ++k) { tx[k] = ex[k]; tr[k] = er[k]; tg[k] = eg[k]; }
+                    movv(ex, x); movv(er, r); movv(eg, g);
+                    if (swap) { movv(x, tx); movv(r, tr); movv(g, tg); }
+                }
+                dir = nd;
+                i = start_doubling ? 0 : i;
             }
-            dir = nd;
-            i = start_doubling ? 0 : i;
         }
         PROF(6);
         if constexpr (!QUEUE) {

@@ -27,6 +27,17 @@ names = ["refill", "leapfrog1", "eval", "leaf tests/first", "park/accept (after 
          "loop-top", "merge loop", "unwind/top-level", "tree end: take record", "tree end: prefetch + rejoin (after 13)", "tree end: x' stores", "tree end: other stores"]
 leaps = smc.leapfrogs[W:].sum()
 print(f"nuts launches {int(tm[1])}, {tm[0]:.3f} ms total; leapfrogs {leaps}; {leaps / tm[0] / 1e6:.3f} G leapfrog/s in the kernel")
+if os.environ.get("PROF_PHASE"):   # a -DSMCN_PROFILE -DSMCN_PROFILE_PHASE build: the slots are by iteration number mod 4
+    book, cnt, inph = v[0:4], v[4:8], v[8:12]
+    print(f"wave-iterations: total {v[14]:.0f}, longest wave {v[15]:.0f}; cycles per wave-iteration {(book.sum() + v[12]) / v[14]:.0f}, "
+          f"of them draws + leapfrog + evaluation {v[12] / v[14]:.0f}")
+    print(f"every live lane's tree began at a multiple of 4: {inph.sum() / cnt.sum() * 100:.2f}% of the wave-iterations")
+    print(f"every leaf of the wavefront parks at level 0 (one branch over the rest of the bookkeeping): {v[13] / cnt.sum() * 100:.2f}% "
+          f"of the wave-iterations (0 in a build without that path, or with smcn_set_phase_paths(0))")
+    for k in range(4):
+        print(f"  it mod 4 = {k}: {cnt[k]:12.0f} wave-iterations, in phase {inph[k] / cnt[k] * 100:6.2f}%, "
+              f"bookkeeping {book[k] / cnt[k]:7.0f} cycles per wave-iteration")
+    sys.exit(0)
 tot = v[:14].sum()
 for n, x in zip(names, v[:14]):
     print(f"  {n:18s} {x/tot*100:6.2f}%   {x:.3e}")
