@@ -178,6 +178,18 @@ int smcn_set_wide_eval(smcn_ctx* ctx, int on);
  * iteration in which no lane starts a tree or a doubling over the start code; 0: every iteration takes the generic code.
  * The results are the same bits either way: the schedule, the draws and the arithmetic do not change. */
 int smcn_set_phase_paths(smcn_ctx* ctx, int on);
+/* The lane kernel with a lane per particle: when a lane's trees start.  A tree takes 2^depth loop iterations, so the lanes of
+ * a wavefront, which all start in iteration 0, reach the leaves with many merges in the same iterations -- until one tree
+ * stops early (a sub-tree U-turn, a depth-1 tree, a divergent leaf) and its lane is out of step for the rest of the
+ * launch.  n = 1, 2, 4 (default) or 8: a lane whose tree ended starts the next one in the first iteration whose number is
+ * a multiple of n, sitting out up to n - 1 iterations; 1 = in the very next iteration.  Only when a tree runs changes:
+ * with smcn_set_wide_eval(0) the results are the same bits for every n.  (Fewer lanes than particles, smcn_set_lane_grid:
+ * the lane queue has its own rule of this kind and ignores this setting.) */
+int smcn_set_tree_align(smcn_ctx* ctx, int n);
+/* Loop iterations each wavefront of the last lane-kernel launch ran, the first n wavefronts' (n at most the launch's number
+ * of wavefronts: a wavefront per 64 particles unless smcn_set_lane_grid caps them).  A lane per particle: the largest, over
+ * the wavefront's lanes, of the iteration its last tree ended in, plus one -- what smcn_set_tree_align changes. */
+int smcn_get_wave_iterations(smcn_ctx* ctx, uint32_t* out, int64_t n);
 /* The lane kernel's schedule: at most `waves` wavefronts are launched (0 = default: one per SIMD, all the chip holds of this
  * kernel; < 0: no cap, one per 64 particles).  With fewer lanes than particles every wavefront owns a contiguous run of
  * particles (N / waves of them) and its 64 lanes work through it, so a population that is no multiple of 65 536 per GPU
@@ -818,7 +830,9 @@ int smcn_forecast_last_ms(const smcn_ctx* ctx, double ms[2]);
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build.  With -DSMCN_PROFILE_PHASE as well the lane kernel's slots are by the
- * iteration's number mod 4 instead (csrc/smcn_nuts.hpp; tools/prof_sections.py with PROF_PHASE=1 prints them). */
+ * iteration's number mod 4 instead (csrc/smcn_nuts.hpp; tools/prof_sections.py with PROF_PHASE=1 prints them).
+ * `reset`: bit 0 clears the sums after the read; bit 1 reads the second page of 16 slots (the phase build's cycles of the
+ * in-phase iterations) instead of the first. */
 int smcn_debug_profile(smcn_ctx* ctx, uint64_t out[16], int reset);
 
 #ifdef __cplusplus

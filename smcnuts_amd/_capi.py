@@ -93,6 +93,8 @@ SIGNATURES = {
     "smcn_set_resample_scheme": ([_ctx, C.c_int], C.c_int),
     "smcn_set_wide_eval": ([_ctx, C.c_int], C.c_int),
     "smcn_set_phase_paths": ([_ctx, C.c_int], C.c_int),
+    "smcn_set_tree_align": ([_ctx, C.c_int], C.c_int),
+    "smcn_get_wave_iterations": ([_ctx, C.POINTER(C.c_uint32), C.c_int64], C.c_int),
     "smcn_set_lane_grid": ([_ctx, C.c_int64], C.c_int),
     "smcn_set_lane_segments": ([_ctx, C.c_int], C.c_int),
     "smcn_set_host_target": ([_ctx, HOST_TARGET_FN, C.c_void_p], C.c_int),

@@ -475,7 +475,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     A_(lpri0, N); A_(llik0, N); A_(lpri1, N); A_(llik1, N); A_(Lg, N); A_(qv, N);
     A_(scan_local, N); A_(ttot, nt + 1); A_(toff, nt + 2);
     A_(part, (int64_t)kMaxPart * (4 * c->D * c->D + 2 * c->D + 8)); A_(scal, 4 * c->D * c->D + 2 * c->D + 64);
-    A_(stage, ND); A_(nleap, N); A_(depth, N); A_(ndraws, N); A_(flags, N); A_(idx, N); A_(queue, 16); A_(prof, 16);
+    A_(stage, ND); A_(nleap, N); A_(depth, N); A_(ndraws, N); A_(flags, N); A_(idx, N); A_(queue, 16); A_(prof, 32);
 #undef A_
     SETUP_TRACE("35 x hipMalloc");
     // (everything below goes through the context's OWN stream: it is non-blocking, so a hipMemset on the null stream is not
@@ -491,7 +491,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     (void)hipMemsetAsync(c->r_new, 0, sizeof(double) * ND, c->stream);
     (void)hipMemsetAsync(c->logw, 0, sizeof(double) * N, c->stream);
     (void)hipMemsetAsync(c->nleap, 0, sizeof(int32_t) * N, c->stream);
-    (void)hipMemsetAsync(c->prof, 0, sizeof(unsigned long long) * 16, c->stream);
+    (void)hipMemsetAsync(c->prof, 0, sizeof(unsigned long long) * 32, c->stream);
     if ((e = stream_wait(c->stream)) != hipSuccess) return fail("initial memsets", e);   // (model_data is the caller's)
     SETUP_TRACE("memsets + wait");
     for (int i = 0; i < kTimerRing; ++i) {
@@ -572,6 +572,26 @@ int smcn_set_phase_paths(smcn_ctx* c, int on) {
     CHECK_CTX(c);
     if (on != 0 && on != 1) FAIL(c, "smcn_set_phase_paths: 0 or 1");
     c->phase_paths = on;
+    return 0;
+}
+// nuts3_kernel with a lane per particle: a lane whose tree ended starts its next one in the next iteration whose number is a
+// multiple of n (default 4; 1 = in the very next iteration).  A tree takes 2^depth iterations, so lanes that start together
+// stay in step until one stops early; with n = 4 that lane sits out up to 3 iterations and its wave mates keep the cheap and
+// the expensive turns of the merge code in the same iterations.  Only WHEN a tree runs changes: same bits with
+// smcn_set_wide_eval(0) (tests/test_gpu_tree_align.py).  The lane queue has its own rule (Nuts2Args::seg_align).
+int smcn_set_tree_align(smcn_ctx* c, int n) {
+    CHECK_CTX(c);
+    if (n != 1 && n != 2 && n != 4 && n != 8) FAIL(c, "smcn_set_tree_align: 1, 2, 4 or 8");
+    c->tree_align = n;
+    return 0;
+}
+// loop iterations of the first n wavefronts of the last nuts3_kernel launch (every instantiation leaves them)
+int smcn_get_wave_iterations(smcn_ctx* c, uint32_t* out, int64_t n) {
+    CHECK_CTX(c);
+    if (!out || n < 0) FAIL(c, "smcn_get_wave_iterations: bad arguments");
+    if (n > c->wave_iters_n) FAIL(c, "smcn_get_wave_iterations: the last lane-kernel launch had fewer wavefronts (or there was none)");
+    HIPC(c, stream_wait(c->stream));
+    if (n > 0) HIPC(c, hipMemcpy(out, c->wave_iters, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
     return 0;
 }
 // pipelined fused blocks: what runs between the NUTS launch and the host's wait.  1 (default): one streaming kernel and
@@ -1545,6 +1565,10 @@ static int launch_nuts3(smcn_ctx* c, Nuts2Args a, const double* tape_d, const in
     if (int rc = grow(c, c->n2_ovf, blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, LC, LF))) return rc;
     a.ovf = c->n2_ovf;
     if (phase != 2) {
+        if (int rc = grow(c, c->wave_iters, blocks)) return rc;
+        a.wave_iters = c->wave_iters;
+        a.tree_align = c->tree_align;
+        c->wave_iters_n = blocks;
         if (c->momentum_set && B != 1) FAIL(c, "nuts3: caller-supplied momenta go with single transitions");
         nuts3_prep_kernel<D><<<grid_for(N * B, 256), 256, 0, c->stream>>>(c->x, c->momentum_set ? c->r : nullptr, c->r,
                                                                          c->in_rec, N, c->base, c->seed, a.iter, B, tape_d,
@@ -2278,6 +2302,7 @@ int smcn_fuse_begin(smcn_ctx* c, int Bmax, int world) {
         if (int rc = reset_records(c, Bmax, D)) return rc;
         const int64_t blocks = (c->N + kN3Block - 1) / kN3Block;
         if (int rc = grow(c, c->n2_ovf, blocks * kN3Block * 2 * (int64_t)n3_ovf_pairs(D, 3, 3))) return rc;
+        if (int rc = grow(c, c->wave_iters, blocks)) return rc;
     }
     return 0;
 }
@@ -3116,12 +3141,12 @@ int smcn_debug_profile(smcn_ctx* c, uint64_t out[16], int reset) {
     CHECK_CTX(c);
     HIPC(c, stream_wait(c->stream));
     if (out) {
-        HIPC(c, hipMemcpy(out, c->prof, sizeof(uint64_t) * 16, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(out, c->prof + ((reset & 2) ? 16 : 0), sizeof(uint64_t) * 16, hipMemcpyDeviceToHost));
         unsigned int qv[4];
         HIPC(c, hipMemcpy(qv, c->queue, sizeof qv, hipMemcpyDeviceToHost));
         if (!c->lane_kernel) out[6] = qv[2];   // residency census of the last launch: max blocks alive at once
     }
-    if (reset) HIPC(c, hipMemsetAsync(c->prof, 0, sizeof(uint64_t) * 16, c->stream));
+    if (reset & 1) HIPC(c, hipMemsetAsync(c->prof, 0, sizeof(uint64_t) * 32, c->stream));
     return 0;
 }
 

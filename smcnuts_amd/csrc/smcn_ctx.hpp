@@ -176,6 +176,9 @@ struct smcn_ctx {
     int tb_world = 0, tb_blocks = 0;
     int wide_eval = 1;         // nuts3_kernel: lane groups evaluate a wavefront's last stragglers (smcn_set_wide_eval)
     int phase_paths = 1;       // nuts3_kernel: one branch over the bookkeeping no lane needs in an iteration (smcn_set_phase_paths)
+    int tree_align = 4;        // nuts3_kernel, a lane per particle: trees start in iterations that are multiples of this (smcn_set_tree_align)
+    Buf<unsigned int> wave_iters;   // nuts3_kernel: loop iterations of each wavefront of the last launch (smcn_get_wave_iterations)
+    int64_t wave_iters_n = 0;  // ... and how many wavefronts that launch had
     int64_t lane_grid_cap = 0; // nuts3_kernel: wavefronts launched at most (0: one per SIMD; < 0: no cap, a wavefront per 64 particles)
     int lane_segments = 0;     // nuts3_kernel, fewer lanes than particles: segments a block is worked off in (0: auto, 1: whole blocks)
     Buf<unsigned long long> handover;  // [N][segments - 1][VH + 1 pairs] (lane queue: x', running log-weight between segments)

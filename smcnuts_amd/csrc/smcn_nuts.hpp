@@ -95,15 +95,16 @@ __device__ __forceinline__ unsigned long long prof_stamp() {
 // (the accumulators are per lane and lane 0's are reported: a stamp inside a divergent region counts for lane 0 only
 // when lane 0 is in it -- the time of a region it skips lands on the next stamp it does execute)
 #define PROF_DECL                                                                                         \
-    unsigned long long pt_ = prof_stamp(), pacc_[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};        \
-    bool prof_on_ = true;                                                                                 \
+    unsigned long long pt_ = prof_stamp(), pacc_[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
+    bool prof_on_ = true, prof_inph_ = false;                                                             \
     unsigned int prof_ph_ = 0u
 #define PROF_ON(c) prof_on_ = (c)   /* count the following stamps only while c holds (wave-uniform) */
 #ifdef SMCN_PROFILE_PHASE
 // (-DSMCN_PROFILE -DSMCN_PROFILE_PHASE, nuts3_kernel: the slots are re-used -- 0..3 the cycles of everything but the draws,
 // the leapfrog and the evaluation (sections 0..2), split by the iteration's number mod 4 (prof_ph_, set at the loop's top);
 // 12 those three sections; 4..7 / 8..11 are counts the kernel adds itself: iterations per residue, and those of them in
-// which every live lane started its tree in an iteration that was a multiple of 4)
+// which every live lane started its tree in an iteration that was a multiple of 4; 16..19 (the buffer's second page,
+// smcn_debug_profile) the part of 0..3 spent in those in-phase iterations (prof_inph_, set with prof_ph_))
 #define PROF(sec)                                                               \
     do {                                                                        \
         const unsigned long long n_ = prof_stamp(), d_ = prof_on_ ? n_ - pt_ : 0ull; \
@@ -113,6 +114,10 @@ __device__ __forceinline__ unsigned long long prof_stamp() {
             pacc_[1] += prof_ph_ == 1u ? d_ : 0ull;                             \
             pacc_[2] += prof_ph_ == 2u ? d_ : 0ull;                             \
             pacc_[3] += prof_ph_ == 3u ? d_ : 0ull;                             \
+            pacc_[16] += prof_inph_ && prof_ph_ == 0u ? d_ : 0ull;              \
+            pacc_[17] += prof_inph_ && prof_ph_ == 1u ? d_ : 0ull;              \
+            pacc_[18] += prof_inph_ && prof_ph_ == 2u ? d_ : 0ull;              \
+            pacc_[19] += prof_inph_ && prof_ph_ == 3u ? d_ : 0ull;              \
         }                                                                       \
         pt_ = n_;                                                               \
     } while (0)
@@ -128,6 +133,7 @@ __device__ __forceinline__ unsigned long long prof_stamp() {
     do {                                                                            \
         if ((threadIdx.x & 63u) == 0) {                                             \
             for (int s_ = 0; s_ < 14; ++s_) atomicAdd(&(a).prof[s_], pacc_[s_]);    \
+            for (int s_ = 16; s_ < 20; ++s_) atomicAdd(&(a).prof[s_], pacc_[s_]);   \
         }                                                                           \
     } while (0)
 #else

@@ -44,6 +44,10 @@ struct Nuts2Args {
                                      // re-associated sums); bit 1 = idle lanes draw the stragglers' uniforms (always on: same bits)
     int phase_paths = 1;             // nuts3: an iteration in which every leaf of the wavefront only parks at level 0 passes over
                                      // the merge, top-level and tree-end code in one branch (smcn_set_phase_paths: same bits)
+    int tree_align = 1;              // nuts3 with a lane per particle: a lane whose tree ended starts its next one in an iteration
+                                     // whose number is a multiple of this (a power of two; 1: in the very next iteration), so that
+                                     // a wavefront's trees stay in step (smcn_set_tree_align: same bits with wide bit 0 off)
+    unsigned int* wave_iters = nullptr;   // [wavefronts]: loop iterations each wavefront of the launch ran (smcn_get_wave_iterations)
 };
 
 // prep: momentum draw (samples.py:155) + slice exponential (nuts.py:69) + packing of the input records, which are

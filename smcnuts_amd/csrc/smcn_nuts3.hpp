@@ -935,6 +935,7 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
         if (phase == INIT) prof_t0 = it;
         {
             const unsigned long long inph = __ballot(act && (prof_t0 & 3u) != 0u) == 0ull ? 1ull : 0ull;   // (wave-uniform)
+            prof_inph_ = inph != 0ull;
             pacc_[4] += prof_ph_ == 0u ? 1ull : 0ull; pacc_[8] += prof_ph_ == 0u ? inph : 0ull;
             pacc_[5] += prof_ph_ == 1u ? 1ull : 0ull; pacc_[9] += prof_ph_ == 1u ? inph : 0ull;
             pacc_[6] += prof_ph_ == 2u ? 1ull : 0ull; pacc_[10] += prof_ph_ == 2u ? inph : 0ull;
@@ -1223,6 +1224,13 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
                             emit_record(!more, qdone, ovdone, nldone);
                             PROF(13);
                             if (more && bdone + 2 < a.B) request();
+                            // the next tree starts in an iteration that keeps the lane's trees in step with its wave mates'
+                            // (always so after a tree that ran its 2^depth iterations); else the lane sits out, everything
+                            // it needs already taken, until the loop's bottom wakes it
+                            if (more && ((it + 1u) & (unsigned int)(a.tree_align - 1)) != 0u) {
+                                phase = DONE;
+                                own_wait = true;
+                            }
                         }
                     } else {
                         start_doubling = true;
@@ -1398,9 +1406,15 @@ __global__ void __launch_bounds__(kN3Block) __attribute__((amdgpu_waves_per_eu(W
         }
         PROF(6);
         if constexpr (!QUEUE) {
-            if (__ballot(phase != DONE) == 0ull) break;
+            // a lane that sat out (a.tree_align) starts its tree in the next iteration if that one is in step
+            const bool wake = own_wait && ((it + 1u) & (unsigned int)(a.tree_align - 1)) == 0u;
+            phase = wake ? (int)INIT : phase;
+            own_wait = own_wait && !wake;
+            if (__ballot(phase != DONE || own_wait) == 0ull) break;
         }
     }
+    // the loop iterations this wavefront ran (smcn_get_wave_iterations: the schedule, for the tests)
+    if (lane == 0) a.wave_iters[blockIdx.x] = QUEUE ? it : it + 1u;
     PROF_FLUSH(a);
 #ifdef SMCN_PROFILE
     if (lane == 0) {   // prof[14]: wave-iterations summed, prof[15]: the longest wave

@@ -34,9 +34,18 @@ if os.environ.get("PROF_PHASE"):   # a -DSMCN_PROFILE -DSMCN_PROFILE_PHASE build
     print(f"every live lane's tree began at a multiple of 4: {inph.sum() / cnt.sum() * 100:.2f}% of the wave-iterations")
     print(f"every leaf of the wavefront parks at level 0 (one branch over the rest of the bookkeeping): {v[13] / cnt.sum() * 100:.2f}% "
           f"of the wave-iterations (0 in a build without that path, or with smcn_set_phase_paths(0))")
+    out2 = (C.c_uint64 * 16)()
+    ctx.call("smcn_debug_profile", out2, 2)      # the second page: slots 16..19, bookkeeping cycles of the in-phase iterations
+    bin_ = np.array(list(out2), dtype=np.float64)[0:4]
     for k in range(4):
         print(f"  it mod 4 = {k}: {cnt[k]:12.0f} wave-iterations, in phase {inph[k] / cnt[k] * 100:6.2f}%, "
-              f"bookkeeping {book[k] / cnt[k]:7.0f} cycles per wave-iteration")
+              f"bookkeeping {book[k] / cnt[k]:7.0f} cycles per wave-iteration: in phase {bin_[k] / max(inph[k], 1):7.0f}, "
+              f"not {(book[k] - bin_[k]) / (cnt[k] - inph[k]) if cnt[k] > inph[k] else 0.0:7.0f}")
+    # what the launch would cost if every wave-iteration had its residue's in-phase bookkeeping (the evaluation as measured)
+    now = (book.sum() + v[12]) / v[14]
+    then = (sum(bin_[k] / max(inph[k], 1) * cnt[k] for k in range(4)) + v[12]) / v[14]
+    print(f"always in phase: {then:.0f} cycles per wave-iteration against {now:.0f} ({(then / now - 1) * 100:+.2f}%); "
+          f"the launch at that rate {tm[0] / max(tm[1], 1) * then / now:.3f} ms against {tm[0] / max(tm[1], 1):.3f}")
     sys.exit(0)
 tot = v[:14].sum()
 for n, x in zip(names, v[:14]):
