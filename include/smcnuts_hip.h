@@ -827,6 +827,63 @@ int smcn_forecast_draws(smcn_ctx* ctx, const double* x_or_null /* [M][4] */, con
                         int64_t* n_bad_out);
 int smcn_forecast_last_ms(const smcn_ctx* ctx, double ms[2]);
 
+/* ---- one-step residual checks of the arma target (SMCN_MODEL_ARMA only; every other model fails with a message that
+ * names it).  Per point x = (mu, beta, theta, s), sigma = exp(s), and the context's series y_1..y_T, in this operation order:
+ *   err_t as above (the density's bits: err_T is what smcn_forecast_points reports)
+ *   nu_t = y_t - err_t                                   the one-step mean
+ *   r_t = err_t / sigma                                  the standardised residual
+ *   l_t = (-0.5 log 2 pi - s) - 0.5 (r_t r_t)            the one-step term; sum_t l_t is the arma log-likelihood
+ *   PIT_t = Phi(r_t) = 0.5 erfc(-r_t sqrt(1/2))
+ * A point is BAD at t when sigma is not finite or not > 0, or err_t or r_t is not finite.  A point whose err_t or r_t is
+ * finite but whose square is not (beyond about 1e154: a chain on its way to overflowing) is NOT bad at t: that row's second
+ * moments (S2, Z2: var and z_sd) are then inf or NaN while its bad count is still 0.
+ * With L lags (0..32, L <= T - 1), r_t := 0 for t < 1, all sums from 0 in ascending t:
+ *   A_0 = fma(r_t, r_t, A_0),  A_k = fma(r_t, r_{t-k}, A_k);   rho_k = A_k / A_0   (uncentred)
+ *   Q = (T (T + 2)) sum_{k=1..L} (rho_k rho_k) / (T - k)       (ascending k)
+ * A point is BAD FOR THE LAG ROWS when it is bad at any t, or A_0 is not finite or not > 0, or Q is not finite.  Q is the
+ * Ljung-Box statistic of the residuals REALISED at x: at a draw from the posterior the r_t are iid N(0, 1) if the model
+ * holds, so Q is compared with chi-square on L degrees of freedom, with no correction for the fitted parameters.
+ *
+ * smcn_residuals_set: the lags L and thresholds q_at [Tn] of Q (Tn 0..8, NULL with Tn = 0, only with L >= 1); all finite.
+ * Series with (T + L + 2) * 20 > 2^18 are refused.  Owned by the context, replaced by the next call.
+ * smcn_residuals_dims: T, L, the column count Qc = 20 of a partials block, Tn.
+ * smcn_residuals_points: the plain form for M caller-supplied points, out[M][W] row-major, W = 2T + (L > 0 ? L + 1 : 0):
+ * nu_1..nu_T, r_1..r_T (, rho_1..rho_L, Q).  A row with a non-finite coordinate is NaN throughout.
+ * smcn_residuals_partials: MERGEABLE partials out[1 + T + (L > 0 ? L + 1 : 0)][20]; x == NULL: the resident particles with
+ * their resident log-weights (M = N, logw = NULL); logw == NULL with x: equal weights.  Row 0 is smcn_pointwise_partials'
+ * header [mw, sw, sw2, cnt, 0 ..].  Time row t (row t), with lw' = lw - mw, w = exp(lw'), over the contributing particles
+ * (finite lw) that are not bad at t:
+ *   0 ml    max (lw' + l_t) over finite terms  (-inf: none)
+ *   1 Sl    sum exp(lw' + l_t - ml)            lpd_t = ml + log Sl - log sw
+ *   2 nbad  contributing particles that are bad at t: the row's moments, z and pit are NaN
+ *   3 c     the shift of nu_t's moments (NaN: none): a wavefront's weighted mean, formed about the nu_t of its first such
+ *           particle with w > 0; merged blocks keep the first block's
+ *   4 SW    sum w
+ *   5 S1    sum w (nu_t - c)                   mean_t = c + S1 / SW
+ *   6 S2    sum w (nu_t - c)^2                 between-particle variance S2 / SW - (S1 / SW)^2
+ *   7 V     sum w sigma^2                      var_t = V / SW + the between-particle variance
+ *   8 cz    the shift of r_t's moments, formed in the same way
+ *   9 Z1    sum w (r_t - cz)                   z_t = cz + Z1 / SW
+ *   10 Z2   sum w (r_t - cz)^2                 z_sd_t^2 = Z2 / SW - (Z1 / SW)^2  (never sum w r^2 - mean^2)
+ *   11 U    sum w Phi(r_t)                     pit_t = U / SW
+ *   12..19  0
+ * Lag row k (row T + k, k = 1..L) and the Q row (row T + L + 1), present with L > 0, over the contributing particles that
+ * are not bad for the lag rows: column 2 counts the contributing particles that are; columns 3..6 are c, SW, S1, S2 of
+ * rho_k (of Q); columns 0, 1 are (-inf, 0), columns 8..10 (NaN, 0, 0), column 7 and 11 are 0.  The Q row's column 12 + j
+ * is sum w [Q > q_at[j]], j < Tn; every other column from 12 on is 0.
+ * Merging two blocks (disjoint particle sets, in order) follows smcn_forecast_partials: headers and (ml, Sl) as
+ * max-shifted sums, the two moment groups re-centred on the first block's shifts, column 2 added unscaled, every other
+ * column scaled by exp(mw_k - max(mw)) and added.  The slices (blocks of 256 particles, a function of M alone) are merged
+ * in slice order, 16 at a time and then the groups.  No atomics: a repeated call returns identical bits.
+ * smcn_residuals_last_ms: device time of the kernels of the last smcn_residuals_partials (HIP events on the context's
+ * stream). */
+int smcn_residuals_set(smcn_ctx* ctx, int L, const double* q_at_or_null /* [Tn] */, int Tn);
+int smcn_residuals_dims(smcn_ctx* ctx, int64_t* T, int* L, int* Qc, int* Tn);
+int smcn_residuals_points(smcn_ctx* ctx, const double* x /* [M][4] */, int64_t M, double* out /* [M][W] */);
+int smcn_residuals_partials(smcn_ctx* ctx, const double* x_or_null /* [M][4] */, const double* logw_or_null /* [M] */,
+                            int64_t M, double* out /* [1 + T + (L > 0 ? L + 1 : 0)][20] */);
+int smcn_residuals_last_ms(const smcn_ctx* ctx, double* ms);
+
 /* Diagnostic builds only (-DSMCN_PROFILE): in-kernel cycle sums per section of
  * the NUTS loop, summed over wavefronts (out[0..7]; out[8], out[9]: loop trips of all wavefronts
  * and of the longest one); zeros in a normal build.  With -DSMCN_PROFILE_PHASE as well the lane kernel's slots are by the

@@ -15,6 +15,7 @@ from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F4
 from .psis import PsisLoo, compare_loo, merge_candidates, tail_len  # noqa: F401
 from .predict import Prediction, PredictiveDraws, combine_predict_partials, compare_heldout  # noqa: F401
 from .forecast import Forecast, combine_forecast_partials  # noqa: F401
+from .residuals import OneStepResiduals, combine_residual_partials  # noqa: F401
 from .summary import PosteriorSummary  # noqa: F401
 from .covariance import PosteriorCovariance, combine_cov_partials, device_covariance  # noqa: F401
 from .stepsize import StepSizeProbe, choose_step_size, combine_stepsize_partials  # noqa: F401

@@ -179,6 +179,11 @@ SIGNATURES = {
     "smcn_forecast_draws": ([_ctx, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, _lp, C.c_int64, C.c_int64, _dp, _lp, _lp],
                             C.c_int),
     "smcn_forecast_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_residuals_set": ([_ctx, C.c_int, _dp, C.c_int], C.c_int),
+    "smcn_residuals_dims": ([_ctx, _lp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    "smcn_residuals_points": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_residuals_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_residuals_last_ms": ([_ctx, _dp], C.c_int),
 }
 
 _lib = None
@@ -696,6 +701,37 @@ class Context:
     def forecast_last_ms(self):
         """Device time [partials, draws] of the last forecast calls' kernels (HIP events on the context's stream)."""
         return self._last_ms("smcn_forecast_last_ms", 2)
+
+    # ---- one-step residual checks (SMCN_MODEL_ARMA; include/smcnuts_hip.h, smcn_residuals_*) --------------
+    def residuals_set(self, lags, q_at=None):
+        """The number of lags L and the thresholds [Tn] of the Ljung-Box statistic (or None)."""
+        q = None if q_at is None else np.ascontiguousarray(q_at, dtype=np.float64).reshape(-1)
+        Tn = 0 if q is None else q.size
+        self.call("smcn_residuals_set", int(lags), dptr(q) if Tn else None, Tn)
+
+    def residuals_dims(self):
+        T, L, q, tn = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self.call("smcn_residuals_dims", C.byref(T), C.byref(L), C.byref(q), C.byref(tn))
+        return T.value, L.value, q.value, tn.value
+
+    def residuals_points(self, x):
+        """[M][2T (+ L + 1)]: nu_1..nu_T, r_1..r_T and, with lags, rho_1..rho_L and Q."""
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        T, L, _, _ = self.residuals_dims()
+        out = np.empty((x.shape[0], 2 * T + (L + 1 if L else 0)))
+        self.call("smcn_residuals_points", dptr(x), x.shape[0], dptr(out))
+        return out
+
+    def residuals_partials(self, x=None, logw=None):
+        """[1 + T (+ L + 1)][Qc] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
+        T, L, q, _ = self.residuals_dims()
+        out = np.empty((1 + T + (L + 1 if L else 0), q))
+        self.call("smcn_residuals_partials", *self._particles(x, logw), dptr(out))
+        return out
+
+    def residuals_last_ms(self):
+        """Device time of the last residuals_partials call's kernels (HIP events on the context's stream)."""
+        return self._last_ms("smcn_residuals_last_ms")
 
     def timers(self, reset=False):
         t = np.zeros(6)

@@ -1,7 +1,7 @@
 // What the units of libsmcnuts_hip.so share (internal, not installed): the context, its owner types, the entry points'
 // macros and the few host helpers that cross units.  smcn_api.hip is the core (context, sampler, loops, exchange); the
-// post-fit subsystems are smcn_loo.hip, smcn_predict.hip, smcn_summary.hip and smcn_forecast.hip, each with its own
-// sub-struct of smcn_ctx.
+// post-fit subsystems are smcn_loo.hip, smcn_predict.hip, smcn_summary.hip and smcn_forecast.hip (forecasts and the
+// one-step residual checks), each with its own sub-structs of smcn_ctx.
 // Every __global__ function is instantiated in exactly ONE unit: a unit that needs another's kernel calls the host
 // launcher declared at the end of this file.  Everything here but smcn_ctx lives in smcn_host, whose symbols are hidden:
 // none of them reaches the library's dynamic symbol table.
@@ -105,6 +105,15 @@ struct FcState {
     int Tn = 0, has_y = 0;
     Event ev0, ev1;
     double ms[2] = {};
+};
+// one-step residual checks of the arma target (smcn_residuals_*): the setting of the last smcn_residuals_set (L lags, -1:
+// none; the Tn thresholds of Q on the device), the log-weights, slices' and groups' partials and the result of a call;
+// device time of the last partials call
+struct RsState {
+    Buf<double> set, buf;
+    int L = -1, Tn = 0;
+    Event ev0, ev1;
+    double ms = 0.0;
 };
 }  // namespace smcn_host
 using namespace smcn_host;
@@ -235,6 +244,7 @@ struct smcn_ctx {
     CovState cov;
     StState st;      // smcn_api.hip (it runs the models' device functors): the step-size probe
     FcState fc;      // smcn_forecast.hip
+    RsState rs;      // smcn_forecast.hip (smcn_residuals.hpp)
 };
 
 #define CHECK_CTX(c)            \

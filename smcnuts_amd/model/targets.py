@@ -18,6 +18,7 @@ from .. import _capi
 from .. import _checks
 from .. import covariance as _covariance
 from .. import forecast as _forecast
+from .. import residuals as _residuals
 from .. import stepsize as _stepsize
 from .. import summary as _summary
 from .._checks import GLM_DISPERSION, GLM_FAMILIES, GLM_MAX_DIM
@@ -344,6 +345,66 @@ class ArmaModel(DeviceTarget):
         ctx = self._context(M)
         ctx.forecast_set(H)
         return PredictiveDraws(*ctx.forecast_draws(S, seed, x2, logw, ancestors))
+
+    # ---- one-step residual checks (smcnuts_amd/residuals.py); the argument checks run before a context exists ----
+    @property
+    def T(self):
+        return int(self.model_data[0])
+
+    def _residual_args(self, who, lags, levels=()):
+        """(L, levels, the chi-square 1 - level quantiles on L degrees of freedom: Q's thresholds; none with L = 0)."""
+        L = _residuals.check_lags(who, lags, self.T)
+        lv = _residuals.check_levels(who, levels) if L else ()
+        return L, lv, np.array([_residuals.chi2_isf(v, L) for v in lv], dtype=np.float64)
+
+    def residual_points(self, x, lags=None):
+        """Per point of x ([4] or [M, 4]) the in-sample one-step quantities: dict(nu [M, T] the one-step means, r [M, T] the
+        standardised residuals) and, with lags > 0 (None: min(10, T // 5)), rho [M, L] the residual autocorrelations and
+        Q [M] the Ljung-Box statistic.  A point with a non-finite coordinate gives NaN."""
+        L, _, _ = self._residual_args("ArmaModel.residual_points", lags)
+        x2 = _checks.points("ArmaModel", x, self.dim)
+        ctx = self._context(x2.shape[0])
+        ctx.residuals_set(L)
+        o, T = ctx.residuals_points(x2), self.T
+        out = dict(nu=o[:, :T], r=o[:, T:2 * T])
+        if L:
+            out.update(rho=o[:, 2 * T:2 * T + L], Q=o[:, 2 * T + L])
+        return out
+
+    def _residual_partials(self, who, x, logw, L, q):
+        """residual_partials' body behind the checks of `who`'s lags and thresholds (q: [Tn] or None)."""
+        x2 = _checks.points("ArmaModel", x, self.dim)
+        if logw is not None and np.shape(logw) != (x2.shape[0],):
+            raise ValueError(f"{who}: logw must hold one log-weight per row of x")
+        ctx = self._context(x2.shape[0])
+        ctx.residuals_set(L, q)
+        return ctx.residuals_partials(x2, logw)
+
+    def residual_partials(self, x, logw=None, lags=None, q_at=None):
+        """The mergeable partials of x's rows ([1 + T (+ L + 1)][20], include/smcnuts_hip.h); q_at: at most 8 thresholds of
+        the Ljung-Box statistic (with lags > 0 only)."""
+        who = "ArmaModel.residual_partials"
+        L, _, _ = self._residual_args(who, lags)
+        q = None
+        if q_at is not None:
+            try:
+                q = np.atleast_1d(np.asarray(q_at, dtype=np.float64))
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: q_at must be numeric") from None
+            if q.ndim != 1 or not 1 <= q.size <= _residuals.MAX_LEVELS or not np.all(np.isfinite(q)):
+                raise ValueError(f"{who}: q_at must hold 1 to {_residuals.MAX_LEVELS} finite thresholds")
+            if not L:
+                raise ValueError(f"{who}: q_at holds thresholds of the Ljung-Box statistic, which lags = 0 does not compute")
+        return self._residual_partials(who, x, logw, L, q)
+
+    def residuals(self, x, logw=None, lags=None, levels=(0.05,)):
+        """One-step residual checks from the weighted points (x [M, 4], logw unnormalised or None for equal weights) ->
+        residuals.OneStepResiduals: the one-step predictive mean, sd and log density of every y_t, the posterior mean of
+        the standardised residuals and PIT values, and with lags > 0 (None: min(10, T // 5)) the residual autocorrelations
+        and the Ljung-Box statistic with the posterior probability that it exceeds the chi-square 1 - level quantiles."""
+        who = "ArmaModel.residuals"
+        L, lv, q = self._residual_args(who, lags, levels)
+        return _residuals.combine_residual_partials([self._residual_partials(who, x, logw, L, q if q.size else None)], L, lv)
 
 
 class PRMwCDModel(DeviceTarget):

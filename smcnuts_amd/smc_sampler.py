@@ -752,6 +752,23 @@ class SMCSampler:
         return self._sharded_draws(ctx, S, H, seed, ANCESTOR_STREAM, lambda anc, s0, n: ctx.forecast_draws(
             S, seed, ancestors=anc, s_first=s0, s_count=n))
 
+    def residuals(self, lags=None, levels=(0.05,)):
+        """One-step residual checks of an ArmaModel fit (residuals.OneStepResiduals: the in-sample one-step predictive
+        mean, sd and log density of every y_t, standardised residuals and PIT values, and with lags > 0 (None:
+        min(10, T // 5)) the residual autocorrelations and the Ljung-Box statistic against the chi-square quantiles at
+        `levels`) of the final generation and its weights, after sample() / finalise(): computed from the resident
+        particles, nothing is downloaded but the [1 + T (+ L + 1)][20] partials.  Several shards: every rank computes its
+        partials, ONE host all-gather moves them, every rank combines them in rank order."""
+        from .residuals import combine_residual_partials
+        self._refuse_pooled("residuals", "residual diagnostics")
+        if not hasattr(self.target, "residual_partials"):
+            raise NotImplementedError(f"{type(self.target).__name__}: one-step residual diagnostics are implemented for "
+                                      "ArmaModel")
+        L, lv, q = self.target._residual_args("residuals", lags, levels)
+        ctx = self._final_generation("residuals")
+        ctx.residuals_set(L, q if q.size else None)
+        return combine_residual_partials(self._gather_partials(ctx.residuals_partials()), L, lv)
+
     def sample(self, show_progress=True):
         start_time = time()
         if self.device_resident and not self._host_loop_used:
