@@ -969,7 +969,9 @@ def test_gaussian_lkernel_algebra_on_the_device(D):
     """smcn_gauss_lkernel_device: the D x D algebra of the Gaussian L-kernel (gaussian_lkernel.py:45-82: pinv of c_xx, the
     conditional covariance with its ridge, the normal log-density) by two Cholesky factorisations of one wavefront gives the
     L values of the NumPy path (the reference's own pinv / eigh calls) and of the oracle's literal restatement -- and
-    refuses, handing the decision back to those calls, when a covariance is singular."""
+    refuses, handing the decision back to those calls, when a covariance is singular.  (How accurate the L values are,
+    and where the device decides to answer: tests/test_gpu_glk.py, against a 50-digit reference -- on its populations the
+    device is 0.002 .. 1.3 x as far from the exact values as the NumPy routes are.)"""
     from smcnuts_amd import GaussianTarget, SMCSampler, _capi
     from smcnuts_amd.lkernel.gaussian_lkernel import GaussianApproxLKernel
     N = 4096
