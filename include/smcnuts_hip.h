@@ -555,6 +555,50 @@ int smcn_pointwise_partials(smcn_ctx* ctx, const double* x_or_null /* [M][D] */,
                             int64_t M, double* out /* [1 + n][Q] */);
 int smcn_pointwise_last_ms(const smcn_ctx* ctx, double* ms);
 
+/* ---- calibration: predictive tails at the observations (SMCN_MODEL_GLM, all four families, D <= 64, any n) ----
+ * Per particle x_p and observation i, with the predictive law family(eta_{p,i} [, e^tau_p]) -- eta and the dispersion as
+ * the density forms them, o_i included:
+ *   lo = P(Y < y_i),  up = P(Y > y_i),  pmf = P(Y = y_i) = exp(ll[p][i]) for the discrete families (normal: lo + up = 1)
+ *   bernoulli_logit     lo: 0 (y = 0), sigmoid(-eta) (y = 1)            up: sigmoid(eta) (y = 0), 0 (y = 1)
+ *   poisson_log         lo: Q(y, mu) (0 at y = 0)                       up: P(y + 1, mu)                mu = e^eta
+ *   normal              lo: erfc(-z / sqrt 2) / 2                       up: erfc(z / sqrt 2) / 2        z = (y - eta) / sigma
+ *   neg_binomial_2_log  lo: I_pr(phi, y) (0 at y = 0)                   up: I_{1 - pr}(y + 1, phi)      pr = phi / (mu + phi)
+ * (P, Q: the regularised incomplete gamma functions; I: the regularised incomplete beta function).  Each tail has
+ * relative accuracy: the smaller one is a series or continued fraction times pmf, the larger one 1 - pmf - the other.
+ * Every such evaluation runs at most 2048 iterations; a pair that reaches the bound is "unconverged" (Poisson counts at
+ * their mode need about 8 sqrt(mu): counts near 1e5 and beyond fall outside).  Served contexts and refusals: as
+ * smcn_pointwise_* (SMCN_MODEL_GLM; SMCN_MODEL_OGLM with offsets alone; a weighted fit and every other model fail with a
+ * message that says so).
+ *
+ * smcn_calibration_dims: n and the column count Qc (= 9) of a partials block.
+ * smcn_calibration_points: out[M][n][2] = (lo, up) of every pair for M caller-supplied points x[M][D]; both NaN where
+ * the term is not finite or the pair is unconverged.
+ * smcn_calibration_partials: the sums OVER PARTICLES per observation as MERGEABLE partials out[1 + n][Qc]; x, logw, M,
+ * "contributing" and row 0 (the header) exactly as smcn_pointwise_partials.  Row 1 + i, observation i, with
+ * lw' = lw - mw, w = exp(lw') and every sum over the contributing particles whose term ll is finite and whose pair
+ * converged:
+ *   0 SW    sum w
+ *   1 LO    sum w lo                        pit_lo_i = LO / SW
+ *   2 UP    sum w up                        sf_i = UP / SW, pit_hi_i = 1 - sf_i
+ *   3 mb    max (lw' - ll)                  (-inf: no such particle) -- the leave-one-out weights, smcn_pointwise_partials' mb
+ *   4 Sb    sum exp(lw' - ll - mb)
+ *   5 LOb   sum exp(lw' - ll - mb) lo       pit_lo_loo_i = LOb / Sb
+ *   6 UPb   sum exp(lw' - ll - mb) up       sf_loo_i = UPb / Sb
+ *   7 ninf  contributing particles with ll = -inf
+ *   8 nunc  contributing particles whose pair is unconverged
+ * Rules of the finished values (smcnuts_amd.calibration.combine_calibration_partials): an observation with ninf > 0 or
+ * nunc > 0 reports NaN; all other observations are unaffected.
+ * Merging two blocks (disjoint particle sets, in order): headers as smcn_pointwise_partials; SW, LO, UP are scaled by
+ * exp(mw_k - max(mw)) and add; (mb, Sb, LOb, UPb) merge as max-shifted sums after adding mw_k - max(mw) to mb; ninf and
+ * nunc add.  No atomics; the particle slices of a call follow from M and n alone and are merged in slice order, so a
+ * repeated call returns identical bits.
+ * smcn_calibration_last_ms: the device time of the last smcn_calibration_partials' kernels, for measurements. */
+int smcn_calibration_dims(const smcn_ctx* ctx, int64_t* n_obs, int* n_cols);
+int smcn_calibration_points(smcn_ctx* ctx, const double* x /* [M][D] */, int64_t M, double* out /* [M][n][2] */);
+int smcn_calibration_partials(smcn_ctx* ctx, const double* x_or_null /* [M][D] */, const double* logw_or_null /* [M] */,
+                              int64_t M, double* out /* [1 + n][Qc] */);
+int smcn_calibration_last_ms(const smcn_ctx* ctx, double* ms);
+
 /* ---- Pareto-smoothed importance-sampling LOO (SMCN_MODEL_GLM, all four families, D <= 64, any n) ----
  * PSIS-LOO of the weighted particles with the shape k of the fitted generalised Pareto tail as its diagnostic (definition:
  * DESIGN.md 4.4).  With lw' = lw - mw, ll = log p(y_i | x_p) and lr = lw' - ll over the contributing particles (finite

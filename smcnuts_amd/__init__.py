@@ -11,6 +11,7 @@ from .smc_sampler import SMCSampler  # noqa: F401
 from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GLMTarget, HierarchicalGLM,  # noqa: F401
                             HostTarget, IsoGaussian, LinearRegression, LogisticRegression, MultilevelGLM,
                             NegativeBinomialRegression, OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel, WideGLMTarget)
+from .calibration import Calibration, combine_calibration_partials  # noqa: F401
 from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F401
 from .psis import PsisLoo, compare_loo, merge_candidates, tail_len  # noqa: F401
 from .predict import Prediction, PredictiveDraws, combine_predict_partials, compare_heldout  # noqa: F401

@@ -143,6 +143,10 @@ SIGNATURES = {
     "smcn_pointwise_loglik": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
     "smcn_pointwise_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
     "smcn_pointwise_last_ms": ([_ctx, _dp], C.c_int),
+    "smcn_calibration_dims": ([_ctx, _lp, C.POINTER(C.c_int)], C.c_int),
+    "smcn_calibration_points": ([_ctx, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_calibration_partials": ([_ctx, _dp, _dp, C.c_int64, _dp], C.c_int),
+    "smcn_calibration_last_ms": ([_ctx, _dp], C.c_int),
     "smcn_psis_candidates": ([_ctx, _dp, _dp, C.c_int64, C.c_double, C.c_int64, _dp], C.c_int),
     "smcn_psis_body": ([_ctx, _dp, _dp, C.c_int64, C.c_double, C.c_int64, _dp, _dp], C.c_int),
     "smcn_psis_fit": ([_ctx, _dp, _dp, C.c_int64, C.c_double, C.c_int64, _dp], C.c_int),
@@ -441,6 +445,31 @@ class Context:
     def pointwise_last_ms(self):
         """Device time of the last pointwise_partials' kernels (HIP events on the context's stream)."""
         return self._last_ms("smcn_pointwise_last_ms")
+
+    # ---- calibration (SMCN_MODEL_GLM; include/smcnuts_hip.h, smcn_calibration_*) --------
+    def calibration_dims(self):
+        n, q = C.c_int64(0), C.c_int(0)
+        self.call("smcn_calibration_dims", C.byref(n), C.byref(q))
+        return n.value, q.value
+
+    def calibration_points(self, x):
+        """[M][n][2]: (lo, up) = (P(Y < y_i), P(Y > y_i)) under every point of x; NaN for an unconverged pair."""
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        n, _ = self.calibration_dims()
+        out = np.empty((x.shape[0], n, 2))
+        self.call("smcn_calibration_points", dptr(x), x.shape[0], dptr(out))
+        return out
+
+    def calibration_partials(self, x=None, logw=None):
+        """[1 + n][Qc] mergeable partials (include/smcnuts_hip.h); x=None: the resident particles and weights."""
+        n, q = self.calibration_dims()
+        out = np.empty((1 + n, q))
+        self.call("smcn_calibration_partials", *self._particles(x, logw), dptr(out))
+        return out
+
+    def calibration_last_ms(self):
+        """Device time of the last calibration_partials' kernels (HIP events on the context's stream)."""
+        return self._last_ms("smcn_calibration_last_ms")
 
     # ---- Pareto-smoothed LOO (SMCN_MODEL_GLM; include/smcnuts_hip.h, smcn_psis_*) ------
     def psis_candidates(self, mw, S, x=None, logw=None):

@@ -50,6 +50,7 @@ struct PwState {
     Buf<double> buf;
     Event ev0, ev1;     // (around the kernels of smcn_predict_partials and smcn_predict_draws too)
     double ms = 0.0;
+    double cal_ms = 0.0;   // smcn_calibration_partials' kernels (they use buf and the events as well)
 };
 // Pareto-smoothed LOO (smcn_psis_*): header, log-weights, the staged slab of ll, candidates, cutoffs, body partials and
 // the result of a call; device time of the stages of the last calls (candidates, body, fit, whole smcn_psis_loo)

@@ -1,7 +1,9 @@
-// libsmcnuts_hip.so, the model-comparison unit: pointwise criteria (smcn_pointwise_*) and Pareto-smoothed LOO
-// (smcn_psis_*).  Owns the kernels of smcn_pointwise.hpp and smcn_psis.hpp, and smcn_ctx's pw and ps.
+// libsmcnuts_hip.so, the model-comparison unit: pointwise criteria (smcn_pointwise_*), calibration (smcn_calibration_*)
+// and Pareto-smoothed LOO (smcn_psis_*).  Owns the kernels of smcn_pointwise.hpp, smcn_calibration.hpp and smcn_psis.hpp,
+// and smcn_ctx's pw and ps.
 #include "smcn_ctx.hpp"
 #include "smcn_pointwise.hpp"
+#include "smcn_calibration.hpp"
 #include "smcn_psis.hpp"
 
 // ---- pointwise log-likelihood and its reductions over particles (smcn_pointwise.hpp) ------------------------------------
@@ -101,6 +103,83 @@ int smcn_pointwise_partials(smcn_ctx* c, const double* x, const double* logw, in
 int smcn_pointwise_last_ms(const smcn_ctx* c, double* ms) {
     if (!c || !ms) return -1;
     *ms = c->pw.ms;
+    return 0;
+}
+
+// ---- calibration: the predictive tails at the observations and their sums over particles (smcn_calibration.hpp) ---------
+int smcn_calibration_dims(const smcn_ctx* cc, int64_t* n_obs, int* n_cols) {
+    smcn_ctx* c = const_cast<smcn_ctx*>(cc);
+    if (!c) return -1;
+    if (!pw_refusal(c).empty()) FAIL(c, "smcn_calibration_dims: " + pw_refusal(c));
+    if (n_obs) *n_obs = c->reg.n;
+    if (n_cols) *n_cols = kCalCols;
+    return 0;
+}
+
+int smcn_calibration_points(smcn_ctx* c, const double* x, int64_t M, double* out) {
+    CHECK_CTX(c);
+    if (!pw_refusal(c).empty()) FAIL(c, "smcn_calibration_points: " + pw_refusal(c));
+    if (!x || !out || M < 1) FAIL(c, "smcn_calibration_points: bad arguments");
+    const int64_t n = c->reg.n, tiles = (n + 63) / 64;
+    int64_t cps = 1;
+    const int64_t slices = pointwise_slices(M, n, &cps);
+    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_calibration_points: too many observations");
+    int rc = ensure_stage(c, M * c->D);
+    if (rc) return rc;
+    if ((rc = grow(c, c->pw.buf, 2 * M * n))) return rc;
+    HIPC(c, hipMemcpyAsync(c->stage, x, sizeof(double) * M * c->D, hipMemcpyHostToDevice, c->stream));
+    const PwArgs a = pw_args(c->reg, c->mdata, c->stage, c->D, 1, M, cps);
+    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
+        calibration_points_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
+            <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, c->pw.buf);
+    });
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(out, c->pw.buf, sizeof(double) * 2 * M * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    return 0;
+}
+
+int smcn_calibration_partials(smcn_ctx* c, const double* x, const double* logw, int64_t M, double* out) {
+    CHECK_CTX(c);
+    if (!pw_refusal(c).empty()) FAIL(c, "smcn_calibration_partials: " + pw_refusal(c));
+    if (!out || M < 1) FAIL(c, "smcn_calibration_partials: bad arguments");
+    const int64_t n = c->reg.n, tiles = (n + 63) / 64, npad = tiles * 64;
+    int64_t cps = 1;
+    const int64_t slices = pointwise_slices(M, n, &cps);
+    if (tiles * slices > 2147483647LL) FAIL(c, "smcn_calibration_partials: too many observations");
+    // pw.buf: [header 16 | lw M | slice partials | group partials | result (1 + n) Qc]
+    const int64_t groups = (slices + kPwGroup - 1) / kPwGroup;
+    const int64_t o_lw = 16, o_part = o_lw + (M + 15) / 16 * 16, o_grp = o_part + slices * kCalCols * npad;
+    const int64_t o_out = o_grp + groups * kCalCols * npad;
+    int rc = grow(c, c->pw.buf, o_out + (1 + n) * kCalCols);
+    if (rc) return rc;
+    double* const head = c->pw.buf;
+    double* const part = c->pw.buf + o_part;
+    double* const grp = c->pw.buf + o_grp;
+    double* const res = c->pw.buf + o_out;
+    Particles P;
+    if ((rc = stage_particles(c, "smcn_calibration_partials", x, logw, M, c->pw.buf + o_lw, &P))) return rc;
+    const double* const lw = P.lw;
+    const PwArgs a = pw_args(c->reg, c->mdata, P.xd, P.rs, P.cs, M, cps);
+    HIPC(c, c->pw.ev0.record(c->stream));
+    launch_pointwise_header(c, lw, M, head);
+    row_cap_glm(c->reg, [&](auto dp, auto disp, auto ow) {
+        calibration_stats_kernel<decltype(dp)::value, decltype(disp)::value, decltype(ow)::value>
+            <<<(int)(tiles * slices), 64, 0, c->stream>>>(a, tiles, lw, head, part);
+    });
+    calibration_combine_kernel<false><<<dim3((unsigned)grid_for(n, 64), (unsigned)groups), 64, 0, c->stream>>>(part, head, slices, n, npad, grp);
+    calibration_combine_kernel<true><<<grid_for(n, 64), 64, 0, c->stream>>>(grp, head, groups, n, npad, res);
+    HIPC(c, hipGetLastError());
+    HIPC(c, c->pw.ev1.record(c->stream));
+    HIPC(c, hipMemcpyAsync(out, res, sizeof(double) * (1 + n) * kCalCols, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, stream_wait(c->stream));
+    HIPC(c, c->pw.ev1.since(c->pw.ev0, &c->pw.cal_ms));
+    return 0;
+}
+
+int smcn_calibration_last_ms(const smcn_ctx* c, double* ms) {
+    if (!c || !ms) return -1;
+    *ms = c->pw.cal_ms;
     return 0;
 }
 

@@ -36,7 +36,9 @@ struct PwArgs {
 
 // Walks the slice's particles for the tile's 64 observations.  `chunk(lane's particle index, live)` returns the
 // particle's log-weight term (per lane: one particle each); f(t, lwq, wq, term, mean) takes one term of the lane's
-// observation, with t, lwq and wq = exp(lwq) wave-uniform.  Particles for which chunk() returns a non-finite value are passed over.
+// observation, with t, lwq and wq = exp(lwq) wave-uniform; a functor that takes (t, lwq, wq, term, mean, eta, y, k) is
+// handed the linear predictor, the lane's response and the particle's dispersion constants (zeros unless DISP) as well.
+// Particles for which chunk() returns a non-finite value are passed over.
 // OW: SMCN_MODEL_OGLM's table -- a row carries o_i and w_i behind lgamma(y_i + 1), the table lies at oglm_table_offset, and
 // eta_i takes o_i.  A parameter, off by default, so that the walks of SMCN_MODEL_GLM keep their instruction streams.
 template <int DPMAX, bool DISP, bool OW = false, class Chunk, class Term>
@@ -90,8 +92,8 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
             double eta = e0 + e1;
             if constexpr (OW) eta += off;
             double term, mean;
+            TauConst k{};
             if constexpr (DISP) {
-                TauConst k;
                 k.tau = group_read<64>(kc.tau, q);
                 k.phi = group_read<64>(kc.phi, q);
                 k.iphi = group_read<64>(kc.iphi, q);
@@ -107,7 +109,10 @@ __device__ __forceinline__ void pw_walk(const PwArgs& a, int64_t tile, int64_t s
             } else {
                 glm_canon_obs(poisson, eta, y, lgy, term, mean);
             }
-            f(p0 + q, lwq, group_read<64>(wv, q), term, mean);
+            if constexpr (std::is_invocable_v<Term&, int64_t, double, double, double, double, double, double, const TauConst&>)
+                f(p0 + q, lwq, group_read<64>(wv, q), term, mean, eta, y, k);     // (smcn_calibration.hpp: the tails want these)
+            else
+                f(p0 + q, lwq, group_read<64>(wv, q), term, mean);
         }
     }
 }

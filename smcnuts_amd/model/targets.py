@@ -92,6 +92,21 @@ class DeviceTarget:
     def loo(self, x, logw=None):
         self._no_pointwise()
 
+    # calibration checks (smcnuts_amd/calibration.py): GLMTarget only
+    def _no_calibration(self):
+        raise NotImplementedError(
+            f"{type(self).__name__}: calibration checks (PIT values, randomised quantile residuals) are implemented for "
+            "GLMTarget (bernoulli_logit, poisson_log, normal, neg_binomial_2_log) only")
+
+    def calibration_points(self, x):
+        self._no_calibration()
+
+    def calibration_partials(self, x, logw=None):
+        self._no_calibration()
+
+    def calibration(self, x, logw=None):
+        self._no_calibration()
+
     def summary(self, x, logw=None, probs=_summary.DEFAULT_PROBS, at=None):
         """summary.PosteriorSummary of the points x [M][D] (unconstrained) with log-weights logw (None: equal): weighted
         quantiles at `probs` (at most 16, each in (0, 1]) and, with `at` (a scalar, [T] or [Dc][T], T <= 16), the mass at
@@ -193,6 +208,15 @@ class HostTarget:
 
     def loo(self, x, logw=None):
         DeviceTarget._no_pointwise(self)
+
+    def calibration_points(self, x):
+        DeviceTarget._no_calibration(self)
+
+    def calibration_partials(self, x, logw=None):
+        DeviceTarget._no_calibration(self)
+
+    def calibration(self, x, logw=None):
+        DeviceTarget._no_calibration(self)
 
     def summary(self, x, logw=None, probs=_summary.DEFAULT_PROBS, at=None):
         """DeviceTarget.summary with the wrapped model's own constrain() on the host and the selection on the device."""
@@ -552,6 +576,33 @@ class GLMTarget(PredictMixin, DeviceTarget):
         for equal weights) -> criteria.Pointwise.  The matrix ll is never formed."""
         from ..criteria import combine_pointwise_partials
         return combine_pointwise_partials([self.pointwise_partials(x, logw)])
+
+    def calibration_points(self, x):
+        """(lo, up) = (P(Y < y_i), P(Y > y_i)) under every point of x: [n, 2] for a 1-D x, [M, n, 2] for 2-D.  NaN where the
+        term is not finite or the tail evaluation reached the device's iteration bound (calibration.py)."""
+        x2 = self._points(x)
+        M, n = x2.shape[0], self.y.shape[0]
+        step = max(1, min(M, self._PW_CHUNK // (2 * n)))
+        ctx = self._context(step)
+        out = np.empty((M, n, 2))
+        for m0 in range(0, M, step):
+            out[m0:m0 + step] = ctx.calibration_points(x2[m0:m0 + step])
+        return out[0] if np.ndim(x) == 1 else out
+
+    def calibration_partials(self, x, logw=None):
+        """The mergeable calibration partials of x's rows ([1 + n][Qc], include/smcnuts_hip.h)."""
+        x2 = self._points(x)
+        if logw is not None and np.shape(logw) != (x2.shape[0],):
+            raise ValueError("GLMTarget.calibration_partials: logw must hold one log-weight per row of x")
+        return self._context(x2.shape[0]).calibration_partials(x2, logw)
+
+    def calibration(self, x, logw=None):
+        """Calibration of the weighted points (x [M, D], logw unnormalised or None for equal weights) ->
+        calibration.Calibration: per observation the predictive cdf just below and at y_i (PIT bounds) and the survival
+        function, under the posterior and the leave-one-out weights; randomised PIT values, quantile residuals and the
+        non-randomised PIT histogram are its methods."""
+        from ..calibration import combine_calibration_partials
+        return combine_calibration_partials([self.calibration_partials(x, logw)])
 
     def loo(self, x, logw=None):
         """Pareto-smoothed importance-sampling LOO of the weighted points (x [M, D], logw unnormalised or None for equal

@@ -635,6 +635,22 @@ class SMCSampler:
         ctx = self._final_generation("pointwise")
         return combine_pointwise_partials(self._gather_partials(ctx.pointwise_partials()))
 
+    def calibration(self):
+        """Calibration checks (calibration.Calibration: per-observation PIT bounds and survival function under the posterior
+        and the leave-one-out weights, with randomised PIT values, quantile residuals and the PIT histogram as methods) of
+        the final generation and its weights, after sample() / finalise(): computed from the resident particles, nothing
+        is downloaded but the [1 + n][Qc] partials.  Several shards: ONE host all-gather, merged in rank order."""
+        from .calibration import combine_calibration_partials
+        self._refuse_pooled("calibration", "calibration checks")
+        if hasattr(self.target, "_refuse_weighted"):
+            self.target._refuse_weighted()      # (a GLMTarget fitted with weights: NotImplementedError)
+        elif hasattr(self.target, "calibration"):
+            self.target.calibration(None)       # raises NotImplementedError naming the supported targets
+        else:
+            raise NotImplementedError(f"{type(self.target).__name__}: calibration checks are implemented for GLMTarget only")
+        ctx = self._final_generation("calibration")
+        return combine_calibration_partials(self._gather_partials(ctx.calibration_partials()))
+
     def loo(self):
         """Pareto-smoothed importance-sampling LOO (psis.PsisLoo: elpd_loo_i, pareto_k_i, psis_ess_i and `plain`, what
         pointwise() returns) of the final generation and its weights, after sample() / finalise(): selected, fitted and
