@@ -83,6 +83,18 @@ typedef struct smcn_ctx smcn_ctx;
                               Pointwise log-likelihoods, prediction and predictive draws as for SMCN_MODEL_GLM (new rows:
                               [family, m, p, intercept, flags, y, o (flags & 1), w = 1.. (flags & 2), X]); the pointwise
                               criteria and PSIS-LOO are refused for a fit with weights (flags & 2) */
+/* (11 is unassigned: refused as an unknown model id) */
+#define SMCN_MODEL_CGLM 12   /* continuous-response GLM, SMCN_MODEL_GLM's linear predictor and coefficient priors with a scale
+                              coordinate: data = [family (0 gamma_log, 1 student_t), n, p, intercept, df (0 for gamma_log),
+                              s_1..s_Dc, m_tau, s_tau, y_1..y_n, X (n x p, row-major)], Dc = p + intercept >= 1,
+                              x = (b_1..b_Dc, tau), D = Dc + 1 <= 64, b_c ~ N(0, s_c^2), tau ~ N(m_tau, s_tau^2);
+                                family 0: y_i ~ Gamma(shape a = e^tau, rate a / e^eta_i) (mean e^eta_i), y finite and > 0;
+                                family 1: y_i ~ student_t(df, eta_i, sigma = e^tau), df finite and > 0 fixed by the caller,
+                                          y finite;
+                              constrain reports (b, e^tau).  llik = -inf where e^tau (gamma) or e^-tau (student_t) leaves
+                              the normal range, where e^-eta_i overflows (gamma) and where (y_i - eta_i) e^-tau overflows
+                              (student_t).  The pointwise criteria, PSIS-LOO, calibration, prediction and predictive draws
+                              are refused for this model */
 
 #define SMCN_LKERNEL_FORWARD 0  /* smcnuts/lkernel/forward_lkernel.py:22-35   */
 #define SMCN_LKERNEL_GAUSSIAN 1 /* smcnuts/lkernel/gaussian_lkernel.py:24-84  */

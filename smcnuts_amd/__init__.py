@@ -8,9 +8,10 @@ include/smcnuts_hip.h (libsmcnuts_hip.so), reached through ctypes.  No PyTorch
 on this path and no CPU fallback.
 """
 from .smc_sampler import SMCSampler  # noqa: F401
-from .model.targets import (ArmaModel, CategoricalRegression, GaussianTarget, GLMTarget, HierarchicalGLM,  # noqa: F401
-                            HostTarget, IsoGaussian, LinearRegression, LogisticRegression, MultilevelGLM,
-                            NegativeBinomialRegression, OrdinalRegression, PoissonRegression, PRMwCDModel, StanModel, WideGLMTarget)
+from .model.targets import (ArmaModel, CategoricalRegression, ContinuousGLM, GammaRegression, GaussianTarget,  # noqa: F401
+                            GLMTarget, HierarchicalGLM, HostTarget, IsoGaussian, LinearRegression, LogisticRegression,
+                            MultilevelGLM, NegativeBinomialRegression, OrdinalRegression, PoissonRegression, PRMwCDModel,
+                            RobustRegression, StanModel, WideGLMTarget)
 from .calibration import Calibration, combine_calibration_partials  # noqa: F401
 from .criteria import Pointwise, combine_pointwise_partials, compare  # noqa: F401
 from .psis import PsisLoo, compare_loo, merge_candidates, tail_len  # noqa: F401

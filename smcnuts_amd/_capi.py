@@ -17,6 +17,7 @@ MODEL_ORDINAL = 7
 MODEL_MLGLM = 8
 MODEL_WGLM = 9
 MODEL_OGLM = 10
+MODEL_CGLM = 12                            # (11 is unassigned)
 HOST_TARGET_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_int,
                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                              C.POINTER(C.c_double))

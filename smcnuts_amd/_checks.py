@@ -28,8 +28,14 @@ def dispersion_prior(who, family, value):
             raise ValueError(f"{who}: {family} has no dispersion parameter; dispersion_prior is for "
                              f"{tuple(GLM_DISPERSION)}")
         return None
+    return scale_prior(who, (0.0, 2.5) if value is NO_PRIOR else value)
+
+
+def scale_prior(who, value):
+    """(m, s) of tau ~ N(m, s^2) on a log scale or log shape that the family always has (ContinuousGLM's): a pair, m
+    finite, s finite and > 0."""
     try:
-        m, s = (float(v) for v in ((0.0, 2.5) if value is NO_PRIOR else value))
+        m, s = (float(v) for v in value)
     except (TypeError, ValueError):
         raise ValueError(f"{who}: dispersion_prior must be a pair (m, s)") from None
     if not math.isfinite(m):
@@ -86,6 +92,46 @@ def family_response(who, family, y, name="y"):
     elif not np.all(np.isfinite(y) & (y >= 0.0) & (y <= 2.0 ** 53) & (y == np.floor(y))):
         raise ValueError(f"{who}: neg_binomial_2_log needs {name} in {{0, 1, 2, ..., 2^53}}")
     return y
+
+
+CONTINUOUS_FAMILIES = ("gamma_log", "student_t")            # ContinuousGLM's, with ids of their own (SMCN_MODEL_CGLM)
+CONTINUOUS_SCALE = {"gamma_log": "shape", "student_t": "sigma"}    # what e^tau is, and its parameter name
+DEFAULT_DF = 4.0
+
+
+def continuous_family(who, family):
+    if family not in CONTINUOUS_FAMILIES:
+        raise ValueError(f"{who}: family must be one of {CONTINUOUS_FAMILIES}, not {family!r}")
+    return family
+
+
+def continuous_response(who, family, y, name="y"):
+    """y within the family's support: finite, and > 0 for gamma_log."""
+    if family == "gamma_log":
+        if np.any(y == 0.0):
+            raise ValueError(f"{who}: gamma_log needs {name} > 0 and {name} holds zeros (the gamma density has none: "
+                             "model the zeros apart, or shift the response)")
+        if not np.all(np.isfinite(y) & (y > 0.0)):
+            raise ValueError(f"{who}: gamma_log needs finite {name} > 0")
+    elif not np.all(np.isfinite(y)):
+        raise ValueError(f"{who}: student_t needs finite {name}")
+    return y
+
+
+def student_df(who, family, df):
+    """student_t's fixed degrees of freedom, finite and > 0; gamma_log has none and refuses a value other than the
+    default.  Returns the header's slot: df, or 0 for gamma_log."""
+    try:
+        v = float(df)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: df must be a number") from None
+    if family != "student_t":
+        if v != DEFAULT_DF:
+            raise ValueError(f"{who}: {family} has no degrees of freedom; df is for student_t")
+        return 0.0
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"{who}: df must be finite and > 0")
+    return v
 
 
 def index_vector(who, v, n, name, what=None):

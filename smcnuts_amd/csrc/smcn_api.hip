@@ -310,6 +310,11 @@ static int with_model(smcn_ctx* c, F&& f) {
     }
     if (c->model == SMCN_MODEL_GLM) return with_flat_glm<false>(c, f);
     if (c->model == SMCN_MODEL_OGLM) return with_flat_glm<true>(c, f);
+    if (c->model == SMCN_MODEL_CGLM) {
+        // (checked at creation: D = Dc + 1 <= 64; the flat dispersion families' two shapes)
+        if (c->D <= kGlmDispG8) return f(GlmContModel<8, kGlmDispG8 / 8>{});
+        return f(GlmContModel<64, 1>{});
+    }
     // (smcn_ctx_create has checked the data and refused D > 64)
     if (c->model == SMCN_MODEL_HGLM) return f(GlmHierModel<64, 1>{});
     if (c->model == SMCN_MODEL_MLGLM) return f(GlmMultiModel<64, 1>{});
@@ -411,7 +416,8 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
         case SMCN_MODEL_ORDINAL:
         case SMCN_MODEL_MLGLM:
         case SMCN_MODEL_WGLM:
-        case SMCN_MODEL_OGLM: {
+        case SMCN_MODEL_OGLM:
+        case SMCN_MODEL_CGLM: {
             const std::string why = reg_check(model_id, model_data, model_data_len, &c->reg);
             if (!why.empty()) {
                 g_create_error = "smcn_ctx_create: " + why;
@@ -430,6 +436,7 @@ int smcn_ctx_create(smcn_ctx** out, int device_id, int64_t n_particles, int64_t 
     // GLM normal / neg_binomial_2_log: the last coordinate is log sigma / log phi, reported as sigma / phi -- the rule
     // constrain_coord applies to arma's log sigma (the other models keep their own id)
     c->cmodel = ((model_id == SMCN_MODEL_GLM || model_id == SMCN_MODEL_WGLM || model_id == SMCN_MODEL_OGLM) && c->reg.disp()) ? SMCN_MODEL_ARMA : model_id;
+    if (model_id == SMCN_MODEL_CGLM) c->cmodel = SMCN_MODEL_ARMA;   // continuous GLM: tau is always there, reported as e^tau
     // hierarchical and multilevel GLM, ordinal: the constrained space is not coordinate-wise; the moment kernels read a constrained copy
     // of the population (model_constrained) with the identity
     if (model_id == SMCN_MODEL_HGLM || model_id == SMCN_MODEL_ORDINAL || model_id == SMCN_MODEL_MLGLM)

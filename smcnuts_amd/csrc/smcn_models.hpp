@@ -1433,3 +1433,5 @@ struct GlmOrdModel {
 };
 
 }  // namespace smcn
+
+#include "smcn_glm_cont.hpp"   // SMCN_MODEL_CGLM: the continuous-response families and their functor

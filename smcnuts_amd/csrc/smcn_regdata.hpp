@@ -1,4 +1,4 @@
-// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL, _MLGLM, _WGLM, _OGLM) on the host: where the
+// The data block of a regression target (SMCN_MODEL_GLM, _HGLM, _CATEGORICAL, _ORDINAL, _MLGLM, _WGLM, _OGLM, _CGLM) on the host: where the
 // header, the priors, y, g (and z) and X sit in the caller's block, which table the functors read behind it, the check
 // of a caller's block and its repacking.  Plain C++17 with no HIP types: it compiles without a device compiler, so the code that
 // indexes by caller-supplied lengths runs under the host sanitizers (tests/test_regdata_host.py).  The layout helpers
@@ -34,6 +34,11 @@ SMCN_HD inline int64_t oglm_table_offset(int64_t npri, int64_t n, int64_t p) {
     return (5 + npri + 3 * n + n * p + 15) / 16 * 16;
 }
 SMCN_HD inline int oglm_row_doubles(int Dc) { return ((Dc + 1) & ~1) + 4; }
+// continuous-response GLM (SMCN_MODEL_CGLM): five header slots (df behind the intercept flag); the flat GLM's rows, with
+// log y_i (gamma_log) or 0 (student_t) in the slot behind y_i
+SMCN_HD inline int64_t cglm_table_offset(int64_t npri, int64_t n, int64_t p) {
+    return (5 + npri + n + n * p + 15) / 16 * 16;
+}
 // hierarchical GLM: the doubles before y, the table behind y, g and X, its row with the group slot
 SMCN_HD inline int64_t hglm_head(int64_t Dc, bool disp) { return 5 + Dc + 1 + (disp ? 2 : 0); }
 SMCN_HD inline int64_t hglm_table_offset(int64_t head, int64_t n, int64_t p) {
@@ -65,6 +70,7 @@ struct RegLayout {
     int64_t Jr[kMlMaxTerms] = {0, 0, 0, 0};
     int ic = 0;                 // intercept flag
     int flags = 0;              // SMCN_MODEL_OGLM: 1 offsets, 2 weights
+    double df = 0.0;            // SMCN_MODEL_CGLM: student_t's degrees of freedom (0: gamma_log)
     int Dc = 0, D = 0;          // columns of a table row (p for the ordinal model), coordinates
     int64_t nh = 0, npri = 0;   // header doubles, prior doubles
     int64_t y0 = 0, g0 = 0, X0 = 0, len = 0;      // offsets in the block (g0 = 0: no groups; multilevel: g_1), the block's length
@@ -156,7 +162,17 @@ inline const Spec* spec(int model) {
         "offset GLM target: the device functor covers D <= 64 coefficients; larger models run host-evaluated "
         "(SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through HostTarget)",
         "offset GLM target: prior sds must be finite and > 0", 0.0, 64.0, nullptr, true};
+    static const Spec cglm = {
+        5, true, false, false, true, 0.0, 1048576.0, "continuous GLM target: ",
+        "continuous GLM target: data = [family, n, p, intercept, df, s_1..s_Dc, m_tau, s_tau, y_1..y_n, X (n x p, "
+        "row-major)]",
+        "continuous GLM target: family must be 0 (gamma_log) or 1 (student_t)",
+        "continuous GLM target: the device functor covers D = Dc + 1 <= 64 coordinates (the coefficients and tau); larger "
+        "models run host-evaluated (SMCN_MODEL_HOST + smcn_set_host_target: any object with logpdf / logpdfgrad through "
+        "HostTarget)",
+        "continuous GLM target: prior sds must be finite and > 0", 0.0, 64.0, nullptr};
     switch (model) {
+        case SMCN_MODEL_CGLM: return &cglm;
         case SMCN_MODEL_OGLM: return &oglm;
         case SMCN_MODEL_GLM: return &glm;
         case SMCN_MODEL_WGLM: return &wglm;
@@ -179,11 +195,15 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     const bool og = model == SMCN_MODEL_OGLM;
     const bool glm = model == SMCN_MODEL_GLM || model == SMCN_MODEL_WGLM || og, hg = model == SMCN_MODEL_HGLM, cat = model == SMCN_MODEL_CATEGORICAL;
     const bool ml = model == SMCN_MODEL_MLGLM;
+    const bool cg = model == SMCN_MODEL_CGLM;          // families of its own (0 gamma_log, 1 student_t), always with tau
     const bool fams = glm || hg || ml;                 // slot 0 is a family, not a class count
     if (len < sp->nh) return sp->layout;
     const double s0 = md[0], nd = md[1], pd = md[2], icd = sp->has_ic ? md[3] : 0.0, Jd = sp->has_J ? md[4] : 0.0;
-    if (fams ? !(s0 == 0.0 || s0 == 1.0 || s0 == 2.0 || s0 == 3.0) : !whole(s0, 2.0, sp->kmax)) return sp->slot0;
-    const bool disp = fams && s0 >= 2.0;
+    if (cg     ? !(s0 == 0.0 || s0 == 1.0)
+        : fams ? !(s0 == 0.0 || s0 == 1.0 || s0 == 2.0 || s0 == 3.0)
+               : !whole(s0, 2.0, sp->kmax))
+        return sp->slot0;
+    const bool disp = cg || (fams && s0 >= 2.0);
     if (!(icd == 0.0 || icd == 1.0)) return say("intercept must be 0 or 1");
     if (!whole(nd, 1.0, 2147483647.0)) return say("n must be an integer >= 1");
     if (!whole(pd, 0.0, sp->pmax)) return say("p must be an integer >= 0");
@@ -207,32 +227,37 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     const double Dcd = pd + icd;
     if (sp->need_cols && Dcd < 1.0) return say("no coefficients (p = 0 without an intercept)");
     // (in doubles: the ordinal model bounds neither p nor K before this)
-    const double Dd = glm  ? Dcd + (disp ? 1 : 0)
+    const double Dd = glm || cg ? Dcd + (disp ? 1 : 0)
                       : hg ? Dcd + Jd + 1 + (disp ? 1 : 0)
                       : ml ? Dcd + Jsum + Rd + (disp ? 1 : 0)
                       : cat ? (s0 - 1.0) * Dcd
                             : pd + s0 - 1.0;
     if (Dd > sp->dmax) return sp->too_big;
     if (Dd < sp->dmin) return sp->too_small;
+    // continuous GLM: df belongs to student_t alone
+    const double dfd = cg ? md[4] : 0.0;
+    if (cg && s0 == 1.0 && !(dfd > 0.0 && std::isfinite(dfd))) return say("student_t needs df finite and > 0");
+    if (cg && s0 == 0.0 && !(dfd == 0.0)) return say("gamma_log has no df: the slot must be 0");
     // the priors: sds, then the named ones -- a mean (finite) or an sd (finite and > 0)
     struct { const char* name; bool mean; } named[kMlMaxTerms + 2];
     int nn = 0;
     if (hg) named[nn++] = {"s_tau", false};
     for (int r = 0; r < (int)Rd; ++r) named[nn++] = {"s_tau", false};
     if (disp) {
-        named[nn++] = {glm ? "m_tau" : "m_d", true};
-        named[nn++] = {glm ? "s_tau" : "s_d", false};
+        named[nn++] = {glm || cg ? "m_tau" : "m_d", true};
+        named[nn++] = {glm || cg ? "s_tau" : "s_d", false};
     }
     RegLayout l;
     l.model = model;
-    (fams ? l.fam : l.K) = (int)s0;
+    (fams || cg ? l.fam : l.K) = (int)s0;
+    l.df = dfd;
     l.n = (int64_t)nd, l.p = (int64_t)pd, l.ic = (int)icd, l.J = (int64_t)Jd;
     l.Dc = (int)Dcd, l.D = (int)Dd;
     if (ml) {
         l.R = (int)Rd, l.J = (int64_t)Jsum;
         for (int r = 0; r < l.R; ++r) l.Jr[r] = (int64_t)md[5 + r];
     }
-    const int64_t n = l.n, p = l.p, nsd = fams ? l.Dc : l.D;
+    const int64_t n = l.n, p = l.p, nsd = fams || cg ? l.Dc : l.D;
     l.nh = sp->nh;
     l.npri = nsd + nn;
     l.y0 = hg ? hglm_head(l.Dc, disp) : l.nh + l.npri;
@@ -265,7 +290,11 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     }
     for (int64_t i = 0; i < n; ++i) {
         const double y = md[l.y0 + i];
-        if (!fams) {
+        if (cg) {
+            if (s0 == 0.0 ? !(y > 0.0 && std::isfinite(y)) : !std::isfinite(y))
+                return say(s0 == 0.0 ? "gamma_log needs finite y > 0 (a zero has no gamma density: model zeros apart)"
+                                     : "student_t needs finite y");
+        } else if (!fams) {
             if (!(y >= 0.0 && y < s0 && y == std::floor(y))) return say("every label y must be an integer in [0, K)");
         } else if (s0 == 0.0) {
             if (!(y == 0.0 || y == 1.0)) return say("bernoulli_logit needs y in {0, 1}");
@@ -301,7 +330,8 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
     for (int64_t t = 0; t < n * p; ++t)
         if (!std::isfinite(md[l.X0 + t])) return say("X must be finite");
     // the table, found as the functors find it (smcn_models.hpp)
-    l.t0 = og   ? oglm_table_offset(l.npri, n, p)
+    l.t0 = cg   ? cglm_table_offset(l.npri, n, p)
+           : og ? oglm_table_offset(l.npri, n, p)
            : glm ? glm_table_offset(l.npri, n, p)
            : hg ? hglm_table_offset(l.y0, n, p)
            : ml ? mlglm_table_offset(l.y0, l.R, n, p)
@@ -320,7 +350,7 @@ inline std::string reg_check(int model, const double* md, int64_t len, RegLayout
 
 // The image the functors read, from a checked block: `mup` becomes [block | padding | table (| class counts)].  A row is
 // [1 (intercept), X_i1 .. X_ip, 0 .. (to an even count), y_i, lgamma(y_i + 1) (families; 0 for the normal, whose y may
-// be negative), g_i (hierarchical) or g_1i, z_1i, .., g_Ri, z_Ri (multilevel) or o_i (0 if absent), w_i (1 if absent)
+// be negative; continuous GLM: log y_i for gamma_log, 0 for student_t), g_i (hierarchical) or g_1i, z_1i, .., g_Ri, z_Ri (multilevel) or o_i (0 if absent), w_i (1 if absent)
 // (offsets / weights: a padding row is all zero, so its weight is 0), 0 ..]; the ordinal model's K class counts n_0..n_{K-1} follow the table.
 inline void reg_repack(const RegLayout& L, const double* md, std::vector<double>& mup) {
     const bool fams = L.model == SMCN_MODEL_GLM || L.model == SMCN_MODEL_HGLM || L.model == SMCN_MODEL_MLGLM ||
@@ -334,6 +364,7 @@ inline void reg_repack(const RegLayout& L, const double* md, std::vector<double>
         const double y = md[L.y0 + i];
         row[L.ys] = y;
         if (fams) row[L.ys + 1] = L.fam == 2 ? 0.0 : std::lgamma(y + 1.0);
+        if (L.model == SMCN_MODEL_CGLM) row[L.ys + 1] = L.fam == 0 ? std::log(y) : 0.0;
         if (L.g0 && !L.R) row[L.ys + 2] = md[L.g0 + i];
         if (L.model == SMCN_MODEL_OGLM) {
             row[L.ys + 2] = L.o0 ? md[L.o0 + i] : 0.0;

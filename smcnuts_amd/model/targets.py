@@ -633,6 +633,50 @@ class WideGLMTarget(DeviceTarget):
         _glm_setup(self, limit, X, y, family, prior_sd, intercept, dispersion_prior)
 
 
+class ContinuousGLM(DeviceTarget):
+    """Regression for a continuous response on the device: GLMTarget's linear predictor and priors, eta = [b_0 +] X b with
+    independent N(0, prior_sd_c^2) priors on the Dc = p + intercept coefficients (the intercept is coordinate 0), and
+      gamma_log:  y_i ~ gamma(shape, shape / e^eta_i)   (mean e^eta_i, variance mean^2 / shape; y finite and > 0)
+      student_t:  y_i ~ student_t(df, eta_i, sigma)     (df fixed by the caller, finite and > 0; y finite)
+    The last coordinate is tau = log shape / log sigma (D = Dc + 1 <= 64), with the prior tau ~ N(m, s^2) for
+    dispersion_prior = (m, s); `constrain` reports shape / sigma.  Coordinates are unconstrained;
+    log pi_phi = lpri + phi * llik.  Sampling with every L-kernel, tempering, shards, moments, summary(), covariance()
+    and the step-size probe as for any device target; the pointwise criteria, LOO, calibration and prediction are not
+    implemented for these families, and df is not estimated.
+
+    Data block (include/smcnuts_hip.h, SMCN_MODEL_CGLM):
+    [family (0 gamma_log, 1 student_t), n, p, intercept, df (0 for gamma_log), s_1..s_Dc, m, s, y_1..y_n, X (n x p,
+    row-major)]."""
+    model_id = _capi.MODEL_CGLM
+
+    def __init__(self, X, y, family="gamma_log", prior_sd=2.5, intercept=True, dispersion_prior=(0.0, 2.5),
+                 df=_checks.DEFAULT_DF):
+        who = type(self).__name__
+        _checks.continuous_family(who, family)
+        dfv = _checks.student_df(who, family, df)
+        tau_prior = _checks.scale_prior(who, dispersion_prior)
+        X = _checks.design(who, X)
+        n, p = X.shape
+        y = _checks.response(who, y, n)
+        _checks.some_rows(who, n)
+        ic = 1 if intercept else 0
+        Dc = p + ic
+        D = Dc + 1
+        if Dc < 1:
+            raise ValueError(f"{who}: no coefficients (p = 0 without an intercept)")
+        _checks.dim_limit(who, D, f"D = {D} coordinates ({Dc} coefficients and tau)")
+        _checks.finite(who, "X", X)
+        _checks.continuous_response(who, family, y)
+        s = _checks.prior_sds(who, "prior_sd", prior_sd, (Dc,), f"a scalar or one value per coefficient ({Dc})")
+        self.family, self.intercept = family, bool(intercept)
+        self.df = dfv if family == "student_t" else None
+        self.X, self.y, self.prior_sd = X.copy(), y.copy(), s.copy()
+        self.dispersion_prior = tau_prior
+        head = [float(_checks.CONTINUOUS_FAMILIES.index(family)), float(n), float(p), float(ic), dfv]
+        data = np.concatenate([head, s, tau_prior, y, X.reshape(-1)])
+        super().__init__(data, D, _coefficient_names(ic, p) + [_checks.CONTINUOUS_SCALE[family]])
+
+
 class HierarchicalGLM(PredictMixin, DeviceTarget):
     """Varying-intercept GLM on the device, non-centred: observations fall into J groups, group j has the intercept
     alpha_j = tau z_j,
@@ -897,6 +941,20 @@ def NegativeBinomialRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), 
     offset = _exposure_offset("NegativeBinomialRegression", offset, exposure)
     return GLMTarget(X, y, family="neg_binomial_2_log", prior_sd=prior_sd, intercept=intercept,
                      dispersion_prior=dispersion_prior, offset=offset, weights=weights)
+
+
+def GammaRegression(X, y, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True):
+    """Bayesian gamma regression with a log link, y ~ gamma(shape, shape / e^eta) with log shape ~ N(m, s^2):
+    ContinuousGLM(X, y, family="gamma_log", ...).  The last coordinate is log shape; constrain() reports shape."""
+    return ContinuousGLM(X, y, family="gamma_log", prior_sd=prior_sd, intercept=intercept,
+                         dispersion_prior=dispersion_prior)
+
+
+def RobustRegression(X, y, df=_checks.DEFAULT_DF, prior_sd=2.5, dispersion_prior=(0.0, 2.5), intercept=True):
+    """Bayesian robust linear regression, y ~ student_t(df, eta, sigma) with df fixed and log sigma ~ N(m, s^2):
+    ContinuousGLM(X, y, family="student_t", df=df, ...).  The last coordinate is log sigma; constrain() reports sigma."""
+    return ContinuousGLM(X, y, family="student_t", prior_sd=prior_sd, intercept=intercept,
+                         dispersion_prior=dispersion_prior, df=df)
 
 
 def StanModel(model_name, model_path=None, data_path=None):
